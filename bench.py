@@ -10,12 +10,16 @@ grad clip, AdamW step; by default forward + criterion + backward replay as
 ONE hipGraph.  Synthetic ZOD-shaped batches generated once
 and kept resident in HBM; random-init weights.
 
-  python bench.py                               # N=1, defaults
+  python bench.py                               # N=1, defaults: the headline figure only
+  python bench.py --full                        # + rooflines, kernel profile, eval leg, CPU baseline
+  python bench.py --dump-outputs DIR            # + the last timed step's outputs as DIR/<name>.npy
   python bench.py --gpus N                      # starts N ranks itself (launch_ranks)
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N         # DP over RCCL (C3), weak scaling
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ``--steps``
+steps and prints the contract keys (metric, value, unit, ms_per_step, ...)
+with the run's configuration.  With ``--full`` the line also carries
 ``roofline`` for the dominant HIP kernel (the grouped expert GEMM: kernel
 times from dispatch-stamped HIP events recorded by libmoe_hip itself -- in
 graph mode over eager steps right after the timed region, since ROCm 7.2
@@ -272,11 +276,19 @@ def rocprof_headline(e, g, src, match):
     return e
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: per-kernel events and "
+                         "rooflines, the eval leg, the model-FLOP count, the CPU baseline, --phase-timing, "
+                         "--dump-prof-records (each still has its own switch below); off: the timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): the loss it returns "
+                         "and its terms, and a fixed seeded sample of the gradients and of the updated weights it "
+                         "leaves; same arguments, same inputs, so two builds compare output for output")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: the workload's)")
     ap.add_argument("--spec-extra", default="", help="model-spec tokens appended to the workload's spec (A/B, "
@@ -316,7 +328,52 @@ def parse_args():
     ap.add_argument("--eval-steps", type=int, default=10,
                     help="eval leg after the training measurement: timed inference forwards of the same batch "
                          "(engine._evaluate's forward: model.eval(), no_grad, bf16 autocast); 0 skips it")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        for flag, given in (("--phase-timing", args.phase_timing), ("--dump-prof-records", args.dump_prof_records)):
+            if given:
+                ap.error(f"{flag} measures beyond the timed steps: add --full")
+    return args
+
+
+DUMP_SAMPLE = 1 << 20  # elements per sampled array (4 MiB as float32)
+
+
+def _sample_flat(tensors, n=DUMP_SAMPLE, seed=0):
+    """The tensors flattened and concatenated in order, as float32 on the host;
+    past ``n`` elements a fixed sample of them (indices drawn once from a seeded
+    host generator: the same elements in every run and every build)."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    if flat.numel() > n:
+        idx = torch.randint(flat.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(out_dir, step, loss):
+    """--dump-outputs: what the timed path computed in its last step, one
+    float32 ``<name>.npy`` each.  ``loss`` is what TrainStep.__call__ returned;
+    ``loss_*`` its weighted terms (one-graph step: the capture's static loss
+    tensors); ``grads_sample`` / ``params_sample`` the state the step leaves its
+    caller -- this step's gradients and the weights after its AdamW update --
+    as a seeded sample over the parameters in model order.  Called right after
+    the timed region, before anything else runs a step.  Returns the names."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    if step.stepper is not None:
+        for k, v in step.stepper.static_losses.items():
+            arrays[k] = v.detach().float().reshape(-1).cpu().numpy()
+    arrays["grads_sample"] = _sample_flat([p.grad if p.grad is not None else torch.zeros_like(p)
+                                           for p in step.params])
+    arrays["params_sample"] = _sample_flat(step.params)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
 
 
 def setup_dist(n_gpus):
@@ -543,8 +600,8 @@ def eval_leg(model, images, ctx, steps, warmup=3):
                     "hipGraph replay per input shape; batch resident in HBM, postprocess excluded"}
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
     world, rank, local = setup_dist(args.gpus)
     if rank == 0:
         heartbeat()
@@ -580,8 +637,8 @@ def main():
 
     graphs = args.graphs  # the EP layer's all-to-alls are fixed-capacity: capturable too
     # library-side kernel events around each MoE/MSDA launch: inside the timed
-    # region when eager; in eager steps right after it when graphed
-    timing = not args.no_kernel_timing
+    # region when eager; in eager steps right after it when graphed (--full)
+    timing = args.full and not args.no_kernel_timing
     ddp_local = local if (world > 1 and not graphs) else None
     step = TrainStep(model, SetCriterion(num_classes=1), images, ctx, graphs=graphs, world=world,
                      precision=args.precision, ddp_local=ddp_local,
@@ -599,12 +656,16 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(images, ctx, targets, num_boxes)
+        loss = step(images, ctx, targets, num_boxes)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     log(rank, f"timed {args.steps} steps: {1e3 * elapsed / args.steps:.2f} ms/step")
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before any later leg runs another step
+        dumped = dump_outputs(args.dump_outputs, step, loss)
+        log(rank, f"wrote {len(dumped)} output arrays to {args.dump_outputs}")
     phases = None
     if args.phase_timing:  # extra steps after the timed region, same execution mode
         step.phases = []
@@ -631,9 +692,9 @@ def main():
         prof_steps = args.profile_steps
     # the exchange accounting of the last TRAINING step (the eval leg's
     # forwards below run eval-mode BatchNorm: different activations, routing)
-    ep_stats = expert_parallel_stats(model, spec, world) if "-ep" in spec else None
+    ep_stats = expert_parallel_stats(model, spec, world) if args.full and "-ep" in spec else None
     ev = None
-    if args.eval_steps > 0:
+    if args.full and args.eval_steps > 0:
         log(rank, f"eval leg: {args.eval_steps} inference forwards")
         ev = eval_leg(model, images, ctx, args.eval_steps)
     el = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -655,6 +716,24 @@ def main():
     if rank == 0:
         images_total = world * batch * args.steps
         value = images_total / elapsed
+        result = {
+            "metric": METRIC, "value": round(value, 3), "unit": "images/sec", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": wl.get("dtype", "bf16"),
+            "data": "synthetic (ZOD-shaped batches resident in HBM, random-init weights)",
+            "config": {"workload": wl["desc"], "arch": spec, "global_batch": world * batch,
+                       "execution": ("hipGraph: forward + criterion (GPU matcher) + backward" if args.step_graph
+                                     else "hipGraph fwd/bwd") if graphs else "eager",
+                       "precision": "bf16 weights + fp32 master" if args.precision == "bf16" else "bf16 autocast",
+                       "img": f"{args.img_w}x{args.img_h} (padded to {data.pad_w}x{data.pad_h})",
+                       "parallelism": f"dp{world}" if "ep" not in spec else f"dp{world}+ep{world}",
+                       "rccl_world": rccl_world, "batch": batch},
+            "build": {"libmoe_hip_sha16": build_id, "precision": args.precision, "graphs": bool(graphs),
+                      "tune": list(args.tune), "spec_extra": args.spec_extra},
+            "full": bool(args.full),
+            **({"dumped_outputs": dumped} if dumped else {}),
+        }
+    if rank == 0 and args.full:
         pmc = load_pmc_traffic(args.workload)
         prof_elapsed = elapsed * prof_steps / args.steps  # share_of_step: per-step kernel time / step time
         roof = roofline_entry(merge_groups(ksum.get("grouped_gemm"), ksum.get("grouped_gemm_fp8")),
@@ -686,20 +765,7 @@ def main():
                            "roofline_time_frac": round(d["t_roof_ms"] / d["total_ms"], 4)}
             if d["flops"]:
                 kprof[name]["TFLOP_s"] = round(d["flops"] / sec / 1e12, 1)
-        result = {
-            "metric": METRIC, "value": round(value, 3), "unit": "images/sec", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": wl.get("dtype", "bf16"),
-            "data": "synthetic (ZOD-shaped batches resident in HBM, random-init weights)",
-            "config": {"workload": wl["desc"], "arch": spec, "global_batch": world * batch,
-                       "execution": ("hipGraph: forward + criterion (GPU matcher) + backward" if args.step_graph
-                                     else "hipGraph fwd/bwd") if graphs else "eager",
-                       "precision": "bf16 weights + fp32 master" if args.precision == "bf16" else "bf16 autocast",
-                       "img": f"{args.img_w}x{args.img_h} (padded to {data.pad_w}x{data.pad_h})",
-                       "parallelism": f"dp{world}" if "ep" not in spec else f"dp{world}+ep{world}",
-                       "rccl_world": rccl_world, "batch": batch},
-            "build": {"libmoe_hip_sha16": build_id, "precision": args.precision, "graphs": bool(graphs),
-                      "tune": list(args.tune), "spec_extra": args.spec_extra},
+        result.update({
             "roofline": roof, "roofline_dispatch": rd, "kernel_profile": kprof,
             "kernel_timing": None if not timing else (
                 f"libmoe_hip dispatch-stamped events over the {args.steps} timed steps" if not graphs else
@@ -709,7 +775,7 @@ def main():
             "dp_exchange": dp_exchange_bytes(model, world),
             **({"phases_gpu_host_ms": phases} if phases else {}),
             **({"expert_parallel": ep_stats} if ep_stats else {}),
-        }
+        })
     if world > 1:
         from src.rtdetr_moe.step import release_graphs
 
@@ -717,7 +783,7 @@ def main():
         step = None  # its captured graphs (C4: RCCL all-to-alls inside) go before the communicator
         release_graphs()
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_e2e_roofline:
             log(rank, "counting model FLOP per image (fp32 CPU fwd+bwd under FlopCounterMode)")
             try:
@@ -740,6 +806,7 @@ def main():
                 result["cpu_baseline"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
         else:
             result["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(result), flush=True)
 
 

@@ -13,6 +13,28 @@ for p in (str(ROOT), str(PKG)):
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 
+def _private_miopen_db():
+    """MIOpen appends every convolution it searches to its user database, and
+    bench.py (imported by the launcher tests) points that at the databases
+    shipped in multimodal-moe_amd/miopen_db.  The suite works on a copy of
+    them, so a test run starts from the same choices and leaves the committed
+    files as they are; child processes inherit the setting."""
+    if "MIOPEN_USER_DB_PATH" in os.environ:
+        return
+    import atexit
+    import shutil
+    import tempfile
+
+    d = tempfile.mkdtemp(prefix="moe_miopen_db_")
+    for f in (PKG / "miopen_db").glob("*.txt"):
+        shutil.copy(f, d)
+    os.environ["MIOPEN_USER_DB_PATH"] = d
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+
+
+_private_miopen_db()
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (run with -m gpu)")
     config.addinivalue_line("markers", "slow: longer CPU test")

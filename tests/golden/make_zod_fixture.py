@@ -22,9 +22,10 @@ box, the reference does not).
 Geometry (notes/experiment_protocol_camera.md:25): 1248x704 -- the S5 grid is
 22x39 = 858 tokens, the deformable-attention levels 88x156 / 44x78 / 22x39.
 The exporter is handed relative image paths, so its symlinks are relative and
-the fixture is relocatable.  dataset.yaml keeps the absolute ``path:`` the
-reference writes (/root/repo/tests/golden/zod_mini, valid on the GPU box too);
-the build's YoloDataset falls back to the yaml's directory when it is absent.
+the fixture is relocatable.  The reference writes its output directory as an
+absolute ``path:`` into dataset.yaml; this script replaces that one line with
+``path: .`` (YoloDataset resolves a relative path from the yaml's directory),
+so a checkout anywhere reads its own files.
 
 Usage:  python tests/golden/make_zod_fixture.py
 """
@@ -113,6 +114,12 @@ def main():
     if r.returncode != 0:
         raise SystemExit(r.stderr[-3000:])
     summary = json.loads(r.stdout.strip().splitlines()[-1])
+    # write_yolo_dataset_yaml records the absolute directory it wrote to; the
+    # committed fixture names its own directory instead, so that a checkout
+    # anywhere reads its own files and probes no path outside the tree
+    y = OUT / "dataset.yaml"
+    y.write_text("".join("path: .\n" if ln.startswith("path:") else ln
+                         for ln in y.read_text().splitlines(keepends=True)))
     expected = {"img_w": W, "img_h": H, "summary": summary,
                 "frames": [{"frame_id": fid, "split": s, "solar_context_bin": c} for fid, s, _b, _u, c in FRAMES]}
     (OUT / "expected.json").write_text(json.dumps(expected, indent=1) + "\n")

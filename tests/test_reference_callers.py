@@ -8,8 +8,8 @@ build's first, so ``from src.models.vision.rtdetr import ...`` (and
 ``src.models.vision.yolo``, ``src.paths``) resolve to this package while the
 scripts themselves are the reference's files, executed where they lie (no copy,
 no bytecode written: PYTHONDONTWRITEBYTECODE).  This is INTEGRATION.md 1's
-recipe.  Build-container only: skipped where /root/reference is absent (the GPU
-box), never imported by product code.  Config C1 (BASELINE.json configs[0]):
+recipe.  Runs only where MOE_REFERENCE_ROOT names a reference checkout (skipped
+otherwise), never imported by product code.  Config C1 (BASELINE.json configs[0]):
 RT-DETR-R18 + 4-expert top-1 MoE, 2 frames at 640x640, CPU.
 """
 from __future__ import annotations
@@ -24,10 +24,12 @@ import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "multimodal-moe_amd"
-REF = Path("/root/reference")
+# the reference checkout is no part of this repository: MOE_REFERENCE_ROOT names
+# one where there is one (nothing outside the tree is probed otherwise)
+REF = Path(os.environ["MOE_REFERENCE_ROOT"]) if os.environ.get("MOE_REFERENCE_ROOT") else None
 
-pytestmark = pytest.mark.skipif(not (REF / "scripts" / "train_rtdetr.py").exists(),
-                                reason="reference checkout not present (build container only)")
+pytestmark = pytest.mark.skipif(REF is None or not os.access(REF / "scripts" / "train_rtdetr.py", os.R_OK),
+                                reason="no reference checkout given (MOE_REFERENCE_ROOT unset or unreadable)")
 
 
 def _env(tmp_path):

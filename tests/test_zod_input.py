@@ -9,7 +9,8 @@ reference's on-disk format.
   /root/reference/scripts/export_coco_dataset.py:139-195
   (``annotations/instances_<split>.json``, ``images[].solar_context_bin`` as a
   bin label or null).
-* Reference-written export (skips where /root/reference is absent): the
+* Reference-written export (runs where MOE_REFERENCE_ROOT names a reference
+  checkout, skips otherwise; tests/golden/zod_mini holds such an export): the
   reference's own ``export_yolo_split`` / ``write_yolo_dataset_yaml`` /
   ``export_coco_split`` run in a child process on a small frames table; both
   readers must return the same boxes and context ids from it.
@@ -27,7 +28,9 @@ import numpy as np
 import pytest
 import torch
 
-REF = Path("/root/reference")
+# the reference checkout is no part of this repository: MOE_REFERENCE_ROOT names
+# one where there is one (nothing outside the tree is probed otherwise)
+REF = Path(os.environ["MOE_REFERENCE_ROOT"]) if os.environ.get("MOE_REFERENCE_ROOT") else None
 
 # content size of the exported (resized) frames and the padded network input
 W, H = 96, 60
@@ -166,7 +169,8 @@ _CHILD = textwrap.dedent("""
 """)
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree absent (GPU box)")
+@pytest.mark.skipif(REF is None or not os.access(REF, os.R_OK | os.X_OK),
+                    reason="no reference checkout given (MOE_REFERENCE_ROOT unset or unreadable)")
 def test_reference_written_export(tmp_path):
     """The reference's own exporters write the dataset (child process with the
     reference root first on sys.path, nothing imported into this process); the

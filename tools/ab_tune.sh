@@ -10,6 +10,6 @@ export MIOPEN_USER_DB_PATH=$O/db
 cd $GRAFT_REPO_ROOT
 for r in a1 b1 a2 b2; do
   T=""; [ "${r:0:1}" = "b" ] && T="--tune $KEY=$VB"
-  timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --eval-steps 0 $T "$@" > $O/$r.json 2> $O/$r.err || exit $?
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --eval-steps 0 $T "$@" > $O/$r.json 2> $O/$r.err || exit $?
   python3 -c "import json;b=json.load(open('$O/$r.json'));print('$r $KEY', b['value'], b['ms_per_step'], b['roofline'].get('avg_us'))"
 done

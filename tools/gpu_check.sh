@@ -12,7 +12,7 @@ echo "PYTEST $rc"; tail -4 $O/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?
 echo "SMOKE $rc"; tail -2 $O/smoke.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 420 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?
+timeout -k 10 420 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?
 echo "BENCH $rc"; tail -c 300 $O/bench.json
 [ $rc -eq 0 ] || exit $rc
 if [ $# -gt 0 ]; then

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O/fetch $O/write
 KRE="gemm_v|gemm_pair|gemm_triple|expert_ffn"
-ARGS="--workload $WL --no-cpu-baseline --no-graphs --steps 1 --warmup 1 --eval-steps 0 --no-e2e-roofline"
+ARGS="--full --workload $WL --no-cpu-baseline --no-graphs --steps 1 --warmup 1 --eval-steps 0 --no-e2e-roofline"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRE" --output-format csv -d $O/fetch -o p -- \
   python3 $R/bench.py $ARGS --dump-prof-records $O/records.json > $O/fetch/bench.json 2> $O/fetch/bench.err; rc=$?

@@ -13,6 +13,6 @@ echo "PYTEST $rc"; tail -15 $O/pytest_gpu.log
 timeout -k 10 420 python multimodal-moe_amd/kbench.py "$@" > $O/kbench.jsonl 2> $O/kbench.err; rc=$?
 echo "KBENCH $rc"; cat $O/kbench.jsonl; tail -3 $O/kbench.err
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 420 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err; rc=$?
+timeout -k 10 420 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; rc=$?
 echo "BENCH $rc"; cat $O/bench.json; tail -3 $O/bench.err
 exit $rc

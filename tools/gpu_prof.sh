@@ -16,12 +16,12 @@ for WL in "$@"; do
   O=$R/gpurun_out/$TAG/$WL
   mkdir -p $O/prof $O/pmc_fetch $O/pmc_write
   cd $R
-  timeout -k 10 420 python bench.py --workload $WL $X > $O/bench.json 2> $O/bench.err; rc=$?
+  timeout -k 10 420 python bench.py --full --workload $WL $X > $O/bench.json 2> $O/bench.err; rc=$?
   echo "BENCH $WL $rc"; tail -c 400 $O/bench.json
   [ $rc -eq 0 ] || exit $rc
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-    python3 $R/bench.py --workload $WL --no-cpu-baseline --eval-steps 0 $X > $O/prof/bench.json 2> $O/prof/bench.err; rc=$?
+    python3 $R/bench.py --full --workload $WL --no-cpu-baseline --eval-steps 0 $X > $O/prof/bench.json 2> $O/prof/bench.err; rc=$?
   echo "ROCPROF $WL $rc"
   [ $rc -eq 0 ] || exit $rc
   timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRE" --output-format csv -d $O/pmc_fetch -o p -- \

@@ -9,7 +9,7 @@ MOE_PARITY_REPORT=$O/parity.json timeout -k 10 900 python -u -m pytest tests -m 
   --timeout-method thread > $O/pytest_gpu.log 2>&1; rc=$?
 echo "PYTEST $rc"; tail -4 $O/pytest_gpu.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-timeout -k 10 420 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?
+timeout -k 10 420 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?
 echo "BENCH $rc"; tail -c 600 $O/bench.json
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 400 python multimodal-moe_amd/kbench.py "$@" > $O/kbench.jsonl 2> $O/kbench.err; rc=$?
