@@ -771,6 +771,18 @@ int rtdetr_attn_bwd(const void* q, long long ldq, const void* k, long long ldk, 
                     const void* o, long long ldo, const void* dout, long long lddo, const float* lse, float* delta,
                     void* dq, long long lddq, void* dk, long long lddk, void* dv, long long lddv, int B, int H,
                     int L, int head_dim, float scale, hipStream_t stream);
+/* The same two with a segment mask (RT-DETR's contrastive denoising queries):
+ * seg is a device vector of L int32 ids shared by all images and heads, and key
+ * k is visible to query q iff seg[k] < 0 (a shared token) or seg[k] == seg[q].
+ * Every query sees itself, so lse stays finite.  No L x L mask is read: the rule
+ * is evaluated in registers.  seg must be non-NULL and 4-byte aligned. */
+int rtdetr_attn_fwd_seg(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
+                        void* o, long long ldo, float* lse, int B, int H, int L, int head_dim, float scale,
+                        hipStream_t stream, const int32_t* seg);
+int rtdetr_attn_bwd_seg(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
+                        const void* o, long long ldo, const void* dout, long long lddo, const float* lse,
+                        float* delta, void* dq, long long lddq, void* dk, long long lddk, void* dv, long long lddv,
+                        int B, int H, int L, int head_dim, float scale, hipStream_t stream, const int32_t* seg);
 
 /* Implicit-GEMM convolutions of the RT-DETR body (the
  * backbone and the HybridEncoder's RepVGG / CSP convolutions, which the

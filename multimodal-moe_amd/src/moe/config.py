@@ -11,6 +11,8 @@ local architecture spec (no network fetch), e.g.::
     rtdetr-r50-moe16-top2-ep8-epmb0    same, every layer at ep_capacity_factor (no lossless budget)
     rtdetr-r50-moe32-top4-cf1.25-fp8   C5: capacity factor 1.25, fp8 experts
     rtdetr-r50                    dense FFN (no MoE)
+    rtdetr-r50-moe8-top2-dn100    C2 trained with ~100 contrastive denoising queries per image
+                                  (-dn<N>: src/rtdetr_moe/denoising.py; default 0 = none)
 """
 from __future__ import annotations
 
@@ -78,6 +80,7 @@ class ModelSpec:
     backbone: str = "r50"          # r18 | r34 | r50 | r101
     moe: MoEConfig | None = field(default_factory=MoEConfig)
     num_decoder_layers: int | None = None  # default by backbone (6 for r50, 3 for r18)
+    num_denoising: int = 0         # contrastive denoising queries per image in training (-dn<N>; 0 = off)
     raw: str = ""
 
 
@@ -85,7 +88,7 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>]``."""
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>]``."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
         raise ValueError(f"{spec!r} is a weights file, not an architecture spec")
@@ -124,6 +127,10 @@ def parse_moe_spec(spec: str) -> ModelSpec:
             moe.expert_parallel = True
         elif tok.startswith("dec"):
             out.num_decoder_layers = int(tok[3:])
+        elif tok.startswith("dn"):
+            out.num_denoising = int(tok[2:])
+            if out.num_denoising < 0:
+                raise ValueError(f"negative denoising query count in model spec {spec!r}")
         else:
             raise ValueError(f"unknown token {tok!r} in model spec {spec!r}")
     if moe is not None:

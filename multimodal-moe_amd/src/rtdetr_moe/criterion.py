@@ -231,6 +231,77 @@ class SetCriterion(nn.Module):
         parts = {n + suffix: det[s_, k] for s_, (suffix, _) in enumerate(sets) for k, n in enumerate(names)}
         return total, parts
 
+    # -- contrastive denoising queries (denoising.py) -----------------------
+    @staticmethod
+    def _dn_names(n):
+        """Suffixes of n denoising sets, the final layer's last."""
+        return [f"_dn_aux{i}" for i in range(n - 1)] + ["_dn"]
+
+    def dn_fused_ok(self, dn_outputs, M):
+        lg = dn_outputs[-1]["pred_logits"]
+        B, _, C = lg.shape
+        return lg.is_cuda and self.gamma == 2.0 and B * 2 * M * C * 4 <= 64 * 1024 and M <= 1024
+
+    def dn_losses(self, dn_outputs, tgt_boxes, tgt_labels, n_valid, num_boxes, G, fused=None):
+        """Losses of the denoising queries (one {pred_logits, pred_boxes} per
+        decoder layer, the final layer's last; [B, 2 M G, .]) under the fixed
+        assignment: target slot j < n_valid[b] belongs to the positive query
+        g 2M + j of every group g, every other denoising query is background.
+        VFL, L1 and GIoU with the matching sets' weights, normalised by
+        num_boxes G -> {"loss_*_dn", "loss_*_dn_aux{i}"}.  Fixed shapes, no host
+        sync.  fused (default: on the GPU when the shapes allow) evaluates them
+        with rtdetr_set_criterion_loss / _loss_bwd: every group viewed as its
+        own prediction set [S G, B, 2M, C] with the constant assignment
+        assign[m] = m, summed over the groups and divided by G."""
+        logits = torch.stack([o["pred_logits"] for o in dn_outputs]).float()  # [S, B, Qdn, C]
+        boxes = torch.stack([o["pred_boxes"] for o in dn_outputs]).float()
+        S, B, Qdn, C = logits.shape
+        M = tgt_boxes.shape[1]
+        if Qdn != 2 * M * G:
+            raise ValueError(f"dn_losses: {Qdn} denoising queries are not 2 x {M} slots x {G} groups")
+        dev = logits.device
+        names = self._dn_names(S)
+        if fused is None:
+            fused = self.dn_fused_ok(dn_outputs, M)
+        if fused:
+            def per_group(t):  # [S, B, G 2M, .] -> [S G, B, 2M, .]
+                return t.view(S, B, G, 2 * M, -1).permute(0, 2, 1, 3, 4).reshape(S * G, B, 2 * M, -1)
+
+            assign = torch.arange(M, dtype=torch.int32, device=dev).expand(S * G, B, M).contiguous()
+            status = torch.zeros(1, dtype=torch.int32, device=dev)  # (no matcher: stays 0)
+            nb = torch.as_tensor(num_boxes, dtype=torch.float32, device=dev)
+            comps, _ = _SetLossHip.apply(per_group(logits), per_group(boxes), tgt_boxes, tgt_labels,
+                                         n_valid.to(torch.int32), nb, status, self.alpha, assign)
+            comps = comps.view(S, G, 3).sum(1) / G
+            vfl, l1, lg = comps[:, 0], comps[:, 1], comps[:, 2]
+        else:
+            norm = num_boxes * G
+            tb = tgt_boxes.float()
+            mask = (torch.arange(M, device=dev)[None, :] < n_valid[:, None]).to(logits.dtype)  # [B, M]
+            pos = boxes.view(S, B, G, 2, M, 4)[:, :, :, 0]                                     # [S, B, G, M, 4]
+            tgt = tb[None, :, None].expand(S, B, G, M, 4)
+            iou, giou = _paired_iou_giou(box_cxcywh_to_xyxy(pos).reshape(-1, 4),
+                                         box_cxcywh_to_xyxy(tgt).reshape(-1, 4))
+            iou, giou = iou.view(S, B, G, M), giou.view(S, B, G, M)
+            m4 = mask[None, :, None, :]
+            l1 = ((pos - tgt).abs().sum(-1) * m4).sum((1, 2, 3)) / norm
+            lg = ((1.0 - giou) * m4).sum((1, 2, 3)) / norm
+            cls = (tgt_labels.long()[..., None] == torch.arange(C, device=dev)).to(logits.dtype) * mask[..., None]
+            onehot_pos = cls[None, :, None].expand(S, B, G, M, C)
+            zeros = torch.zeros_like(onehot_pos)
+            onehot = torch.stack([onehot_pos, zeros], 3).reshape(S, B, Qdn, C)
+            score = torch.stack([onehot_pos * iou.detach()[..., None], zeros], 3).reshape(S, B, Qdn, C)
+            pred = logits.sigmoid().detach()
+            weight = self.alpha * pred.pow(self.gamma) * (1 - onehot) + score
+            vfl = F.binary_cross_entropy_with_logits(logits, score, weight=weight, reduction="none")
+            vfl = vfl.sum((1, 2, 3)) / norm
+        losses = {}
+        for s_, suffix in enumerate(names):
+            losses["loss_vfl" + suffix] = vfl[s_] * self.w["loss_vfl"]
+            losses["loss_bbox" + suffix] = l1[s_] * self.w["loss_bbox"]
+            losses["loss_giou" + suffix] = lg[s_] * self.w["loss_giou"]
+        return losses
+
     def fused_ok(self, outputs, M):
         lg = outputs["pred_logits"]
         B, Q, C = lg.shape
@@ -298,10 +369,12 @@ class SetCriterion(nn.Module):
 class _SetLossHip(torch.autograd.Function):
     """Matching + VFL/L1/GIoU losses of all prediction sets in three HIP
     launches (rtdetr_set_criterion_match / _loss), their gradients computed in
-    the same pass and scaled in the backward (rtdetr_set_criterion_loss_bwd)."""
+    the same pass and scaled in the backward (rtdetr_set_criterion_loss_bwd).
+    With a given ``assign`` (int32 [S, B, M]: the query of each target slot;
+    the denoising queries' fixed assignment) the matcher is not launched."""
 
     @staticmethod
-    def forward(ctx, logits, boxes, tgt_boxes, tgt_labels, n_valid, num_boxes, status, vfl_alpha):
+    def forward(ctx, logits, boxes, tgt_boxes, tgt_labels, n_valid, num_boxes, status, vfl_alpha, assign=None):
         from ..moe import _lib as L
 
         S, B, Q, C = logits.shape
@@ -309,11 +382,17 @@ class _SetLossHip(torch.autograd.Function):
         lg, bx = logits.contiguous(), boxes.contiguous()
         tb, tl, nv = tgt_boxes.float().contiguous(), tgt_labels.to(torch.int32).contiguous(), n_valid.contiguous()
         nb = num_boxes.float().reshape(1).contiguous()
-        assign = torch.empty((S, B, M), dtype=torch.int32, device=lg.device)
         s = L._stream()
-        L._check(L.lib().rtdetr_set_criterion_match(lg.data_ptr(), bx.data_ptr(), tb.data_ptr(), tl.data_ptr(),
-                                                    nv.data_ptr(), S, B, Q, C, M, assign.data_ptr(),
-                                                    status.data_ptr(), s), "rtdetr_set_criterion_match")
+        if assign is None:
+            assign = torch.empty((S, B, M), dtype=torch.int32, device=lg.device)
+            L._check(L.lib().rtdetr_set_criterion_match(lg.data_ptr(), bx.data_ptr(), tb.data_ptr(), tl.data_ptr(),
+                                                        nv.data_ptr(), S, B, Q, C, M, assign.data_ptr(),
+                                                        status.data_ptr(), s), "rtdetr_set_criterion_match")
+        else:
+            L._need(assign, torch.int32, "assign")
+            if assign.shape != (S, B, M):
+                raise L.MoEKernelError(f"assign: expected shape {(S, B, M)}, got {tuple(assign.shape)}")
+            assign = assign.clone()
         comps = torch.empty((S, 3), dtype=torch.float32, device=lg.device)
         d_lg = torch.empty_like(lg)
         d_l1 = torch.empty_like(bx)
@@ -338,7 +417,7 @@ class _SetLossHip(torch.autograd.Function):
         L._check(L.lib().rtdetr_set_criterion_loss_bwd(g.data_ptr(), S, B, Q, C, d_lg.data_ptr(), d_l1.data_ptr(),
                                                        d_gi.data_ptr(), g_lg.data_ptr(), g_bx.data_ptr(),
                                                        L._stream()), "rtdetr_set_criterion_loss_bwd")
-        return g_lg, g_bx, None, None, None, None, None, None
+        return g_lg, g_bx, None, None, None, None, None, None, None
 
 
 PAD_BOX = (0.5, 0.5, 0.1, 0.1)  # finite stand-in for padded target slots (masked out of every loss)

@@ -441,9 +441,9 @@ class TransformerDecoderLayer(nn.Module):
         self.ffn = make_ffn(d, hidden, moe, act="relu")
         self.norm3 = AddLayerNorm(d)
 
-    def forward(self, tgt, ref_boxes, memory, shapes, query_pos, ctx, vslot=None):
+    def forward(self, tgt, ref_boxes, memory, shapes, query_pos, ctx, vslot=None, seg=None):
         # t1 and the cross-attention query t1 + query_pos from one LayerNorm launch
-        tgt, q = self.norm1.with_pos(tgt, self.self_attn(tgt + query_pos, tgt), query_pos)
+        tgt, q = self.norm1.with_pos(tgt, self.self_attn(tgt + query_pos, tgt, seg), query_pos)
         tgt = self.norm2(tgt, self.cross_attn(q, ref_boxes, memory, shapes, vslot))
         tgt = self.norm3(self.ffn(tgt, ctx, residual=True))  # tgt + FFN(tgt)
         return tgt
@@ -452,8 +452,9 @@ class TransformerDecoderLayer(nn.Module):
 class RTDETRDecoder(nn.Module):
     def __init__(self, num_classes=1, hidden=256, feat_channels=(256, 256, 256), feat_strides=(8, 16, 32),
                  num_queries=300, num_layers=6, nhead=8, dim_feedforward=1024, npoints=4,
-                 moe: MoEConfig | None = None):
+                 moe: MoEConfig | None = None, num_denoising: int = 0):
         super().__init__()
+        self.num_denoising = num_denoising
         self.hidden = hidden
         self.num_queries = num_queries
         self.num_classes = num_classes
@@ -469,7 +470,16 @@ class RTDETRDecoder(nn.Module):
         self.enc_bbox_head = MLP(hidden, hidden, 4, 3)
         self.dec_score_head = nn.ModuleList([TokenLinear(hidden, num_classes) for _ in range(num_layers)])
         self.dec_bbox_head = nn.ModuleList([MLP(hidden, hidden, 4, 3) for _ in range(num_layers)])
+        if num_denoising > 0:
+            # content embedding of the denoising queries' (noised) class labels
+            # (denoising.py); row num_classes -- padded target slots -- is held at
+            # zero: it never enters the lookup, so its gradient is zero too
+            self.denoising_class_embed = nn.Parameter(torch.empty(num_classes + 1, hidden))
+            nn.init.normal_(self.denoising_class_embed)
+            with torch.no_grad():
+                self.denoising_class_embed[num_classes].zero_()
         self._anchor_cache = {}
+        self._seg_cache = {}
         # query selection of the last forward ([B, Q] token indices), and an
         # optional override replayed instead of the top-k (tests/test_gpu_model_parity.py
         # feeds the CPU run's selection to the GPU run so both decode the same queries)
@@ -579,7 +589,29 @@ class RTDETRDecoder(nn.Module):
         shapes = [tuple(f.shape[-2:]) for f in proj]
         return torch.cat([f.flatten(2).permute(0, 2, 1) for f in proj], 1).contiguous(), shapes  # [B, S, d]
 
-    def forward(self, feats, ctx):
+    def _dn_embed(self, labels, dtype):
+        """denoising_class_embed[labels] as a one-hot product (a GEMM each way:
+        capturable in a hipGraph, and a deterministic backward, which
+        embedding's atomic scatter is not); labels == num_classes -> 0."""
+        classes = torch.arange(self.num_classes, device=labels.device)
+        onehot = (labels[..., None] == classes).to(dtype)  # (F.one_hot reads min / max back to the host)
+        return onehot @ self.denoising_class_embed[:-1].to(dtype)
+
+    def _segments(self, G, M, Q, device):
+        key = (G, M, Q, device)
+        if key not in self._seg_cache:
+            from .denoising import segments
+
+            self._seg_cache[key] = segments(G, M, Q, device)
+        return self._seg_cache[key]
+
+    def forward(self, feats, ctx, dn=None):
+        """dn = (labels int64 [B, Qdn], ref_unact fp32 [B, Qdn, 4], G) of
+        denoising.make_denoising: in training mode the denoising queries run
+        through the layers in front of the matching queries, under the segment
+        mask, and come back as out["dn_outputs"] / out["dn_meta"]."""
+        if dn is not None and not (self.training and self.num_denoising > 0):
+            dn = None
         memory, shapes = self._memory(feats)
         B = memory.shape[0]
         anchors, valid = self._anchors(shapes, memory.device, torch.float32)
@@ -614,11 +646,18 @@ class RTDETRDecoder(nn.Module):
         enc_topk_boxes = ref_unact.sigmoid()
         tgt = sel.detach()
         ref_detach = ref_unact.detach().sigmoid()
+        seg, Qdn = None, 0
+        if dn is not None:
+            dn_labels, dn_unact, G = dn
+            Qdn = dn_labels.shape[1]
+            tgt = torch.cat([self._dn_embed(dn_labels, tgt.dtype), tgt], 1)
+            ref_detach = torch.cat([dn_unact.float(), ref_unact.detach()], 1).sigmoid()
+            seg = self._segments(G, Qdn // (2 * G), self.num_queries, tgt.device)
         ref = ref_detach
         dec_logits, dec_boxes = [], []
         for i, layer in enumerate(self.layers):
             query_pos = self.query_pos_head(ref_detach.to(tgt.dtype))
-            tgt = layer(tgt, ref_detach, memory, shapes, query_pos, ctx, vslots[i])
+            tgt = layer(tgt, ref_detach, memory, shapes, query_pos, ctx, vslots[i], seg)
             # boxes_i = sigmoid(delta_i + inverse_sigmoid(ref)) with a gradient to
             # the previous layer's boxes; the next reference is the same value
             # without it (upstream: inter on ref_detach, boxes on ref)
@@ -627,7 +666,15 @@ class RTDETRDecoder(nn.Module):
             dec_boxes.append(boxes)
             ref = inter
             ref_detach = inter.detach()
+        dn_outputs = None
+        if dn is not None:  # split every layer's outputs at Qdn: denoising part | matching part
+            dn_outputs = [{"pred_logits": a[:, :Qdn], "pred_boxes": b[:, :Qdn]} for a, b in zip(dec_logits, dec_boxes)]
+            dec_logits = [a[:, Qdn:] for a in dec_logits]
+            dec_boxes = [b[:, Qdn:] for b in dec_boxes]
         out = {"pred_logits": dec_logits[-1], "pred_boxes": dec_boxes[-1],
                "aux_outputs": [{"pred_logits": a, "pred_boxes": b} for a, b in zip(dec_logits[:-1], dec_boxes[:-1])],
                "enc_outputs": {"pred_logits": enc_topk_logits, "pred_boxes": enc_topk_boxes}}
+        if dn_outputs is not None:
+            out["dn_outputs"] = dn_outputs
+            out["dn_meta"] = {"groups": G, "slots": Qdn // (2 * G)}
         return out

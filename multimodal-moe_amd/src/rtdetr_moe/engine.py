@@ -345,7 +345,7 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
                                  weight_decay=a.weight_decay, clip_norm=a.clip_norm, graphs=on_gpu, world=world,
                                  precision="bf16" if on_gpu else "fp32",
                                  ddp_local=None, targets=tg if on_gpu else None,
-                                 num_boxes=float(num_boxes))
+                                 num_boxes=float(num_boxes), seed=a.seed)
                 shape = tuple(images.shape)
             if on_gpu and tuple(images.shape) != shape:
                 raise RuntimeError(f"batch shape {tuple(images.shape)} differs from the captured {shape}")

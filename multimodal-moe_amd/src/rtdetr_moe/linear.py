@@ -556,10 +556,13 @@ class _SelfAttentionHIP(torch.autograd.Function):
     (rtdetr_attn_fwd / rtdetr_attn_bwd, csrc/attn.hip), reading q and k in
     place from the fused [q | k] projection output [B, L, 2d] and v from
     [B, L, d]; o comes back as [B, L, d] (heads concatenated), so no head
-    transposes in either direction.  Head dim 32 only (RT-DETR: d 256, 8 heads)."""
+    transposes in either direction.  Head dim 32 only (RT-DETR: d 256, 8 heads).
+    seg (optional, int32 [L] on the GPU): segment ids shared by all images and
+    heads; key k is visible to query q iff seg[k] < 0 or seg[k] == seg[q]
+    (rtdetr_attn_fwd_seg / rtdetr_attn_bwd_seg)."""
 
     @staticmethod
-    def forward(ctx, qk, v, H):
+    def forward(ctx, qk, v, H, seg=None):
         from ..moe import _lib as L
 
         B, T, d2 = qk.shape
@@ -572,9 +575,16 @@ class _SelfAttentionHIP(torch.autograd.Function):
         o = torch.empty((B, T, d), dtype=torch.bfloat16, device=qk.device)
         lse = torch.empty((B, H, T), dtype=torch.float32, device=qk.device)
         scale = 1.0 / math.sqrt(d // H)
-        L._check(L.lib().rtdetr_attn_fwd(qk.data_ptr(), d2, qk.data_ptr() + 2 * d, d2, v.data_ptr(), d,
-                                         o.data_ptr(), d, lse.data_ptr(), B, H, T, d // H, scale, L._stream()),
-                 "rtdetr_attn_fwd")
+        args = (qk.data_ptr(), d2, qk.data_ptr() + 2 * d, d2, v.data_ptr(), d, o.data_ptr(), d, lse.data_ptr(),
+                B, H, T, d // H, scale, L._stream())
+        if seg is None:
+            L._check(L.lib().rtdetr_attn_fwd(*args), "rtdetr_attn_fwd")
+        else:
+            L._need(seg, torch.int32, "seg")
+            if seg.shape != (T,):
+                raise L.MoEKernelError(f"seg: expected shape ({T},), got {tuple(seg.shape)}")
+            L._check(L.lib().rtdetr_attn_fwd_seg(*args, seg.data_ptr()), "rtdetr_attn_fwd_seg")
+        ctx.seg = seg
         ctx.save_for_backward(qk, v, o, lse)
         ctx.H, ctx.scale = H, scale
         return o
@@ -591,17 +601,28 @@ class _SelfAttentionHIP(torch.autograd.Function):
         dqk = torch.empty_like(qk)
         dv = torch.empty_like(v)
         delta = torch.empty_like(lse)
-        L._check(L.lib().rtdetr_attn_bwd(qk.data_ptr(), d2, qk.data_ptr() + 2 * d, d2, v.data_ptr(), d,
-                                         o.data_ptr(), d, do.data_ptr(), d, lse.data_ptr(), delta.data_ptr(),
-                                         dqk.data_ptr(), d2, dqk.data_ptr() + 2 * d, d2, dv.data_ptr(), d,
-                                         B, H, T, d // H, ctx.scale, L._stream()), "rtdetr_attn_bwd")
-        return dqk.to(ctx.in_dtypes[0]), dv.to(ctx.in_dtypes[1]), None
+        args = (qk.data_ptr(), d2, qk.data_ptr() + 2 * d, d2, v.data_ptr(), d, o.data_ptr(), d, do.data_ptr(), d,
+                lse.data_ptr(), delta.data_ptr(), dqk.data_ptr(), d2, dqk.data_ptr() + 2 * d, d2, dv.data_ptr(), d,
+                B, H, T, d // H, ctx.scale, L._stream())
+        if ctx.seg is None:
+            L._check(L.lib().rtdetr_attn_bwd(*args), "rtdetr_attn_bwd")
+        else:
+            L._check(L.lib().rtdetr_attn_bwd_seg(*args, ctx.seg.data_ptr()), "rtdetr_attn_bwd_seg")
+        return dqk.to(ctx.in_dtypes[0]), dv.to(ctx.in_dtypes[1]), None, None
 
 
-def self_attention_hip(qk: torch.Tensor, v: torch.Tensor, num_heads: int) -> torch.Tensor:
+def self_attention_hip(qk: torch.Tensor, v: torch.Tensor, num_heads: int,
+                       seg: torch.Tensor | None = None) -> torch.Tensor:
     """Multi-head self-attention of [B, L, 2d] fused q|k and [B, L, d] v on the
-    GPU (HIP kernels; no scaled_dot_product_attention)."""
-    return _SelfAttentionHIP.apply(qk, v, num_heads)
+    GPU (HIP kernels; no scaled_dot_product_attention).  seg: optional int32
+    [L] segment ids (see _SelfAttentionHIP); None is the unmasked attention."""
+    return _SelfAttentionHIP.apply(qk, v, num_heads, seg)
+
+
+def segment_mask(seg: torch.Tensor) -> torch.Tensor:
+    """The boolean [L, L] mask (True = query row sees key column) of a segment
+    id vector: key k is visible to query q iff seg[k] < 0 or seg[k] == seg[q]."""
+    return (seg[None, :] < 0) | (seg[None, :] == seg[:, None])
 
 
 class TokenSelfAttention(nn.Module):
@@ -633,8 +654,9 @@ class TokenSelfAttention(nn.Module):
                 return _TokenLinear.apply(x, w, b, dtype)
         return F.linear(x, w, b)
 
-    def forward(self, qk_in: torch.Tensor, v_in: torch.Tensor) -> torch.Tensor:
-        """qk_in = x + pos, v_in = x, both [B, L, d] -> [B, L, d]."""
+    def forward(self, qk_in: torch.Tensor, v_in: torch.Tensor, seg: torch.Tensor | None = None) -> torch.Tensor:
+        """qk_in = x + pos, v_in = x, both [B, L, d] -> [B, L, d]; seg: optional
+        int32 [L] segment ids masking the attention (segment_mask)."""
         B, L, d = qk_in.shape
         H = self.num_heads
         qk = self._proj(qk_in, 0, 2 * d)
@@ -642,8 +664,9 @@ class TokenSelfAttention(nn.Module):
         if qk.is_cuda and d % H == 0 and d // H == 32 and d % 8 == 0:
             # HIP attention (csrc/attn.hip, head_dim 32: RT-DETR's 256 / 8):
             # no Triton-generated SDPA kernels in the step
-            return self.out_proj(self_attention_hip(qk, v, H))
+            return self.out_proj(self_attention_hip(qk, v, H, seg))
         q, k = qk.split(d, -1)
         heads = lambda t: t.reshape(B, L, H, d // H).transpose(1, 2)  # noqa: E731
-        o = F.scaled_dot_product_attention(heads(q), heads(k), heads(v))
+        mask = None if seg is None else segment_mask(seg.to(qk.device))
+        o = F.scaled_dot_product_attention(heads(q), heads(k), heads(v), attn_mask=mask)
         return self.out_proj(o.transpose(1, 2).reshape(B, L, d))

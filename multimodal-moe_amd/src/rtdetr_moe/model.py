@@ -29,7 +29,8 @@ class RTDETRMoE(nn.Module):
                                      strides=self.backbone.out_strides, moe=spec.moe,
                                      expansion=0.5 if depth < 50 else 1.0)
         nl = spec.num_decoder_layers or _DEC_LAYERS[spec.backbone]
-        self.decoder = RTDETRDecoder(num_classes=num_classes, num_layers=nl, moe=spec.moe)
+        self.decoder = RTDETRDecoder(num_classes=num_classes, num_layers=nl, moe=spec.moe,
+                                     num_denoising=spec.num_denoising)
 
     @property
     def GFLOPs(self) -> float | None:
@@ -89,10 +90,12 @@ class RTDETRMoE(nn.Module):
     def moe_layers(self):
         return [m for m in self.modules() if isinstance(m, MoEFFN)]
 
-    def forward(self, images: torch.Tensor, ctx_ids: torch.Tensor | None = None):
+    def forward(self, images: torch.Tensor, ctx_ids: torch.Tensor | None = None, dn=None):
+        """dn: optional (labels, ref_unact, G) denoising pack (denoising.make_denoising),
+        used in training mode by a model built with a -dn<N> spec."""
         feats = self.backbone(images)
         feats = self.encoder(feats, ctx_ids)
-        return self.decoder(feats, ctx_ids)
+        return self.decoder(feats, ctx_ids, dn)
 
     def moe_aux_loss(self):
         terms = [m.aux_loss() for m in self.moe_layers()]

@@ -117,15 +117,17 @@ def release_graphs():
 
 class FlatOutputs(nn.Module):
     """Model wrapper whose forward returns a flat tuple of tensors (a graph
-    output signature): final, auxiliary and encoder logits/boxes + MoE aux loss."""
+    output signature): final, auxiliary and encoder logits/boxes, then -- with
+    a denoising pack ``dn`` (denoising.make_denoising) -- the denoising
+    logits/boxes of every decoder layer, + MoE aux loss."""
 
     def __init__(self, model: RTDETRMoE):
         super().__init__()
         self.model = model
 
-    def forward(self, images, ctx):
-        out = self.model(images, ctx)
-        sets = [out] + list(out["aux_outputs"]) + [out["enc_outputs"]]
+    def forward(self, images, ctx, dn=None):
+        out = self.model(images, ctx) if dn is None else self.model(images, ctx, dn)
+        sets = [out] + list(out["aux_outputs"]) + [out["enc_outputs"]] + list(out.get("dn_outputs", []))
         flat = []
         for s in sets:
             flat += [s["pred_logits"], s["pred_boxes"]]
@@ -134,11 +136,17 @@ class FlatOutputs(nn.Module):
         return tuple(flat)
 
     @staticmethod
-    def unflatten(flat):
+    def unflatten(flat, n_dn=0):
+        """n_dn: how many denoising pairs follow the encoder pair (0, or one per
+        decoder layer)."""
         pairs = [{"pred_logits": flat[i], "pred_boxes": flat[i + 1]} for i in range(0, len(flat) - 1, 2)]
+        dn_pairs = pairs[len(pairs) - n_dn:] if n_dn else []
+        pairs = pairs[:len(pairs) - n_dn] if n_dn else pairs
         out = dict(pairs[0])
         out["aux_outputs"] = pairs[1:-1]
         out["enc_outputs"] = pairs[-1]
+        if n_dn:
+            out["dn_outputs"] = dn_pairs
         return out, flat[-1]
 
 
@@ -223,6 +231,29 @@ class GraphedModel:
         return _ReplayFn.apply(self, self.anchor)
 
 
+class DenoisingState:
+    """What a step needs to make denoising queries for a model built with a
+    -dn<N> spec: the query count, the decoder's class / layer counts, the
+    noise configuration and ONE device generator, created once per TrainStep
+    and seeded from the run's seed and the rank."""
+
+    def __init__(self, model: RTDETRMoE, device, seed=0, cfg=None):
+        from .denoising import DenoisingConfig
+
+        self.num_denoising = model.decoder.num_denoising
+        self.num_classes = model.decoder.num_classes
+        self.num_layers = len(model.decoder.layers)
+        self.cfg = cfg or DenoisingConfig()
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.generator = torch.Generator(device=device)
+        self.generator.manual_seed(int(seed) * 1000 + rank)
+
+    def make(self, tgt_boxes, tgt_labels, n_valid, G, out=None):
+        from .denoising import make_denoising
+
+        return make_denoising(tgt_boxes, tgt_labels, n_valid, self.num_classes, G, self.cfg, self.generator, out)
+
+
 class GraphedStep:
     """The whole differentiable step -- model forward, set criterion with the
     GPU Hungarian matcher (``SetCriterion.forward_padded``), backward to every
@@ -233,13 +264,18 @@ class GraphedStep:
     launches the optimizer.  Targets are padded to ``max_boxes`` per image;
     a batch with more boxes re-captures at the next multiple of 16; the new
     capture allocates new gradient buffers, announced through ``on_capture``
-    (TrainStep re-points ``p.grad`` and drops its flat all-reduce views)."""
+    (TrainStep re-points ``p.grad`` and drops its flat all-reduce views).
+    ``dn`` (a DenoisingState, for a model with denoising queries): the noised
+    labels and reference boxes live in static buffers sized from M, refreshed
+    by denoising.make_denoising next to the targets before each replay; their
+    losses (SetCriterion.dn_losses) are part of the captured loss."""
 
     def __init__(self, fn, criterion, params, images, ctx, targets, num_boxes, *, warmup=3, autocast=False,
-                 max_boxes=None, on_capture=None):
+                 max_boxes=None, on_capture=None, dn=None):
         from .criterion import pad_targets
 
         self.fn, self.criterion, self.params, self.autocast = fn, criterion, params, autocast
+        self.dn = dn
         self.on_capture = on_capture  # called with static_grads after every (re-)capture
         self.captures = 0
         dev = images.device
@@ -251,17 +287,50 @@ class GraphedStep:
         self.nb = torch.full((), float(num_boxes), dtype=torch.float32, device=dev)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.warmup = warmup
+        self._dn_alloc()
         self._capture()
+
+    def _dn_alloc(self):
+        """Static denoising buffers for the current M (G and Qdn follow M),
+        filled once for the warm-up and the capture without advancing the
+        generator: the first replay draws what an eager first step draws."""
+        self.dn_pack = None
+        if self.dn is None:
+            return
+        from .denoising import dn_shapes
+
+        G, Qdn = dn_shapes(self.M, self.dn.num_denoising)
+        B, dev = self.tb.shape[0], self.tb.device
+        self.dn_pack = (torch.empty((B, Qdn), dtype=torch.int64, device=dev),
+                        torch.empty((B, Qdn, 4), dtype=torch.float32, device=dev), G)
+        state = self.dn.generator.get_state()
+        self._dn_refresh()
+        self.dn.generator.set_state(state)
+
+    def _dn_refresh(self):
+        if self.dn_pack is not None:
+            self.dn.make(self.tb, self.tl, self.nv, self.dn_pack[2], out=self.dn_pack[:2])
 
     def _loss(self):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.autocast, cache_enabled=False):
-            flat = self.fn(self.static_images, self.static_ctx)
-        out, aux = FlatOutputs.unflatten(flat)
+            if self.dn_pack is None:
+                flat = self.fn(self.static_images, self.static_ctx)
+            else:
+                flat = self.fn(self.static_images, self.static_ctx, self.dn_pack)
+        n_dn = 0 if self.dn_pack is None else self.dn.num_layers
+        out, aux = FlatOutputs.unflatten(flat, n_dn)
         if _FUSED_CRIT and self.criterion.fused_ok(out, self.M):  # matching + losses in 3 HIP launches
             total, losses = self.criterion.loss_padded(out, self.tb, self.tl, self.nv, self.nb, self.status)
-            return total + aux, losses
-        losses = self.criterion.forward_padded(out, self.tb, self.tl, self.nv, self.nb, self.status)
-        return sum(losses.values()) + aux, losses
+            total = total + aux
+        else:
+            losses = self.criterion.forward_padded(out, self.tb, self.tl, self.nv, self.nb, self.status)
+            total = sum(losses.values()) + aux
+        if n_dn:  # fixed assignment, no matching
+            dnl = self.criterion.dn_losses(out["dn_outputs"], self.tb, self.tl, self.nv, self.nb, self.dn_pack[2],
+                                           fused=None if _FUSED_CRIT else False)
+            total = total + sum(dnl.values())
+            losses = {**losses, **dnl}
+        return total, losses
 
     def _grads(self, loss):
         """Gradients of every parameter: autograd for most, the conforming dense
@@ -315,12 +384,14 @@ class GraphedStep:
             self.M = (need + 15) // 16 * 16
             self.tb, self.tl, self.nv = pad_targets(targets, self.M)
             self.graph = None
+            self._dn_alloc()  # G and Qdn follow M
             self._capture()
         if images.data_ptr() != self.static_images.data_ptr():
             self.static_images.copy_(images)
         if ctx.data_ptr() != self.static_ctx.data_ptr():
             self.static_ctx.copy_(ctx)
         pad_targets(targets, self.M, self.tb, self.tl, self.nv)
+        self._dn_refresh()
         if torch.is_tensor(num_boxes):  # device scalar (e.g. all-reduced box count): no host sync
             self.nb.copy_(num_boxes.reshape(()))
         else:
@@ -404,8 +475,9 @@ class TrainStep:
 
     def __init__(self, model: RTDETRMoE, criterion, images, ctx, *, lr=1e-4, lr_backbone=1e-5,
                  weight_decay=1e-4, clip_norm=0.1, graphs=True, ddp_local=None, world=1, precision="bf16",
-                 targets=None, num_boxes=1.0, zero=None):
-        """zero: the ZeRO-1 optimizer (optim.ShardedDPAdamW) -- default: at
+                 targets=None, num_boxes=1.0, zero=None, seed=0):
+        """seed: the run's seed (the denoising queries' noise generator).
+        zero: the ZeRO-1 optimizer (optim.ShardedDPAdamW) -- default: at
         world > 1 unless MOE_ZERO=0; True also at world 1 (a world-1 process
         group: the RCCL reduce-scatter / all-gather branch on one GPU, tests)."""
         self.model = model
@@ -470,9 +542,14 @@ class TrainStep:
         images = self._cast_in(images)
         self.runner = None
         self.stepper = None
+        # contrastive denoising queries (a -dn<N> spec): one generator per TrainStep
+        self.dn = DenoisingState(model, images.device, seed) if model.decoder.num_denoising > 0 else None
+        self.last_losses = None  # {component: detached value} of the last step (criterion sets, _dn sets)
+        if graphs and self.dn is not None and targets is None:
+            raise ValueError("a model with denoising queries needs targets= for graphs=True (the whole-step graph)")
         if graphs and targets is not None:  # whole step as one graph (GPU matcher)
             self.stepper = GraphedStep(self.flat, criterion, self.params, images, ctx, targets, num_boxes,
-                                       autocast=self.precision == "amp", on_capture=self._bind_grads)
+                                       autocast=self.precision == "amp", on_capture=self._bind_grads, dn=self.dn)
             self.fn = None
             self.ddp = None
         elif graphs:
@@ -532,6 +609,7 @@ class TrainStep:
         self._mark("start")
         if self.stepper is not None:
             loss = self.stepper(self._cast_in(images), ctx, targets, num_boxes)
+            self.last_losses = self.stepper.static_losses
             self._mark("step_graph")
             self._optimizer_step()
             self._mark("optimizer")
@@ -539,11 +617,26 @@ class TrainStep:
         if self.runner is None:
             for p in self.params:
                 p.grad = None
+        dn_pack = None
+        if self.dn is not None:  # as GraphedStep, without static buffers
+            from .criterion import pad_targets
+            from .denoising import dn_shapes
+
+            need = max((len(t["boxes"]) for t in targets), default=0)
+            M = max(16, (need + 15) // 16 * 16)
+            tb, tl, nv = pad_targets(targets, M)
+            G, _ = dn_shapes(M, self.dn.num_denoising)
+            dn_pack = (*self.dn.make(tb, tl, nv, G), G)
         with torch.autocast(images.device.type, dtype=torch.bfloat16, enabled=self.precision == "amp"):
-            flat = self.fn(self._cast_in(images), ctx)
+            flat = self.fn(self._cast_in(images), ctx) if dn_pack is None else \
+                self.fn(self._cast_in(images), ctx, dn_pack)
         self._mark("forward")
-        out, aux = FlatOutputs.unflatten(flat)
+        out, aux = FlatOutputs.unflatten(flat, 0 if dn_pack is None else self.dn.num_layers)
         losses = self.criterion(out, targets, num_boxes)
+        if dn_pack is not None:
+            losses.update(self.criterion.dn_losses(out["dn_outputs"], tb, tl, nv, num_boxes, G,
+                                                   fused=None if _FUSED_CRIT else False))
+        self.last_losses = {k: v.detach() for k, v in losses.items()}
         loss = sum(losses.values()) + aux
         self._mark("criterion")
         if self.ddp is None and self.runner is None and images.is_cuda:
