@@ -918,6 +918,31 @@ int train_adamw_step(const void* tensors, const int32_t* chunks, int n_chunks, c
                      const float* lrs, int n_groups, float weight_decay, float beta1, float beta2, float eps,
                      hipStream_t stream);
 
+/* Exponential moving average of the weights (reference: Ultralytics' ModelEMA
+ * inside RTDETR.train, which validates and checkpoints the averaged model).
+ * `ema`: flat fp32 buffer laid out exactly like `master` (same flat_offset,
+ * same 8-element alignment), 16-B aligned; `ema_decay` in [0, 1): the HOST
+ * computes the schedule d_t = decay (1 - exp(-t / tau)).  The blend is
+ *   ema = fmaf(d, ema, (1 - d) * w)      (one rounded product, one fma)
+ * in both entry points, so the fused and the unfused average agree bit for bit.
+ *   train_adamw_ema_step     train_adamw_step, then the blend of the new fp32
+ *                            master while it is in registers; a tensor with
+ *                            grad_dtype 2 keeps its master and moments but is
+ *                            still averaged (every tensor, every update)
+ *   train_ema_update         the blend from any source: each record's `grad`
+ *                            is the source pointer (grad_dtype 0 bf16, 1 fp32;
+ *                            2: record skipped), flat_offset its place in
+ *                            `ema` -- the floating-point buffers (BatchNorm
+ *                            running statistics), or the masters after a plain
+ *                            train_adamw_step (the unfused A/B path)
+ * n_chunks == 0 returns 0 without a launch. */
+int train_adamw_ema_step(const void* tensors, const int32_t* chunks, int n_chunks, const float* coef,
+                         float* master, float* exp_avg, float* exp_avg_sq, const int32_t* tensor_steps,
+                         const float* lrs, int n_groups, float weight_decay, float beta1, float beta2, float eps,
+                         float* ema, float ema_decay, hipStream_t stream);
+int train_ema_update(const void* tensors, const int32_t* chunks, int n_chunks, float* ema, float ema_decay,
+                     hipStream_t stream);
+
 /* Launch profiler (measurement only; no reference counterpart).
  * While enabled, every kernel launch of the library carries a hipEvent pair
  * stamped by its own dispatch packet (hipExtLaunchKernel: kernel execution

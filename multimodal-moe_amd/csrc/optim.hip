@@ -14,6 +14,15 @@
 // Masters, exp_avg and exp_avg_sq are flat fp32 buffers (each tensor's
 // segment starts at a multiple of 8 elements, so chunk interiors are
 // 16-B/32-B vector accesses).  HBM-bound: ~28 B per parameter per step.
+//
+// Exponential moving average of the weights (Ultralytics' ModelEMA, which the
+// reference's RTDETR.train validates and checkpoints): a fourth flat fp32
+// buffer laid out like the masters, ema = d ema + (1 - d) w after every update.
+//   train_adamw_ema_step    train_adamw_step + the blend of the new master
+//                           while it is still in registers (+8 B per parameter)
+//   train_ema_update        the same blend from any bf16 / fp32 source: the
+//                           floating-point buffers (BatchNorm statistics), and
+//                           the unfused A/B path over the masters
 #include "moe_common.h"
 #include "prof.h"
 
@@ -141,17 +150,64 @@ __global__ __launch_bounds__(1024) void grad_norm_finalize_kernel(const float* _
   }
 }
 
+// The EMA blend, shared by adamw_step_kernel<true> and ema_update_kernel so
+// that the fused and the unfused average agree bit for bit: one rounded
+// product, one fma.
+__device__ __forceinline__ float ema_blend(float ema, float p, float d, float omd) {
+#pragma clang fp contract(off)
+  const float q = omd * p;
+  return fmaf(d, ema, q);
+}
+
+// ema[0..8) = blend(ema, p) at element e of a tensor of numel elements (ep points at element e)
+__device__ __forceinline__ void ema_blend8(float* ep, const float (&p)[8], long long e, long long numel, float d) {
+  const float omd = 1.f - d;
+  if (e + 8 <= numel) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float4 x = reinterpret_cast<const float4*>(ep)[h];
+      reinterpret_cast<float4*>(ep)[h] =
+          make_float4(ema_blend(x.x, p[4 * h], d, omd), ema_blend(x.y, p[4 * h + 1], d, omd),
+                      ema_blend(x.z, p[4 * h + 2], d, omd), ema_blend(x.w, p[4 * h + 3], d, omd));
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (e + i < numel) ep[i] = ema_blend(ep[i], p[i], d, omd);
+  }
+}
+
+// EMA: also blend the new master into the flat average (train_adamw_ema_step);
+// a tensor without a gradient is still averaged (Ultralytics averages every
+// tensor on every update).  EMA = false is train_adamw_step's kernel.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_step_kernel(const OptTensor* __restrict__ tens,
                                                          const int2* __restrict__ chunks,
                                                          const float* __restrict__ coef,
                                                          float* __restrict__ master, float* __restrict__ exp_avg,
                                                          float* __restrict__ exp_avg_sq,
-                                                         const int32_t* __restrict__ tsteps, AdamArgs a) {
+                                                         const int32_t* __restrict__ tsteps, AdamArgs a,
+                                                         float* __restrict__ ema, float ema_decay) {
   const int2 ch = chunks[blockIdx.x];
   const OptTensor t = tens[ch.x];
   const long long e = (long long)ch.y * OPT_CHUNK + threadIdx.x * 8;
-  if (e >= t.numel || t.gdtype == 2) return;
+  if (e >= t.numel) return;
   const bool full = e + 8 <= t.numel;
+  if (t.gdtype == 2) {
+    if constexpr (EMA) {
+      const float* mp = master + t.moff + e;
+      float p[8];
+      if (full) {
+        const float4 x = reinterpret_cast<const float4*>(mp)[0], y = reinterpret_cast<const float4*>(mp)[1];
+        p[0] = x.x; p[1] = x.y; p[2] = x.z; p[3] = x.w; p[4] = y.x; p[5] = y.y; p[6] = y.z; p[7] = y.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) p[i] = (e + i < t.numel) ? mp[i] : 0.f;
+      }
+      ema_blend8(ema + t.moff + e, p, e, t.numel, ema_decay);
+    }
+    return;
+  }
   const float scale = coef[1];
   const float lr = a.lr[t.group];
   const float decay = 1.f - lr * a.wd;
@@ -226,6 +282,21 @@ __global__ __launch_bounds__(256) void adamw_step_kernel(const OptTensor* __rest
       }
     }
   }
+  if constexpr (EMA) ema_blend8(ema + t.moff + e, p, e, t.numel, ema_decay);
+}
+
+// ema = d ema + (1 - d) src for every record: grad = the source (gdtype 0 bf16,
+// 1 fp32), moff = its offset in the flat average.
+__global__ __launch_bounds__(256) void ema_update_kernel(const OptTensor* __restrict__ tens,
+                                                         const int2* __restrict__ chunks, float* __restrict__ ema,
+                                                         float ema_decay) {
+  const int2 ch = chunks[blockIdx.x];
+  const OptTensor t = tens[ch.x];
+  const long long e = (long long)ch.y * OPT_CHUNK + threadIdx.x * 8;
+  if (e >= t.numel || t.gdtype == 2) return;
+  float p[8];
+  load_grad8(t, e, e + 8 <= t.numel, p);
+  ema_blend8(ema + t.moff + e, p, e, t.numel, ema_decay);
 }
 
 }  // namespace moe
@@ -268,6 +339,30 @@ extern "C" int train_grad_norm_finalize(const float* partials, int n, float max_
   return check_launch("train_grad_norm_finalize");
 }
 
+static int adamw_launch(const char* name, const void* tensors, const int32_t* chunks, int n_chunks,
+                        const float* coef, float* master, float* exp_avg, float* exp_avg_sq,
+                        const int32_t* tensor_steps, const float* lrs, int n_groups, float weight_decay, float beta1,
+                        float beta2, float eps, float* ema, float ema_decay, bool with_ema, hipStream_t stream) {
+  AdamArgs a{};
+  for (int i = 0; i < n_groups; ++i) a.lr[i] = lrs[i];
+  a.wd = weight_decay;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  // bytes: per element grad (<= 4) + master/m/v read and written (24) + bf16 weight (<= 2) [+ ema read and written (8)]
+  ProfScope prof(stream, PROF_OPTIM, (with_ema ? 38.0 : 30.0) * OPT_CHUNK * n_chunks);
+  if (with_ema) {
+    MOE_LAUNCH(prof, adamw_step_kernel<true>, dim3(n_chunks), dim3(256), 0, stream,
+               static_cast<const OptTensor*>(tensors), reinterpret_cast<const int2*>(chunks), coef, master, exp_avg,
+               exp_avg_sq, tensor_steps, a, ema, ema_decay);
+  } else {
+    MOE_LAUNCH(prof, adamw_step_kernel<false>, dim3(n_chunks), dim3(256), 0, stream,
+               static_cast<const OptTensor*>(tensors), reinterpret_cast<const int2*>(chunks), coef, master, exp_avg,
+               exp_avg_sq, tensor_steps, a, ema, ema_decay);
+  }
+  return check_launch(name);
+}
+
 extern "C" int train_adamw_step(const void* tensors, const int32_t* chunks, int n_chunks, const float* coef,
                                 float* master, float* exp_avg, float* exp_avg_sq, const int32_t* tensor_steps,
                                 const float* lrs, int n_groups, float weight_decay, float beta1, float beta2,
@@ -277,15 +372,43 @@ extern "C" int train_adamw_step(const void* tensors, const int32_t* chunks, int 
     return fail("train_adamw_step: bad arguments");
   if (tensor_steps == nullptr) return fail("train_adamw_step: tensor_steps is NULL");
   if (n_chunks == 0) return 0;
-  AdamArgs a{};
-  for (int i = 0; i < n_groups; ++i) a.lr[i] = lrs[i];
-  a.wd = weight_decay;
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  // bytes: per element grad (<= 4) + master/m/v read and written (24) + bf16 weight (<= 2)
-  ProfScope prof(stream, PROF_OPTIM, 30.0 * OPT_CHUNK * n_chunks);
-  MOE_LAUNCH(prof, adamw_step_kernel, dim3(n_chunks), dim3(256), 0, stream, static_cast<const OptTensor*>(tensors),
-             reinterpret_cast<const int2*>(chunks), coef, master, exp_avg, exp_avg_sq, tensor_steps, a);
-  return check_launch("train_adamw_step");
+  return adamw_launch("train_adamw_step", tensors, chunks, n_chunks, coef, master, exp_avg, exp_avg_sq, tensor_steps,
+                      lrs, n_groups, weight_decay, beta1, beta2, eps, nullptr, 0.f, false, stream);
+}
+
+// 0, or fail(): the average must be a 16-B aligned buffer, the decay in [0, 1) (NaN refused)
+static int check_ema_args(const char* name, const float* ema, float ema_decay) {
+  if (ema == nullptr || reinterpret_cast<uintptr_t>(ema) % 16)
+    return fail(std::string(name) + ": ema must be non-NULL and 16-B aligned");
+  if (!(ema_decay >= 0.f && ema_decay < 1.f)) return fail(std::string(name) + ": ema_decay must lie in [0, 1)");
+  return 0;
+}
+
+extern "C" int train_adamw_ema_step(const void* tensors, const int32_t* chunks, int n_chunks, const float* coef,
+                                    float* master, float* exp_avg, float* exp_avg_sq, const int32_t* tensor_steps,
+                                    const float* lrs, int n_groups, float weight_decay, float beta1, float beta2,
+                                    float eps, float* ema, float ema_decay, hipStream_t stream) {
+  if (n_groups < 1 || n_groups > OPT_MAX_GROUPS || lrs == nullptr)
+    return fail("train_adamw_ema_step: 1..4 lr groups");
+  if (n_chunks < 0 || coef == nullptr || master == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr)
+    return fail("train_adamw_ema_step: bad arguments");
+  if (tensor_steps == nullptr) return fail("train_adamw_ema_step: tensor_steps is NULL");
+  if (int rc = check_ema_args("train_adamw_ema_step", ema, ema_decay)) return rc;
+  if (n_chunks == 0) return 0;
+  if (tensors == nullptr || chunks == nullptr) return fail("train_adamw_ema_step: bad arguments");
+  return adamw_launch("train_adamw_ema_step", tensors, chunks, n_chunks, coef, master, exp_avg, exp_avg_sq,
+                      tensor_steps, lrs, n_groups, weight_decay, beta1, beta2, eps, ema, ema_decay, true, stream);
+}
+
+extern "C" int train_ema_update(const void* tensors, const int32_t* chunks, int n_chunks, float* ema, float ema_decay,
+                                hipStream_t stream) {
+  if (n_chunks < 0 || (n_chunks > 0 && (tensors == nullptr || chunks == nullptr)))
+    return fail("train_ema_update: bad arguments");
+  if (int rc = check_ema_args("train_ema_update", ema, ema_decay)) return rc;
+  if (n_chunks == 0) return 0;
+  // bytes: per element source (<= 4) + ema read and written (8)
+  ProfScope prof(stream, PROF_OPTIM, 12.0 * OPT_CHUNK * n_chunks);
+  MOE_LAUNCH(prof, ema_update_kernel, dim3(n_chunks), dim3(256), 0, stream, static_cast<const OptTensor*>(tensors),
+             reinterpret_cast<const int2*>(chunks), ema, ema_decay);
+  return check_launch("train_ema_update");
 }

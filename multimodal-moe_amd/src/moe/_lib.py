@@ -146,6 +146,8 @@ SIGNATURES = {
     "train_grad_sqnorm": (_I, [_P, _P, _I, _P, _P]),
     "train_grad_norm_finalize": (_I, [_P, _I, _F, _F, _P, _P, _I, _P, _P]),
     "train_adamw_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _P]),
+    "train_adamw_ema_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _P, _F, _P]),
+    "train_ema_update": (_I, [_P, _P, _I, _P, _F, _P]),
     "moe_profile_enable": (_I, [_I]),
     "moe_profile_count": (_I, []),
     "moe_profile_get": (_I, [_I, _P, _P, _P, _P]),

@@ -13,6 +13,10 @@ local architecture spec (no network fetch), e.g.::
     rtdetr-r50                    dense FFN (no MoE)
     rtdetr-r50-moe8-top2-dn100    C2 trained with ~100 contrastive denoising queries per image
                                   (-dn<N>: src/rtdetr_moe/denoising.py; default 0 = none)
+    rtdetr-r50-moe8-top2-ema      C2 trained with an exponential moving average of the weights
+                                  (src/rtdetr_moe/ema.py; Ultralytics' decay 0.9999, tau 2000), which
+                                  is what gets validated and checkpointed.  -ema<d> sets the decay
+                                  (-ema0.999), -ematau<N> the warm-up constant; default: no average
 """
 from __future__ import annotations
 
@@ -81,6 +85,8 @@ class ModelSpec:
     moe: MoEConfig | None = field(default_factory=MoEConfig)
     num_decoder_layers: int | None = None  # default by backbone (6 for r50, 3 for r18)
     num_denoising: int = 0         # contrastive denoising queries per image in training (-dn<N>; 0 = off)
+    ema_decay: float = 0.0         # EMA of the weights in training (-ema = 0.9999, -ema<d>; 0 = off)
+    ema_tau: float = 2000.0        # EMA warm-up: d_t = ema_decay (1 - exp(-t / ema_tau)) (-ematau<N>)
     raw: str = ""
 
 
@@ -88,7 +94,7 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>]``."""
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>]``."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
         raise ValueError(f"{spec!r} is a weights file, not an architecture spec")
@@ -121,6 +127,14 @@ def parse_moe_spec(spec: str) -> ModelSpec:
         elif tok.startswith("epmb"):
             moe = moe or MoEConfig()
             moe.ep_lossless_mb = float(tok[4:])
+        elif tok.startswith("ematau"):  # before "ema"
+            out.ema_tau = float(tok[6:])
+            if not out.ema_tau > 0:
+                raise ValueError(f"EMA tau must be positive in model spec {spec!r}")
+        elif tok.startswith("ema"):
+            out.ema_decay = float(tok[3:]) if tok[3:] else 0.9999
+            if not 0.0 <= out.ema_decay < 1.0:
+                raise ValueError(f"EMA decay outside [0, 1) in model spec {spec!r}")
         elif tok.startswith("ep"):
             moe = moe or MoEConfig()
             moe.ep_size = int(tok[2:])

@@ -173,7 +173,10 @@ def resolve_spec(raw: str):
     return spec
 
 
-def save_checkpoint(path: Path, model: RTDETRMoE, epoch: int, fitness: float, optimizer=None, state_dict=None):
+def save_checkpoint(path: Path, model: RTDETRMoE, epoch: int, fitness: float, optimizer=None, state_dict=None,
+                    ema=None):
+    """ema: {"decay", "tau", "updates"} when ``state_dict`` holds the averaged
+    weights of a run with a weight average (ema.ModelEMA); the key is absent otherwise."""
     path.parent.mkdir(parents=True, exist_ok=True)
     sd = model.state_dict() if state_dict is None else state_dict
     ck = {"spec": model.spec.raw, "num_classes": model.num_classes, "epoch": int(epoch),
@@ -183,6 +186,8 @@ def save_checkpoint(path: Path, model: RTDETRMoE, epoch: int, fitness: float, op
         ck["moe_cfg"] = {k: v for k, v in asdict(model.spec.moe).items()}
     if optimizer is not None:
         ck["optimizer"] = optimizer.state_dict()
+    if ema is not None:
+        ck["ema"] = dict(ema)
     torch.save(ck, path)
 
 
@@ -261,6 +266,8 @@ class TrainArgs:
     weight_decay: float = 1e-4
     clip_norm: float = 0.1
     num_classes: int = 1
+    ema_decay: float | None = None  # weight average (ema.ModelEMA); None: the model spec's -ema token (0 = off)
+    ema_tau: float | None = None
 
 
 def _seed_all(seed: int):
@@ -293,7 +300,12 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
     CPU (config C1) fp32 eager with torch.optim.AdamW + clip_grad_norm_ (DDP
     over gloo when world > 1).  The graph has static shapes, so on the GPU the
     train loader drops a last partial batch (every step sees ``batch`` images);
-    the loss is accumulated on the device and read once per epoch."""
+    the loss is accumulated on the device and read once per epoch.
+    With a weight average (an -ema spec token or ``ema_decay``; ema.ModelEMA)
+    the validation runs on the averaged weights (``step.ema.applied()``), so
+    the fitness is the averaged model's, and the checkpoints carry the averaged
+    state dict plus an "ema" entry -- what Ultralytics' trainer validates and
+    saves."""
     from .step import TrainStep
 
     on_gpu = local != "cpu"
@@ -345,7 +357,8 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
                                  weight_decay=a.weight_decay, clip_norm=a.clip_norm, graphs=on_gpu, world=world,
                                  precision="bf16" if on_gpu else "fp32",
                                  ddp_local=None, targets=tg if on_gpu else None,
-                                 num_boxes=float(num_boxes), seed=a.seed)
+                                 num_boxes=float(num_boxes), seed=a.seed, ema_decay=a.ema_decay,
+                                 ema_tau=a.ema_tau)
                 shape = tuple(images.shape)
             if on_gpu and tuple(images.shape) != shape:
                 raise RuntimeError(f"batch shape {tuple(images.shape)} differs from the captured {shape}")
@@ -356,19 +369,31 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         # model's forward holds all-to-alls, so every rank runs the same
         # validation batches in lockstep (rank 0 keeps the metrics)
         metrics = None
-        if rank == 0 or ep:
+        ema = getattr(step, "ema", None)
+        sharded = getattr(getattr(step, "opt", None), "W", 1) > 1
+        # with a weight average the averaged model is validated; entering is a
+        # collective under the sharded optimizer (every rank enters, rank 0 evaluates)
+        if ema is not None and (rank == 0 or ep or sharded):
+            with ema.applied():
+                if rank == 0 or ep:
+                    metrics = _evaluate(core, a.data, "val", a.imgsz, a.batch, device, a.workers, a.seed)
+        elif rank == 0 or ep:
             metrics = _evaluate(core, a.data, "val", a.imgsz, a.batch, device, a.workers, a.seed)
-        # checkpoint state: fp32 masters; expert shards gathered to [E, ...] (collective)
+        # checkpoint state: fp32 masters (the fp32 averages with a weight average); expert
+        # shards gathered to [E, ...] (collective)
         # (a sharded data-parallel optimizer gathers masters collectively: every rank joins)
-        collective = ep or getattr(getattr(step, "opt", None), "W", 1) > 1
-        sd = gather_expert_shards(core, _master_state_dict(core, step)) if (rank == 0 or collective) else None
+        collective = ep or sharded
+        sd = None
+        if rank == 0 or collective:
+            sd = gather_expert_shards(core, _master_state_dict(core, step) if ema is None else ema.state_dict())
+        ema_info = None if ema is None else {"decay": ema.decay, "tau": ema.tau, "updates": ema.updates}
         if rank == 0:
             last_metrics = metrics
             fit = _results_dict(metrics)["fitness"]
-            save_checkpoint(wdir / "last.pt", core, epoch, fit, state_dict=sd)
+            save_checkpoint(wdir / "last.pt", core, epoch, fit, state_dict=sd, ema=ema_info)
             if fit > best_fit:
                 best_fit, best_epoch = fit, epoch
-                save_checkpoint(wdir / "best.pt", core, epoch, fit, state_dict=sd)
+                save_checkpoint(wdir / "best.pt", core, epoch, fit, state_dict=sd, ema=ema_info)
             row = {"epoch": epoch + 1, "train/loss": float(tot) / max(n, 1), "time_s": time.perf_counter() - t_ep,
                    **_results_dict(metrics)}
             row.update(_moe_stats(core))

@@ -15,10 +15,17 @@ their own storage, which the kernel refreshes with the RNE of the new master.
 Gradients are read where autograd (or the backward hipGraph) left them,
 through a device table rebuilt only when a gradient address changes -- three
 launches per step instead of ~400 per-tensor casts, norms and scales.
+
+Exponential moving average of the weights (``enable_ema``; Ultralytics'
+ModelEMA, src/rtdetr_moe/ema.py): a fourth flat fp32 buffer laid out like the
+masters, blended inside the AdamW launch (``train_adamw_ema_step``) when
+``step`` is given the step's decay.  ``MOE_EMA_FUSED=0`` is the A/B switch:
+the plain AdamW launch followed by ``train_ema_update`` over the masters.
 """
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -42,6 +49,46 @@ def _storage_flat(t: torch.Tensor) -> torch.Tensor:
             raise ValueError(f"FlatAdamW: tensor with strides {t.stride()} is not dense")
         expect *= t.size(i)
     return t.as_strided((t.numel(),), (1,))
+
+
+def _ema_fused() -> bool:
+    """MOE_EMA_FUSED=0: the unfused A/B path (read per step, so a test can flip it)."""
+    return os.environ.get("MOE_EMA_FUSED", "1") != "0"
+
+
+def _self_table(buf, segments, device):
+    """Record table whose sources are segments (offset, numel) of the flat fp32
+    ``buf`` itself, blended at the same offsets of the average: the unfused
+    EMA pass over the masters (``train_ema_update``)."""
+    rec = np.zeros(max(len(segments), 1), dtype=_REC)
+    for k, (o, n) in enumerate(segments):
+        rec[k]["grad"] = buf.data_ptr() + 4 * o
+        rec[k]["numel"] = n
+        rec[k]["moff"] = o
+        rec[k]["gdtype"] = 1
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device)
+
+
+def _adamw_launch(opt, tab, chunks, n_chunks, ema_decay):
+    """The AdamW launch of ``opt`` (FlatAdamW / ShardedDPAdamW) over its record
+    table: today's kernel when ``ema_decay`` is None, else the update + EMA
+    blend in one launch, or (MOE_EMA_FUSED=0) the update, then the blend."""
+    lib, s = L.lib(), L._stream()
+    lrs = (ctypes.c_float * len(opt.lrs))(*opt.lrs)
+    args = (tab, chunks.data_ptr(), n_chunks, opt.coef.data_ptr(), opt.master.data_ptr(), opt.exp_avg.data_ptr(),
+            opt.exp_avg_sq.data_ptr(), opt.tsteps.data_ptr(), lrs, len(opt.lrs), opt.wd, opt.beta1, opt.beta2,
+            opt.eps)
+    if ema_decay is None:
+        L._check(lib.train_adamw_step(*args, s), "train_adamw_step")
+        return
+    if opt.ema is None:
+        raise RuntimeError("step(ema_decay=...) needs enable_ema() first")
+    if _ema_fused():
+        L._check(lib.train_adamw_ema_step(*args, opt.ema.data_ptr(), float(ema_decay), s), "train_adamw_ema_step")
+    else:
+        L._check(lib.train_adamw_step(*args, s), "train_adamw_step")
+        L._check(lib.train_ema_update(opt._ema_self_table.data_ptr(), chunks.data_ptr(), n_chunks,
+                                      opt.ema.data_ptr(), float(ema_decay), s), "train_ema_update")
 
 
 class FlatAdamW:
@@ -103,6 +150,14 @@ class FlatAdamW:
         self._ptrs = None
         self._table = None
         self.steps = 0
+        self.ema = None  # enable_ema(): flat fp32 average, laid out like the masters
+
+    def enable_ema(self):
+        """Allocate the weight average, starting at the current masters (call
+        after the masters are filled and before any step)."""
+        self.ema = self.master.clone()
+        self._ema_self_table = _self_table(self.master, [(o, p.numel()) for p, o in zip(self.params, self.offsets)],
+                                           self.device)
 
     # -- gradient table ---------------------------------------------------
     def _grad_source(self, i, p, g):
@@ -131,10 +186,12 @@ class FlatAdamW:
 
     # -- step --------------------------------------------------------------
     @torch.no_grad()
-    def step(self, grads=None, inv_world=1.0):
+    def step(self, grads=None, inv_world=1.0, ema_decay=None):
         """One clipped AdamW update from ``grads`` (aligned with the parameters;
         default: each parameter's ``.grad``).  ``inv_world`` scales gradients
-        that hold a sum over data-parallel ranks."""
+        that hold a sum over data-parallel ranks.  ``ema_decay``: this step's
+        EMA decay d (``ema = d ema + (1 - d) master`` for every tensor, with or
+        without a gradient); None: no average."""
         if grads is None:
             grads = [p.grad for p in self.params]
         srcs = [self._grad_source(i, p, g) for i, (p, g) in enumerate(zip(self.params, grads))]
@@ -151,11 +208,7 @@ class FlatAdamW:
         L._check(lib.train_grad_norm_finalize(self.partials.data_ptr(), self.n_chunks, self.clip_norm,
                                               float(inv_world), self.coef.data_ptr(), tab, len(self.params),
                                               self.tsteps.data_ptr(), s), "train_grad_norm_finalize")
-        lrs = (ctypes.c_float * len(self.lrs))(*self.lrs)
-        L._check(lib.train_adamw_step(tab, self.chunks.data_ptr(), self.n_chunks, self.coef.data_ptr(),
-                                      self.master.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                      self.tsteps.data_ptr(), lrs, len(self.lrs), self.wd, self.beta1, self.beta2,
-                                      self.eps, s), "train_adamw_step")
+        _adamw_launch(self, tab, self.chunks, self.n_chunks, ema_decay)
 
     def _reduce_sharded_partials(self):
         """Sum the sharded tensors' squared-norm partials over the shard group:
@@ -180,13 +233,25 @@ class FlatAdamW:
                 return self.master[o:o + p.numel()]
         raise KeyError("not a parameter of this optimizer")
 
+    def ema_of(self, p) -> torch.Tensor:
+        """The fp32 average of parameter ``p`` (storage order, 1-D view)."""
+        if self.ema is None:
+            raise RuntimeError("EMA is not enabled")
+        for q, o in zip(self.params, self.offsets):
+            if q is p:
+                return self.ema[o:o + p.numel()]
+        raise KeyError("not a parameter of this optimizer")
+
     def grad_norm(self) -> torch.Tensor:
         """Total gradient norm of the last step (device scalar, no sync)."""
         return self.coef[0]
 
     def state_dict(self):
-        return {"steps": self.steps, "lrs": list(self.lrs), "master": self.master, "exp_avg": self.exp_avg,
-                "exp_avg_sq": self.exp_avg_sq, "tensor_steps": self.tsteps}
+        sd = {"steps": self.steps, "lrs": list(self.lrs), "master": self.master, "exp_avg": self.exp_avg,
+              "exp_avg_sq": self.exp_avg_sq, "tensor_steps": self.tsteps}
+        if self.ema is not None:
+            sd["ema"] = self.ema
+        return sd
 
     def load_state_dict(self, sd):
         self.steps = int(sd["steps"])
@@ -195,6 +260,8 @@ class FlatAdamW:
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.tsteps.copy_(sd["tensor_steps"])
+        if self.ema is not None:
+            self.ema.copy_(sd["ema"])
         with torch.no_grad():
             for p, o in zip(self.params, self.offsets):
                 if p.dtype == torch.bfloat16:
@@ -440,6 +507,17 @@ class ShardedDPAdamW:
         self._opt_table = None
         self._has_grad = None  # agreed (over the group) on the first step
         self._staged = {}
+        self.ema = None  # enable_ema(): the average of this rank's slice + expert shards
+
+    def enable_ema(self):
+        """Allocate the weight average of this rank's masters (its 1/W slice of
+        the replicated parameters + its expert shards), starting at their
+        current values; call before any step."""
+        self.ema = self.master.clone()
+        Sb = self.S[0]
+        segs = [(self.poff[i] + i0 - r * self.S[s] + (Sb if s else 0), n) for _, (i, i0, n, r, s) in self.mine]
+        segs += [(o, self.params[i].numel()) for i, o in zip(self.ep_idx, self.ep_off)]
+        self._ema_self_table = _self_table(self.master, segs, self.device)
 
     @staticmethod
     def layout(tensors, W, A=8):
@@ -547,10 +625,11 @@ class ShardedDPAdamW:
         self._opt_table = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device)
 
     @torch.no_grad()
-    def step(self, grads=None, inv_world=None):
+    def step(self, grads=None, inv_world=None, ema_decay=None):
         """One clipped AdamW update of the rank-mean gradient from ``grads``
         (aligned with the parameters; default: each parameter's ``.grad``,
-        the rank-local gradients -- the reduction happens here)."""
+        the rank-local gradients -- the reduction happens here).
+        ``ema_decay``: this step's EMA decay (FlatAdamW.step); None: no average."""
         if grads is None:
             grads = [p.grad for p in self.params]
         inv = 1.0 / self.W if inv_world is None else float(inv_world)
@@ -582,11 +661,7 @@ class ShardedDPAdamW:
         n_ent = len(self.mine) + len(self.ep_idx)
         L._check(lib.train_grad_norm_finalize(self.tot.data_ptr(), 1, self.clip_norm, inv, self.coef.data_ptr(),
                                               tab, n_ent, self.tsteps.data_ptr(), s), "train_grad_norm_finalize")
-        lrs = (ctypes.c_float * len(self.lrs))(*self.lrs)
-        L._check(lib.train_adamw_step(tab, self.opt_chunks.data_ptr(), nch, self.coef.data_ptr(),
-                                      self.master.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                      self.tsteps.data_ptr(), lrs, len(self.lrs), self.wd, self.beta1, self.beta2,
-                                      self.eps, s), "train_adamw_step")
+        _adamw_launch(self, tab, self.opt_chunks, nch, ema_decay)
         Sb, Sf = self.S
         _collective("ag", self.PB, self.PB[self.rank * Sb:(self.rank + 1) * Sb], self.group)
         _collective("ag", self.PF, self.PF[self.rank * Sf:(self.rank + 1) * Sf], self.group)
@@ -618,6 +693,57 @@ class ShardedDPAdamW:
         """The fp32 master of parameter ``p`` (storage order, 1-D): gathered
         from the owning ranks for replicated parameters (a collective: call on
         every rank), local for expert shards."""
+        return self._gathered(self.master, p)
+
+    def ema_of(self, p) -> torch.Tensor:
+        """The fp32 average of parameter ``p``: a collective for replicated
+        parameters, local for expert shards, exactly as ``master_of``."""
+        if self.ema is None:
+            raise RuntimeError("EMA is not enabled")
+        return self._gathered(self.ema, p)
+
+    def state_dict(self):
+        """This rank's optimizer state (its slice of the masters and moments,
+        its expert shards; ``ema`` when enabled)."""
+        sd = {"steps": self.steps, "lrs": list(self.lrs), "master": self.master, "exp_avg": self.exp_avg,
+              "exp_avg_sq": self.exp_avg_sq, "tensor_steps": self.tsteps}
+        if self.ema is not None:
+            sd["ema"] = self.ema
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """Restore this rank's state and refresh the weights from the masters
+        (a collective: the all-gathers of the two parameter spaces)."""
+        self.steps = int(sd["steps"])
+        self.lrs = [float(x) for x in sd["lrs"]]
+        self.master.copy_(sd["master"])
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.tsteps.copy_(sd["tensor_steps"])
+        if self.ema is not None:
+            self.ema.copy_(sd["ema"])
+        Sb, Sf = self.S
+        self.PB[self.rank * Sb:(self.rank + 1) * Sb].copy_(self.master[:Sb])
+        self.PF[self.rank * Sf:(self.rank + 1) * Sf].copy_(self.master[Sb:Sb + Sf])
+        _collective("ag", self.PB, self.PB[self.rank * Sb:(self.rank + 1) * Sb], self.group)
+        _collective("ag", self.PF, self.PF[self.rank * Sf:(self.rank + 1) * Sf], self.group)
+        for i, o in zip(self.ep_idx, self.ep_off):
+            p = self.params[i]
+            _storage_flat(p).copy_(self.master[o:o + p.numel()])
+
+    def gather_slices(self, buf) -> torch.Tensor:
+        """Every rank's slice of the per-rank flat fp32 ``buf`` (masters or
+        average), rank-block-major: one all-gather (a collective)."""
+        B = self.S[0] + self.S[1]
+        allm = torch.empty(B * self.W, dtype=torch.float32, device=self.device)
+        _collective("ag", allm, buf[:B], self.group)
+        return allm
+
+    def _gathered(self, buf, p, allm=None) -> torch.Tensor:
+        """``p``'s segment of the per-rank flat fp32 ``buf`` (masters or
+        average); ``allm``: a ``gather_slices(buf)`` to cut replicated
+        parameters from (else gathered here)."""
         for i, q in enumerate(self.params):
             if q is p:
                 break
@@ -625,11 +751,11 @@ class ShardedDPAdamW:
             raise KeyError("not a parameter of this optimizer")
         if i in self.ep_idx:
             o = self.ep_off[self.ep_idx.index(i)]
-            return self.master[o:o + p.numel()]
+            return buf[o:o + p.numel()]
         Sb, Sf = self.S
         B = Sb + Sf
-        allm = torch.empty(B * self.W, dtype=torch.float32, device=self.device)
-        _collective("ag", allm, self.master[:B], self.group)
+        if allm is None:
+            allm = self.gather_slices(buf)
         flat = torch.empty(p.numel(), dtype=torch.float32, device=self.device)
         for (j, i0, n, r, sp) in self.pieces:
             if j == i:

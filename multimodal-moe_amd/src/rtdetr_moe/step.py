@@ -475,8 +475,12 @@ class TrainStep:
 
     def __init__(self, model: RTDETRMoE, criterion, images, ctx, *, lr=1e-4, lr_backbone=1e-5,
                  weight_decay=1e-4, clip_norm=0.1, graphs=True, ddp_local=None, world=1, precision="bf16",
-                 targets=None, num_boxes=1.0, zero=None, seed=0):
+                 targets=None, num_boxes=1.0, zero=None, seed=0, ema_decay=None, ema_tau=None):
         """seed: the run's seed (the denoising queries' noise generator).
+        ema_decay / ema_tau: the weight average (ema.ModelEMA: updated once per
+        optimizer step, on the GPU inside the AdamW launch); None takes the
+        model spec's values (-ema / -ematau<N> tokens), a decay of 0 is off
+        (``self.ema`` is None and the step is unchanged).
         zero: the ZeRO-1 optimizer (optim.ShardedDPAdamW) -- default: at
         world > 1 unless MOE_ZERO=0; True also at world 1 (a world-1 process
         group: the RCCL reduce-scatter / all-gather branch on one GPU, tests)."""
@@ -567,6 +571,17 @@ class TrainStep:
         else:
             self.fn = self.flat
             self.ddp = None
+        spec = getattr(model, "spec", None)
+        ema_decay = float(getattr(spec, "ema_decay", 0.0) if ema_decay is None else ema_decay)
+        ema_tau = float(getattr(spec, "ema_tau", 2000.0) if ema_tau is None else ema_tau)
+        self.ema = None
+        if ema_decay > 0.0:
+            # the average starts at the state the first step sees: after the optimizer took over
+            # the parameters (fp32 views, flat spaces) and after the captures' warm-up passes
+            # (they move the BatchNorm statistics, not the weights); allocates, moves nothing
+            from .ema import ModelEMA
+
+            self.ema = ModelEMA(model, self.opt, decay=ema_decay, tau=ema_tau)
 
     def _bind_grads(self, static_grads):
         """Point every parameter's .grad at the (new) static gradient buffers of
@@ -658,14 +673,18 @@ class TrainStep:
 
     def _optimizer_step(self):
         if self.opt_params is None:  # GPU: FlatAdamW / ShardedDPAdamW (reduction + clip inside)
+            # with a weight average, ModelEMA.update runs the optimizer step with this update's decay
+            opt_step = self.opt.step if self.ema is None else self.ema.update
             if self.reducer is not None:
-                self.opt.step(self._allreduce_grads(), inv_world=1.0 / self.world)
+                opt_step(self._allreduce_grads(), inv_world=1.0 / self.world)
             else:
-                self.opt.step()
+                opt_step()
         else:
             if self.clip_norm > 0:
                 clip_grad_norm_sharded(self.dp_params, self.ep_params, self.clip_norm, self.ep_group)
             self.opt.step()
+            if self.ema is not None:
+                self.ema.update()
 
     def phase_summary(self):
         """{phase: (gpu ms, host ms)} averaged over the marked steps (syncs)."""

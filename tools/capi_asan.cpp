@@ -68,6 +68,12 @@ int main() {
   const float lr = 1e-4f;
   expect_error("adamw_step 0 groups", train_adamw_step(p, i32, 1, f32, f32, f32, f32, i32, &lr, 0, 0.f, 0.9f,
                                                        0.999f, 1e-8f, s));
+  expect_error("adamw_ema_step ema=NULL", train_adamw_ema_step(p, i32, 1, f32, f32, f32, f32, i32, &lr, 1, 0.f, 0.9f,
+                                                               0.999f, 1e-8f, nullptr, 0.5f, s));
+  expect_error("adamw_ema_step decay=1", train_adamw_ema_step(p, i32, 1, f32, f32, f32, f32, i32, &lr, 1, 0.f, 0.9f,
+                                                              0.999f, 1e-8f, f32, 1.0f, s));
+  expect_error("ema_update misaligned ema", train_ema_update(p, i32, 1, f32 + 1, 0.5f, s));
+  expect_error("ema_update decay<0", train_ema_update(p, i32, 1, f32, -0.1f, s));
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
