@@ -943,6 +943,42 @@ int train_adamw_ema_step(const void* tensors, const int32_t* chunks, int n_chunk
 int train_ema_update(const void* tensors, const int32_t* chunks, int n_chunks, float* ema, float ema_decay,
                      hipStream_t stream);
 
+/* Training batch augmentation (reference: the defaults of Ultralytics'
+ * RTDETR.train -- random_perspective with scale / translate only, fliplr,
+ * HSV jitter -- src/models/vision/rtdetr.py:82-94; semantics restated in
+ * src/rtdetr_moe/augment.py, whose augment_reference is the plain-torch form).
+ * `table`: device fp32 [B, 16], one row per image, drawn on the host:
+ *   [0..5]  forward 2x3 matrix (x' = m0 x + m1 y + m2, y' = m3 x + m4 y + m5)
+ *   [6..11] its inverse, [12] hue shift dh, [13] saturation gain gs,
+ *   [14] value gain gv, [15] the scale s.
+ * Coordinates are pixels of the content rectangle w x h, the top-left part of
+ * the padded Hp x Wp tensor.
+ *   train_augment_images  dst (channels_last [B,3,Hp,Wp]; dst_dtype 0 bf16,
+ *       1 fp32; 16-B aligned; Wp % 4 == 0) = for every content pixel centre
+ *       (x+.5, y+.5): the inverse map, bilinear sampling of src (a tap outside
+ *       the content rectangle contributes `fill`), then -- unless dh = 0 and
+ *       gs = gv = 1, or no tap lies inside -- RGB->HSV, h' = frac(h + dh),
+ *       s' = min(1, s gs), v' = min(1, v gv), HSV->RGB; padding rows / columns
+ *       are written as 0.  src: src_dtype 0 uint8 (scaled by 1/255) or 1 fp32,
+ *       element strides sn, sc, sh, sw of [B,3,Hp,Wp] (any layout).  fp32
+ *       arithmetic; bf16 rounds to nearest-even at the store.
+ *   train_augment_boxes   padded targets (boxes fp32 [B,M,4] cxcywh normalised
+ *       to the padded tensor, labels int64 [B,M], n_valid int32 [B];
+ *       M <= 1024, B <= 1024): both corners through the forward matrix,
+ *       min / max, clip to [0,w] x [0,h]; kept iff new width >= 2 px, new
+ *       height >= 2 px, aspect ratio < 100 and new area > 0.1 s^2 old area;
+ *       survivors compacted to the front in their order, (0.5, 0.5, 0.1, 0.1)
+ *       / label 0 behind them, the new counts in n_valid_out and their sum
+ *       (fp32) in total_out[0].  Outputs must not alias inputs.
+ * Both return non-zero (message in moe_last_error) before any launch on a bad
+ * argument. */
+int train_augment_images(const void* src, int src_dtype, long long sn, long long sc, long long sh, long long sw,
+                         void* dst, int dst_dtype, const float* table, int B, int Hp, int Wp, int h, int w,
+                         float fill, hipStream_t stream);
+int train_augment_boxes(const float* boxes, const int64_t* labels, const int32_t* n_valid, const float* table,
+                        int B, int M, int Hp, int Wp, int h, int w, float* boxes_out, int64_t* labels_out,
+                        int32_t* n_valid_out, float* total_out, hipStream_t stream);
+
 /* Launch profiler (measurement only; no reference counterpart).
  * While enabled, every kernel launch of the library carries a hipEvent pair
  * stamped by its own dispatch packet (hipExtLaunchKernel: kernel execution
@@ -954,7 +990,7 @@ int train_ema_update(const void* tensors, const int32_t* chunks, int n_chunks, f
  * 6 MXFP8 weight quantizer, 7 backbone convolution epilogues, 8 optimizer,
  * 9 Hungarian matching, 10 fp8 grouped GEMM, 11 dense linear weight gradients,
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
- * context-bias gradients.
+ * context-bias gradients, 15 training batch augmentation.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -972,7 +1008,8 @@ enum moe_prof_kind {
   MOE_PROF_LINEAR = 11,   /* dense linear weight + bias gradients (rtdetr_linear_wgrad) */
   MOE_PROF_ATTN = 12,     /* multi-head self-attention (rtdetr_attn_fwd / rtdetr_attn_bwd) */
   MOE_PROF_CONV = 13,     /* implicit-GEMM convolutions (rtdetr_conv_*) */
-  MOE_PROF_ROUTER_WGRAD = 14 /* router weight / context-bias gradients (moe_router_wgrad) */
+  MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
+  MOE_PROF_AUGMENT = 15    /* training batch augmentation (train_augment_images / train_augment_boxes) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

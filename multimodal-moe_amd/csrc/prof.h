@@ -32,7 +32,8 @@ enum ProfKind {
   PROF_LINEAR = 11,    // dense linear weight + bias gradients (rtdetr_linear_wgrad)
   PROF_ATTN = 12,      // multi-head self-attention (rtdetr_attn_fwd / _bwd)
   PROF_CONV = 13,      // implicit-GEMM convolutions (rtdetr_conv_*)
-  PROF_ROUTER_WGRAD = 14  // router weight / context-bias gradients (moe_router_wgrad)
+  PROF_ROUTER_WGRAD = 14,  // router weight / context-bias gradients (moe_router_wgrad)
+  PROF_AUGMENT = 15        // training batch augmentation (train_augment_images / _boxes)
 };
 
 class ProfScope {

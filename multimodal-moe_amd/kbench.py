@@ -6,6 +6,7 @@ tuning variants in one process (median of rounds), and prints one JSON line
 per (kernel, shape, variant) with us / TFLOP/s / GB/s.
 
   python multimodal-moe_amd/kbench.py [--reps 50] [--rounds 5] [--variants 1,2] [--stages 3,4]
+  python multimodal-moe_amd/kbench.py --augment     the batch-augmentation kernels at C2's batch
 """
 from __future__ import annotations
 
@@ -164,8 +165,73 @@ def kernels(c):
     return out
 
 
+def augment_leg(reps, rounds):
+    """The augmentation kernels at C2's batch (B 8, 3x736x1280 with 720 content
+    rows, M 16): us and GB/s of algorithmic bytes (the source content once +
+    the destination; boxes: the padded targets in and out), median over
+    rounds, next to the same work done by augment_reference on GPU tensors
+    (the torch-composition baseline, timed with events around the whole call,
+    its cast to bf16 channels_last included)."""
+    from src.rtdetr_moe import augment as A
+    from src.rtdetr_moe.criterion import pad_targets
+
+    B, hw, phw, M = 8, (720, 1280), (736, 1280), 16
+    g = torch.Generator().manual_seed(0)
+    table = A.draw_params(g, B, hw, phw).cuda()
+    u8 = torch.zeros((B, 3, *phw), dtype=torch.uint8)
+    u8[:, :, :hw[0]] = torch.randint(0, 256, (B, 3, *hw), generator=g, dtype=torch.uint8)
+    u8 = u8.cuda()
+    f32 = (u8.float() / 255.0).contiguous(memory_format=torch.channels_last)
+    targets = [{"boxes": torch.rand((n, 4), generator=g).cuda() * 0.2 + 0.3,
+                "labels": torch.zeros(n, dtype=torch.int64, device="cuda")} for n in (3, 0, 16, 5, 1, 7, 2, 4)]
+    tb, tl, nv = pad_targets(targets, M)
+    outs = {dt: torch.empty((B, 3, *phw), dtype=dt, device="cuda", memory_format=torch.channels_last)
+            for dt in (torch.bfloat16, torch.float32)}
+    box_out = (torch.empty_like(tb), torch.empty_like(tl), torch.empty_like(nv),
+               torch.empty((), dtype=torch.float32, device="cuda"))
+    px_src, px_dst = B * 3 * hw[0] * hw[1], B * 3 * phw[0] * phw[1]
+    legs = [("augment_images u8_nchw->bf16", lambda: A.augment_images_hip(u8, table, outs[torch.bfloat16], hw),
+             px_src + 2 * px_dst),
+            ("augment_images f32_nhwc->bf16", lambda: A.augment_images_hip(f32, table, outs[torch.bfloat16], hw),
+             4 * px_src + 2 * px_dst),
+            ("augment_images f32_nhwc->f32", lambda: A.augment_images_hip(f32, table, outs[torch.float32], hw),
+             4 * px_src + 4 * px_dst),
+            ("augment_boxes (2 launches)", lambda: A.augment_boxes_hip(tb, tl, nv, table, hw, phw, out=box_out),
+             B * (M * 48 + 8 + 64) + 4 * B + 4)]
+
+    def torch_ref():
+        img, *_ = A.augment_reference(f32, tb, tl, nv, table, hw)
+        return img.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+    def event_timed(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    res = {}
+    for _ in range(rounds):
+        for name, fn, byts in legs:
+            res.setdefault((name, byts), []).append(timed(fn, reps))
+        res.setdefault(("augment_reference torch f32_nhwc->bf16 (events, whole call)", 4 * px_src + 2 * px_dst),
+                       []).append(event_timed(torch_ref, max(3, reps // 10)))
+    for (name, byts), us in res.items():
+        med = statistics.median(us)
+        print(json.dumps({"kernel": name, "shape": f"B{B} 3x{phw[0]}x{phw[1]} content {hw[0]}x{hw[1]} M{M}",
+                          "us": round(med, 2), "us_min": round(min(us), 2), "us_max": round(max(us), 2),
+                          "GBs": round(byts / med * 1e-3, 1), "bytes": byts}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--augment", action="store_true", help="time the batch-augmentation kernels (C2's batch) and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -188,6 +254,9 @@ def main():
     a = ap.parse_args()
     SKEW[0] = a.skew
     L.lib()
+    if a.augment:
+        augment_leg(a.reps, a.rounds)
+        return
     for kv in a.tune:
         key, val = kv.split("=", 1)
         L.set_tuning(key, int(val))

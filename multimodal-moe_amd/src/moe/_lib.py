@@ -148,6 +148,8 @@ SIGNATURES = {
     "train_adamw_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _P]),
     "train_adamw_ema_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _P, _F, _P]),
     "train_ema_update": (_I, [_P, _P, _I, _P, _F, _P]),
+    "train_augment_images": (_I, [_P, _I, _LL, _LL, _LL, _LL, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "train_augment_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "moe_profile_enable": (_I, [_I]),
     "moe_profile_count": (_I, []),
     "moe_profile_get": (_I, [_I, _P, _P, _P, _P]),
@@ -199,7 +201,7 @@ def lib() -> ctypes.CDLL:
 
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
-              11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad"}
+              11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E

@@ -17,6 +17,10 @@ local architecture spec (no network fetch), e.g.::
                                   (src/rtdetr_moe/ema.py; Ultralytics' decay 0.9999, tau 2000), which
                                   is what gets validated and checkpointed.  -ema<d> sets the decay
                                   (-ema0.999), -ematau<N> the warm-up constant; default: no average
+    rtdetr-r50-moe8-top2-aug      C2 trained with GPU batch augmentation (src/rtdetr_moe/augment.py):
+                                  scale / translate jitter, horizontal flip and HSV jitter at Ultralytics'
+                                  default magnitudes, images and boxes on the device.  The token takes no
+                                  value (magnitudes: augment.AugmentParams); default: no augmentation
 """
 from __future__ import annotations
 
@@ -87,6 +91,7 @@ class ModelSpec:
     num_denoising: int = 0         # contrastive denoising queries per image in training (-dn<N>; 0 = off)
     ema_decay: float = 0.0         # EMA of the weights in training (-ema = 0.9999, -ema<d>; 0 = off)
     ema_tau: float = 2000.0        # EMA warm-up: d_t = ema_decay (1 - exp(-t / ema_tau)) (-ematau<N>)
+    augment: bool = False          # GPU batch augmentation in training (-aug; rtdetr_moe/augment.py)
     raw: str = ""
 
 
@@ -94,7 +99,8 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>]``."""
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug]``
+    (``-aug``: training batch augmentation, no value)."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
         raise ValueError(f"{spec!r} is a weights file, not an architecture spec")
@@ -106,7 +112,9 @@ def parse_moe_spec(spec: str) -> ModelSpec:
     out = ModelSpec(backbone=m.group(1), moe=None, raw=spec)
     moe = None
     for tok in [t for t in m.group(2).split("-") if t]:
-        if tok.startswith("moe"):
+        if tok == "aug":  # exact, ahead of every prefix match
+            out.augment = True
+        elif tok.startswith("moe"):
             moe = moe or MoEConfig()
             moe.num_experts = int(tok[3:])
         elif tok.startswith("top"):

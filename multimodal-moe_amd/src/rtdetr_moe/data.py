@@ -127,8 +127,25 @@ def _read_yaml(path: Path) -> dict:
         return yaml.safe_load(f) or {}
 
 
+def _padded_image(hwc: np.ndarray, pad_h: int, pad_w: int, as_uint8: bool) -> torch.Tensor:
+    """uint8 [h, w, 3] -> [3, pad_h, pad_w], content top-left, zero padding:
+    fp32 in [0, 1] (x / 255), or the uint8 values themselves."""
+    arr = torch.from_numpy(hwc.copy()).permute(2, 0, 1)
+    h, w = arr.shape[1:]
+    if as_uint8:
+        img = torch.zeros((3, pad_h, pad_w), dtype=torch.uint8)
+        img[:, :h, :w] = arr
+        return img
+    img = torch.zeros((3, pad_h, pad_w))
+    img[:, :h, :w] = arr.float() / 255.0
+    return img
+
+
 class YoloDataset(torch.utils.data.Dataset):
-    def __init__(self, data_yaml: str | Path, split="train", imgsz=(704, 1248), pad_to=32):
+    def __init__(self, data_yaml: str | Path, split="train", imgsz=(704, 1248), pad_to=32, as_uint8=False):
+        """as_uint8: yield the padded image as a uint8 tensor (0..255) instead
+        of fp32 / 255 (the training augmentation kernel scales it on the GPU)."""
+        self.as_uint8 = bool(as_uint8)
         self.yaml_path = Path(data_yaml)
         cfg = _read_yaml(self.yaml_path)
         root = Path(cfg.get("path", self.yaml_path.parent))
@@ -178,9 +195,7 @@ class YoloDataset(torch.utils.data.Dataset):
 
         p = self.images[i]
         im = Image.open(p).convert("RGB").resize((self.w, self.h), Image.BILINEAR)
-        arr = torch.from_numpy(np.asarray(im, dtype=np.uint8).copy()).permute(2, 0, 1).float() / 255.0
-        img = torch.zeros((3, self.pad_h, self.pad_w))
-        img[:, : self.h, : self.w] = arr
+        img = _padded_image(np.asarray(im, dtype=np.uint8), self.pad_h, self.pad_w, self.as_uint8)
         boxes, labels = [], []
         lp = self._label_path(p)
         if lp.exists():
@@ -199,7 +214,9 @@ class YoloDataset(torch.utils.data.Dataset):
 
 
 class CocoDataset(torch.utils.data.Dataset):
-    def __init__(self, img_folder: str | Path, ann_file: str | Path, imgsz=(704, 1248), pad_to=32):
+    def __init__(self, img_folder: str | Path, ann_file: str | Path, imgsz=(704, 1248), pad_to=32, as_uint8=False):
+        """as_uint8: as YoloDataset."""
+        self.as_uint8 = bool(as_uint8)
         self.img_folder = Path(img_folder)
         d = json.loads(Path(ann_file).read_text())
         cats = sorted(int(c["id"]) for c in d.get("categories", []))
@@ -227,9 +244,7 @@ class CocoDataset(torch.utils.data.Dataset):
         pil = Image.open(self.img_folder / im["file_name"]).convert("RGB")
         ow, oh = int(im.get("width", pil.width)), int(im.get("height", pil.height))
         pil = pil.resize((self.w, self.h), Image.BILINEAR)
-        arr = torch.from_numpy(np.asarray(pil, dtype=np.uint8).copy()).permute(2, 0, 1).float() / 255.0
-        img = torch.zeros((3, self.pad_h, self.pad_w))
-        img[:, : self.h, : self.w] = arr
+        img = _padded_image(np.asarray(pil, dtype=np.uint8), self.pad_h, self.pad_w, self.as_uint8)
         boxes, labels = [], []
         for a in self.anns[im["id"]]:
             x, y, w, h = map(float, a["bbox"])

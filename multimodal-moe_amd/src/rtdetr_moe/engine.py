@@ -221,7 +221,9 @@ def _hw(imgsz):
     return (imgsz, imgsz) if isinstance(imgsz, int) else (int(imgsz[0]), int(imgsz[1]))
 
 
-def _batches(data, split, imgsz, batch, workers, seed, rank, world, epoch, drop_last=False):
+def _batches(data, split, imgsz, batch, workers, seed, rank, world, epoch, drop_last=False, as_uint8=False):
+    """as_uint8: the file datasets yield the padded uint8 tensor (a quarter of
+    the host-to-device copy; the augmentation kernel scales it by 1/255)."""
     h, w = _hw(imgsz)
     if _is_synthetic(data):
         gen = SyntheticZOD(batch=batch, img_h=h, img_w=w, seed=seed * 1000 + rank + (0 if split == "train" else 777)
@@ -230,9 +232,9 @@ def _batches(data, split, imgsz, batch, workers, seed, rank, world, epoch, drop_
             yield gen.sample()
         return
     if isinstance(data, dict):  # COCO export: {"train"/"val": {"img_folder", "ann_file"}}
-        ds = CocoDataset(data[split]["img_folder"], data[split]["ann_file"], imgsz=(h, w))
+        ds = CocoDataset(data[split]["img_folder"], data[split]["ann_file"], imgsz=(h, w), as_uint8=as_uint8)
     else:
-        ds = YoloDataset(data, split=split, imgsz=(h, w))
+        ds = YoloDataset(data, split=split, imgsz=(h, w), as_uint8=as_uint8)
     sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=split == "train",
                                                               seed=seed) if world > 1 else None
     if sampler is not None:
@@ -268,6 +270,7 @@ class TrainArgs:
     num_classes: int = 1
     ema_decay: float | None = None  # weight average (ema.ModelEMA); None: the model spec's -ema token (0 = off)
     ema_tau: float | None = None
+    augment: bool | None = None  # GPU batch augmentation (augment.BatchAugment); None: the model spec's -aug token
 
 
 def _seed_all(seed: int):
@@ -305,7 +308,11 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
     the validation runs on the averaged weights (``step.ema.applied()``), so
     the fitness is the averaged model's, and the checkpoints carry the averaged
     state dict plus an "ema" entry -- what Ultralytics' trainer validates and
-    saves."""
+    saves.
+    With batch augmentation (an -aug spec token or ``augment``) the training
+    batches -- never the validation ones -- go through augment.BatchAugment
+    inside the step; on the GPU the file datasets then hand over uint8 images,
+    in the loader's layout (the kernel reads through strides)."""
     from .step import TrainStep
 
     on_gpu = local != "cpu"
@@ -332,6 +339,7 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         wdir.mkdir(parents=True, exist_ok=True)
     best_fit, best_epoch = -1.0, -1
     last_metrics = BoxMetrics()
+    augment = bool(getattr(getattr(core, "spec", None), "augment", False)) if a.augment is None else bool(a.augment)
     csv_rows = []
     epoch = 0
     step = None
@@ -342,23 +350,26 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         tot = torch.zeros((), dtype=torch.float64, device=device)
         n = 0
         for images, targets, ctx in _batches(a.data, "train", a.imgsz, a.batch, a.workers, a.seed, rank, world,
-                                             epoch, drop_last=on_gpu):
+                                             epoch, drop_last=on_gpu, as_uint8=augment and on_gpu):
             images = images.to(device, non_blocking=True)
-            if on_gpu:
+            if on_gpu and not augment:
                 images = images.contiguous(memory_format=torch.channels_last)
             ctx = ctx.to(device)
             tg = [{"boxes": t["boxes"].to(device), "labels": t["labels"].to(device)} for t in targets]
-            nb = torch.tensor([float(sum(len(t["boxes"]) for t in targets))], device=device)
-            if world > 1:
-                dist.all_reduce(nb)
-            num_boxes = (nb / world).clamp_(min=1.0).reshape(())
+            if augment and on_gpu and step is not None:
+                num_boxes = None  # the step counts the surviving boxes itself, on the device (all-reduced there)
+            else:
+                nb = torch.tensor([float(sum(len(t["boxes"]) for t in targets))], device=device)
+                if world > 1:
+                    dist.all_reduce(nb)
+                num_boxes = (nb / world).clamp_(min=1.0).reshape(())
             if step is None:
                 step = TrainStep(core, crit, images, ctx, lr=a.lr, lr_backbone=a.lr_backbone,
                                  weight_decay=a.weight_decay, clip_norm=a.clip_norm, graphs=on_gpu, world=world,
                                  precision="bf16" if on_gpu else "fp32",
                                  ddp_local=None, targets=tg if on_gpu else None,
                                  num_boxes=float(num_boxes), seed=a.seed, ema_decay=a.ema_decay,
-                                 ema_tau=a.ema_tau)
+                                 ema_tau=a.ema_tau, augment=augment, content_hw=_hw(a.imgsz))
                 shape = tuple(images.shape)
             if on_gpu and tuple(images.shape) != shape:
                 raise RuntimeError(f"batch shape {tuple(images.shape)} differs from the captured {shape}")

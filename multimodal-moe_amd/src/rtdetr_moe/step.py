@@ -17,6 +17,10 @@ clipping and the fused AdamW update.
 
 The captured forward keeps the MoE aux losses as an explicit graph output so
 their gradients reach the router through the captured backward.
+
+Batch augmentation (an -aug model spec, augment.BatchAugment) runs in front of
+the step, outside every graph: with the whole-step graph its two HIP launches
+write the graph's static images, padded targets and box count directly.
 """
 from __future__ import annotations
 
@@ -376,26 +380,38 @@ class GraphedStep:
         if self.on_capture is not None:
             self.on_capture(self.static_grads)
 
-    def __call__(self, images, ctx, targets, num_boxes):
+    def reserve(self, targets):
+        """Make room for this batch's targets: a batch with more boxes than the
+        captured padding re-captures at the next multiple of 16 (rare)."""
         from .criterion import pad_targets
 
         need = max((len(t["boxes"]) for t in targets), default=0)
-        if need > self.M:  # larger than the captured padding: re-capture (rare)
+        if need > self.M:
             self.M = (need + 15) // 16 * 16
             self.tb, self.tl, self.nv = pad_targets(targets, self.M)
             self.graph = None
             self._dn_alloc()  # G and Qdn follow M
             self._capture()
-        if images.data_ptr() != self.static_images.data_ptr():
-            self.static_images.copy_(images)
+
+    def __call__(self, images, ctx, targets, num_boxes, in_place=False):
+        """in_place: the caller (TrainStep with batch augmentation) has already
+        called ``reserve`` and written this step's images, padded targets and
+        box count into ``static_images``, ``tb`` / ``tl`` / ``nv`` and ``nb``;
+        nothing but the context ids is copied."""
+        from .criterion import pad_targets
+
+        if not in_place:
+            self.reserve(targets)
+            if images.data_ptr() != self.static_images.data_ptr():
+                self.static_images.copy_(images)
+            pad_targets(targets, self.M, self.tb, self.tl, self.nv)
+            if torch.is_tensor(num_boxes):  # device scalar (e.g. all-reduced box count): no host sync
+                self.nb.copy_(num_boxes.reshape(()))
+            else:
+                self.nb.fill_(float(num_boxes))
         if ctx.data_ptr() != self.static_ctx.data_ptr():
             self.static_ctx.copy_(ctx)
-        pad_targets(targets, self.M, self.tb, self.tl, self.nv)
         self._dn_refresh()
-        if torch.is_tensor(num_boxes):  # device scalar (e.g. all-reduced box count): no host sync
-            self.nb.copy_(num_boxes.reshape(()))
-        else:
-            self.nb.fill_(float(num_boxes))
         self.graph.replay()
         return self.static_loss
 
@@ -475,8 +491,21 @@ class TrainStep:
 
     def __init__(self, model: RTDETRMoE, criterion, images, ctx, *, lr=1e-4, lr_backbone=1e-5,
                  weight_decay=1e-4, clip_norm=0.1, graphs=True, ddp_local=None, world=1, precision="bf16",
-                 targets=None, num_boxes=1.0, zero=None, seed=0, ema_decay=None, ema_tau=None):
-        """seed: the run's seed (the denoising queries' noise generator).
+                 targets=None, num_boxes=1.0, zero=None, seed=0, ema_decay=None, ema_tau=None, augment=None,
+                 content_hw=None):
+        """seed: the run's seed (the denoising queries' noise generator, the
+        augmentation parameters' generator).
+        augment: batch augmentation (augment.BatchAugment: scale / translate
+        jitter, flip, HSV jitter of images and boxes, on the GPU two HIP
+        launches in front of the step graph); None takes the model spec's
+        -aug token, False leaves the step unchanged (``self.aug`` is None).
+        With it the step takes uint8 or fp32 images in any layout.  With
+        graphs=True it needs targets= (the whole-step graph, whose static
+        inputs the kernels write; the forward / backward graph pair without
+        targets is refused with a ValueError).  The eager / CPU step takes any
+        batch size up to the first batch's.
+        content_hw: the (h, w) of the image content inside the padded tensor
+        (the augmentation's frame; default: the whole tensor).
         ema_decay / ema_tau: the weight average (ema.ModelEMA: updated once per
         optimizer step, on the GPU inside the AdamW launch); None takes the
         model spec's values (-ema / -ematau<N> tokens), a decay of 0 is off
@@ -543,6 +572,23 @@ class TrainStep:
             for m in model.modules():
                 if isinstance(m, MoEFFN) and m.ep_size > 1:
                     m.ep_grad_scale = 1.0
+        spec = getattr(model, "spec", None)
+        self.aug = None
+        if bool(getattr(spec, "augment", False)) if augment is None else bool(augment):
+            from .augment import BatchAugment
+
+            if graphs and targets is None:
+                raise ValueError("batch augmentation needs targets= for graphs=True (the whole-step graph)")
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            padded_hw = tuple(images.shape[-2:])
+            self.aug = BatchAugment(images.shape[0], content_hw or padded_hw, padded_hw, images.device, seed=seed,
+                                    rank=rank,
+                                    out_dtype=torch.bfloat16 if self.precision == "bf16" else torch.float32)
+            # the static image buffer is what the kernel writes: float, channels_last
+            if images.dtype == torch.uint8:
+                images = images.float() / 255.0
+            if images.is_cuda:
+                images = images.contiguous(memory_format=torch.channels_last)
         images = self._cast_in(images)
         self.runner = None
         self.stepper = None
@@ -571,7 +617,6 @@ class TrainStep:
         else:
             self.fn = self.flat
             self.ddp = None
-        spec = getattr(model, "spec", None)
         ema_decay = float(getattr(spec, "ema_decay", 0.0) if ema_decay is None else ema_decay)
         ema_tau = float(getattr(spec, "ema_tau", 2000.0) if ema_tau is None else ema_tau)
         self.ema = None
@@ -588,6 +633,43 @@ class TrainStep:
         a capture (the reducer rebuilds its table when the addresses change)."""
         for p, g in zip(self.params, static_grads):
             p.grad = g
+
+    def _augment_in_place(self, images, targets):
+        """Graphed step: pad the incoming targets into the augmenter's raw
+        buffers, then let its kernels write the step graph's static inputs --
+        images, padded targets, counts -- and the box count (the batch sum of
+        the surviving boxes; at world > 1 its mean over the ranks, clamped at
+        1, as the engine forms the host count), all on the device."""
+        from .criterion import pad_targets
+
+        st = self.stepper
+        st.reserve(targets)
+        raw = self.aug.raw_targets(st.M)
+        pad_targets(targets, st.M, *raw)
+        _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images, out_targets=(st.tb, st.tl, st.nv))
+        self._box_count(total, st.nb)
+
+    def _box_count(self, total, out):
+        if self.world > 1 and dist.is_available() and dist.is_initialized():
+            total = total.reshape(1).clone()
+            dist.all_reduce(total)
+            total = total.reshape(()) / self.world
+        torch.clamp(total, min=1.0, out=out)
+        return out
+
+    def _augment_eager(self, images, targets):
+        """Eager / CPU step: augment, then back to the list of dicts the eager
+        criterion takes (one host read of the counts)."""
+        from .augment import targets_from_padded
+        from .criterion import pad_targets
+
+        need = max((len(t["boxes"]) for t in targets), default=0)
+        M = max(16, (need + 15) // 16 * 16)
+        raw = self.aug.raw_targets(M, len(targets))  # a shorter batch (an epoch's last) uses the leading slots
+        pad_targets(targets, M, *raw)
+        img, tb, tl, nv, total = self.aug(images, *raw)
+        nb = self._box_count(total, torch.empty_like(total))
+        return img, targets_from_padded(tb, tl, nv), nb if img.is_cuda else float(nb)
 
     def _cast_in(self, images):
         return images.to(torch.bfloat16) if self.precision == "bf16" else images
@@ -622,8 +704,16 @@ class TrainStep:
 
     def __call__(self, images, ctx, targets, num_boxes):
         self._mark("start")
+        if self.aug is not None and self.stepper is None:
+            images, targets, num_boxes = self._augment_eager(images, targets)
+            self._mark("augment")
         if self.stepper is not None:
-            loss = self.stepper(self._cast_in(images), ctx, targets, num_boxes)
+            if self.aug is not None:  # the kernels write the graph's static inputs
+                self._augment_in_place(images, targets)
+                self._mark("augment")
+                loss = self.stepper(None, ctx, targets, None, in_place=True)
+            else:
+                loss = self.stepper(self._cast_in(images), ctx, targets, num_boxes)
             self.last_losses = self.stepper.static_losses
             self._mark("step_graph")
             self._optimizer_step()
