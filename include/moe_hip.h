@@ -729,6 +729,32 @@ int moe_aux_loss_fwd(const float* aux_partials, int nblk, int E, const int32_t* 
 int rtdetr_hungarian_match(const float* cost, const int32_t* n_valid, int S, int B, int Q, int M,
                            int32_t* assign, int32_t* status, hipStream_t stream);
 
+/* Validation: the detections of B images matched to their ground truth on the
+ * device (the evaluator's per-image metrics.match_predictions + box_iou_np on
+ * the host, restated so that tp is the same bit for bit).
+ * boxes fp32 [B][K][4] xyxy pixels, scores fp32 [B][K], labels int32 [B][K]:
+ * K predictions per image, in any order.  gt_boxes fp64 [B][M][4] xyxy
+ * pixels, gt_labels int32 [B][M]: M padded truths of which the first
+ * n_valid[b] are real (n_valid int32 [B], clamped to [0, M]); the padding is
+ * never read.  thr fp64 [T]: the IoU thresholds as the host holds them
+ * (np.linspace(0.5, 0.95, 10) has 0.8999999999999999, not 0.9).
+ * tp uint8 [B][K][T] <- 1 where prediction k of image b is a true positive at
+ * threshold t, else 0 (every entry written), in the INPUT prediction order.
+ * Per threshold the predictions are visited in np.argsort(-scores,
+ * kind="stable") order (descending score, equal scores by index; ranks are
+ * computed in the kernel); a prediction takes, among the truths j < n_valid[b]
+ * of its label that are not taken yet and have iou >= thr[t], the one with
+ * the largest IoU (equal IoUs: the lowest j, as np.argmax).  IoU in numpy's
+ * dtypes: intersection, truth area and union in fp64 on the exactly widened
+ * fp32 prediction coordinates, the prediction's own area in fp32 (subtract,
+ * clamp at 0, multiply) and then widened, union = (area_a + area_b) - inter,
+ * iou = inter / max(union, 1e-9); no FMA contraction.  Coordinates must be
+ * finite.  One workgroup per image, one 64-lane wave per threshold;
+ * K <= 1024, M <= 1024, T <= 16 (62 KiB of LDS at the largest). */
+int rtdetr_eval_match(const float* boxes, const float* scores, const int32_t* labels, const double* gt_boxes,
+                      const int32_t* gt_labels, const int32_t* n_valid, const double* thr, int B, int K, int M,
+                      int T, uint8_t* tp, hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -990,7 +1016,8 @@ int train_augment_boxes(const float* boxes, const int64_t* labels, const int32_t
  * 6 MXFP8 weight quantizer, 7 backbone convolution epilogues, 8 optimizer,
  * 9 Hungarian matching, 10 fp8 grouped GEMM, 11 dense linear weight gradients,
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
- * context-bias gradients, 15 training batch augmentation.
+ * context-bias gradients, 15 training batch augmentation, 16 validation
+ * matching.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1009,7 +1036,8 @@ enum moe_prof_kind {
   MOE_PROF_ATTN = 12,     /* multi-head self-attention (rtdetr_attn_fwd / rtdetr_attn_bwd) */
   MOE_PROF_CONV = 13,     /* implicit-GEMM convolutions (rtdetr_conv_*) */
   MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
-  MOE_PROF_AUGMENT = 15    /* training batch augmentation (train_augment_images / train_augment_boxes) */
+  MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_images / train_augment_boxes) */
+  MOE_PROF_EVAL = 16       /* validation: detections matched to ground truth (rtdetr_eval_match) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

@@ -7,6 +7,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
 
   python multimodal-moe_amd/kbench.py [--reps 50] [--rounds 5] [--variants 1,2] [--stages 3,4]
   python multimodal-moe_amd/kbench.py --augment     the batch-augmentation kernels at C2's batch
+  python multimodal-moe_amd/kbench.py --eval-match  the validation matcher against the host loop
 """
 from __future__ import annotations
 
@@ -229,9 +230,87 @@ def augment_leg(reps, rounds):
                           "GBs": round(byts / med * 1e-3, 1), "bytes": byts}), flush=True)
 
 
+def eval_match_leg(reps, rounds):
+    """The validation matcher at the eval leg's shape (B 16, K 300 predictions,
+    M 20 or 64 truths per image, one class): us per batch of rtdetr_eval_match
+    (dispatch-stamped kernel time) next to ms per batch of the host's
+    metrics.match_predictions on the same inputs (wall clock, 16 images), and
+    ms per batch of the whole device path of the evaluator (upload, launch, one
+    packed copy back; wall clock ending in that copy).  Median, min and max
+    over the rounds, the two sides interleaved in each round."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import metrics as MT
+
+    B, K = 16, 300
+    rng = np.random.default_rng(0)
+    for M in (20, 64):
+        xy = rng.uniform(0, 1100, (B, M, 2))
+        gt = np.concatenate([xy, xy + rng.uniform(15, 120, (B, M, 2))], 2)
+        src = rng.integers(0, M, (B, K))
+        boxes = np.take_along_axis(gt, src[..., None], 1) + rng.uniform(-6, 6, (B, K, 4))
+        noise = rng.random((B, K)) < 0.5
+        p = rng.uniform(0, 1100, (int(noise.sum()), 2))
+        boxes[noise] = np.concatenate([p, p + rng.uniform(5, 120, p.shape)], 1)  # half the predictions: noise
+        boxes = boxes.astype(np.float32)
+        scores = rng.random((B, K)).astype(np.float32)
+        labels = np.zeros((B, K), np.int64)
+        gl = np.zeros((B, M), np.int64)
+        cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+        d = (cu(boxes), cu(scores), cu(labels.astype(np.int32)), cu(gt), cu(gl.astype(np.int32)),
+             torch.full((B,), M, dtype=torch.int32, device="cuda"), cu(np.asarray(MT.IOU_THRESHOLDS, np.float64)))
+        tp = L.eval_match(*d).cpu().numpy().astype(bool)
+        want = np.stack([MT.match_predictions(boxes[b], scores[b], labels[b], gt[b], gl[b]) for b in range(B)])
+        if not np.array_equal(tp, want):
+            raise SystemExit("eval_match differs from match_predictions")
+        # the evaluator's device path end to end, on normalised cxcywh targets of a 1280 x 736 image
+        W, H = 1280, 736
+        tg = [{"boxes": torch.from_numpy(np.stack([(gt[b, :, 0] + gt[b, :, 2]) / 2 / W,
+                                                   (gt[b, :, 1] + gt[b, :, 3]) / 2 / H,
+                                                   (gt[b, :, 2] - gt[b, :, 0]) / W,
+                                                   (gt[b, :, 3] - gt[b, :, 1]) / H], 1).astype(np.float32)),
+               "labels": torch.zeros(M, dtype=torch.int64)} for b in range(B)]
+        db, ds, dl = d[0], d[1], cu(labels)
+
+        def device_path():
+            MT.DeviceDetectionEvaluator().update_batch(db, ds, dl, tg, size=(W, H))
+
+        def wall(fn, n):
+            fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(n):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            return statistics.median(ts)
+
+        def host_path():
+            for b in range(B):
+                MT.match_predictions(boxes[b], scores[b], labels[b], gt[b], gl[b])
+
+        res = {"kernel_us": [], "device_path_ms": [], "host_match_ms": []}
+        for _ in range(rounds):
+            res["kernel_us"].append(timed(lambda: L.eval_match(*d), reps))
+            res["device_path_ms"].append(wall(device_path, max(3, reps // 5)))
+            res["host_match_ms"].append(wall(host_path, 3))
+        out = {"kernel": "rtdetr_eval_match", "shape": f"B{B} K{K} M{M} T{len(MT.IOU_THRESHOLDS)}",
+               "true_positives_at_0.5": int(want[..., 0].sum())}
+        for k, v in res.items():
+            out[k] = round(statistics.median(v), 3)
+            out[k + "_min"] = round(min(v), 3)
+            out[k + "_max"] = round(max(v), 3)
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--augment", action="store_true", help="time the batch-augmentation kernels (C2's batch) and exit")
+    ap.add_argument("--eval-match", action="store_true",
+                    help="time the validation matcher (B 16, K 300, M 20 / 64) against the host loop and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -256,6 +335,9 @@ def main():
     L.lib()
     if a.augment:
         augment_leg(a.reps, a.rounds)
+        return
+    if a.eval_match:
+        eval_match_leg(a.reps, a.rounds)
         return
     for kv in a.tune:
         key, val = kv.split("=", 1)

@@ -114,6 +114,7 @@ SIGNATURES = {
     "moe_router_wgrad_workspace": (_LL, [_I, _I, _I, _I]),
     "moe_router_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rtdetr_hungarian_match": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "rtdetr_eval_match": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -201,7 +202,8 @@ def lib() -> ctypes.CDLL:
 
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
-              11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment"}
+              11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
+              16: "eval_match"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -763,6 +765,36 @@ def hungarian_match(cost, n_valid, status=None):
     rc = lib().rtdetr_hungarian_match(_ptr(cost), _ptr(n_valid), S, B, Q, M, _ptr(assign), _ptr(status), _stream())
     _check(rc, "rtdetr_hungarian_match")
     return assign
+
+
+EVAL_MATCH_MAX_K, EVAL_MATCH_MAX_M, EVAL_MATCH_MAX_T = 1024, 1024, 16  # rtdetr_eval_match's limits
+
+
+def eval_match(boxes, scores, labels, gt_boxes, gt_labels, n_valid, thr):
+    """Validation matching of a batch (metrics.match_predictions per image, bit
+    for bit).  boxes fp32 [B, K, 4] xyxy pixels, scores fp32 [B, K], labels
+    int32 [B, K]; gt_boxes fp64 [B, M, 4] and gt_labels int32 [B, M] padded, the
+    first n_valid[b] (int32 [B]) real; thr fp64 [T] -> tp uint8 [B, K, T] in
+    the input prediction order."""
+    _need(boxes, torch.float32, "boxes")
+    _need(scores, torch.float32, "scores")
+    _need(labels, torch.int32, "labels")
+    _need(gt_boxes, torch.float64, "gt_boxes")
+    _need(gt_labels, torch.int32, "gt_labels")
+    _need(n_valid, torch.int32, "n_valid")
+    _need(thr, torch.float64, "thr")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4 or gt_boxes.dim() != 3 or gt_boxes.shape[-1] != 4 or thr.dim() != 1:
+        raise MoEKernelError("eval_match: boxes [B, K, 4], gt_boxes [B, M, 4], thr [T]")
+    B, K, _ = boxes.shape
+    M, T = int(gt_boxes.shape[1]), int(thr.shape[0])
+    if (tuple(scores.shape) != (B, K) or tuple(labels.shape) != (B, K) or int(gt_boxes.shape[0]) != B
+            or tuple(gt_labels.shape) != (B, M) or tuple(n_valid.shape) != (B,)):
+        raise MoEKernelError("eval_match: scores / labels [B, K], gt_labels [B, M], n_valid [B] expected")
+    tp = torch.empty((B, K, T), dtype=torch.uint8, device=boxes.device)
+    rc = lib().rtdetr_eval_match(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(gt_boxes), _ptr(gt_labels),
+                                 _ptr(n_valid), _ptr(thr), B, K, M, T, _ptr(tp), _stream())
+    _check(rc, "rtdetr_eval_match")
+    return tp
 
 
 def grouped_gemm_wgrad(x, y, offsets, G, want_colsum=True, out_dtype=torch.float32):

@@ -31,7 +31,7 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 from ..moe.config import parse_moe_spec
 from .criterion import SetCriterion
 from .data import CocoDataset, SyntheticZOD, YoloDataset, collate
-from .metrics import BoxMetrics, DetectionEvaluator
+from .metrics import BoxMetrics, DetectionEvaluator, DeviceDetectionEvaluator, gt_xyxy_pixels
 from .model import RTDETRMoE
 
 
@@ -563,7 +563,8 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
     model.eval()
     on_gpu = device.type == "cuda"
     fwd = EvalForward(model)
-    ev = DetectionEvaluator()
+    # on the GPU the per-image matching is one HIP launch per batch (MOE_EVAL_MATCH=0: the host loop)
+    ev = DeviceDetectionEvaluator() if on_gpu else DetectionEvaluator()
     if ev_out is not None:
         ev_out.append(ev)
     t_pre = t_inf = t_post = 0.0
@@ -585,14 +586,15 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
             torch.cuda.synchronize()
         t2 = time.perf_counter()
         H, W = images.shape[-2:]
-        dets = model.postprocess(out, [(W, H)] * images.shape[0])
-        for det, t in zip(dets, targets):
-            gt = t["boxes"].numpy().astype(np.float64)
-            gt_xyxy = np.stack([(gt[:, 0] - gt[:, 2] / 2) * W, (gt[:, 1] - gt[:, 3] / 2) * H,
-                                (gt[:, 0] + gt[:, 2] / 2) * W, (gt[:, 1] + gt[:, 3] / 2) * H], 1) \
-                if len(gt) else np.zeros((0, 4))
-            ev.update(det["boxes"].float().cpu().numpy(), det["scores"].float().cpu().numpy(),
-                      det["labels"].cpu().numpy(), gt_xyxy, t["labels"].numpy())
+        if on_gpu:
+            ev.update_batch(*model.postprocess_batched(out, [(W, H)] * images.shape[0]), targets, size=(W, H))
+            torch.cuda.synchronize()
+        else:
+            dets = model.postprocess(out, [(W, H)] * images.shape[0])
+            for det, t in zip(dets, targets):
+                gt_xyxy = gt_xyxy_pixels(t["boxes"].numpy().astype(np.float64), W, H)
+                ev.update(det["boxes"].float().cpu().numpy(), det["scores"].float().cpu().numpy(),
+                          det["labels"].cpu().numpy(), gt_xyxy, t["labels"].numpy())
         t3 = time.perf_counter()
         t_pre += t1 - t0 - t_cap
         t_inf += t2 - t1

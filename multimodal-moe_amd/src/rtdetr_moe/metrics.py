@@ -51,6 +51,17 @@ def match_predictions(pred_boxes, pred_scores, pred_labels, gt_boxes, gt_labels,
     return tp
 
 
+def gt_xyxy_pixels(gt_cxcywh: np.ndarray, W, H) -> np.ndarray:
+    """Ground truth for the matcher: normalised cxcywh float64 [n, 4] -> xyxy
+    pixels float64 [n, 4] of a W x H image.  The one expression both evaluators
+    use, so the host and the device path see the same doubles."""
+    gt = gt_cxcywh
+    if not len(gt):
+        return np.zeros((0, 4))
+    return np.stack([(gt[:, 0] - gt[:, 2] / 2) * W, (gt[:, 1] - gt[:, 3] / 2) * H,
+                     (gt[:, 0] + gt[:, 2] / 2) * W, (gt[:, 1] + gt[:, 3] / 2) * H], 1)
+
+
 def _ap(recall, precision):
     """COCO 101-point AP: mean over recall thresholds r of the best precision
     at any recall >= r (0 where r is never reached)."""
@@ -168,3 +179,98 @@ class DetectionEvaluator:
                               [r["px"], r["p_curve"], "Confidence", "Precision"],
                               [r["px"], r["r_curve"], "Confidence", "Recall"]]
         return box
+
+
+class DeviceDetectionEvaluator(DetectionEvaluator):
+    """DetectionEvaluator whose per-image matching runs on the GPU, a batch per
+    launch (``rtdetr_eval_match``: match_predictions and box_iou_np restated bit
+    for bit, numpy's dtypes included).  ``update_batch`` appends to ``tp / conf /
+    pred_cls / target_cls`` exactly what ``update`` would have appended for each
+    image, so ``compute()`` and ``average_recall()`` -- inherited -- return the
+    same floats.
+
+    The kernel matches all K predictions and the rows below ``conf_thres`` are
+    dropped afterwards.  That equals dropping them first, as ``update`` does:
+    they sort strictly after every kept row, so no kept row ever sees a truth
+    they took.
+
+    The host path (``update`` per image, no error) runs instead when the inputs
+    are on the CPU, when ``MOE_EVAL_MATCH=0`` (read per call), or when K, the
+    batch's largest truth count or the number of thresholds exceeds the
+    kernel's limits.  NaN scores and non-finite boxes are outside the contract;
+    labels must fit int32.
+    """
+
+    def __init__(self):
+        super().__init__()
+        self._thr = {}  # device -> IOU_THRESHOLDS uploaded once
+
+    def _device_path(self, boxes, K, max_gt) -> bool:
+        import os
+
+        if not boxes.is_cuda or os.environ.get("MOE_EVAL_MATCH", "1") == "0":
+            return False
+        from ..moe import _lib as L
+
+        return (1 <= K <= L.EVAL_MATCH_MAX_K and max_gt <= L.EVAL_MATCH_MAX_M
+                and 1 <= len(IOU_THRESHOLDS) <= L.EVAL_MATCH_MAX_T)
+
+    def update_batch(self, boxes, scores, labels, targets, conf_thres=0.001, *, size):
+        """boxes [B, K, 4] xyxy pixels, scores [B, K], labels [B, K]: the stacked
+        tensors of the postprocessor (``RTDETRMoE.postprocess_batched``).
+        targets: per image a dict with ``boxes`` (normalised cxcywh [n, 4]) and
+        ``labels`` [n] on the CPU, as the loader yields them.  size: (W, H), the
+        pixel size the predictions are scaled to.
+
+        Device path: one host-to-device copy (the padded truth), one launch and
+        one device-to-host copy (tp, scores and labels packed) per batch."""
+        import torch
+
+        W, H = size
+        B, K = int(scores.shape[0]), int(scores.shape[1])
+        gts = [(gt_xyxy_pixels(np.asarray(t["boxes"]).astype(np.float64), W, H), np.asarray(t["labels"]))
+               for t in targets]
+        if len(gts) != B:
+            raise ValueError(f"update_batch: {B} images of predictions, {len(gts)} targets")
+        max_gt = max((len(g) for g, _ in gts), default=0)
+        boxes, scores = boxes.float(), scores.float()
+        if B == 0 or not self._device_path(boxes, K, max_gt):
+            for b, (g, gl) in enumerate(gts):
+                self.update(boxes[b].cpu().numpy(), scores[b].cpu().numpy(), labels[b].cpu().numpy(), g, gl,
+                            conf_thres)
+            return
+        from ..moe import _lib as L
+
+        dev = boxes.device
+        thr = self._thr.get(dev)
+        if thr is None:
+            thr = self._thr[dev] = torch.from_numpy(np.ascontiguousarray(IOU_THRESHOLDS, dtype=np.float64)).to(dev)
+        # the padded truth in one host buffer: fp64 boxes | int32 labels | int32 counts
+        M = max(max_gt, 1)
+        nb, nl = B * M * 32, B * M * 4
+        host = np.zeros(nb + nl + B * 4, dtype=np.uint8)
+        gb = host[:nb].view(np.float64).reshape(B, M, 4)
+        gl32 = host[nb:nb + nl].view(np.int32).reshape(B, M)
+        nv = host[nb + nl:].view(np.int32)
+        for b, (g, gl) in enumerate(gts):
+            gb[b, :len(g)] = g
+            gl32[b, :len(g)] = gl
+            nv[b] = len(g)
+        d = torch.from_numpy(host).to(dev)
+        lab32 = labels.to(torch.int32).contiguous()
+        scores = scores.contiguous()
+        tp = L.eval_match(boxes.contiguous(), scores, lab32, d[:nb].view(torch.float64).view(B, M, 4),
+                          d[nb:nb + nl].view(torch.int32).view(B, M), d[nb + nl:].view(torch.int32), thr)
+        T = int(tp.shape[2])
+        packed = torch.cat([scores.view(torch.uint8).view(B, K * 4), lab32.view(torch.uint8).view(B, K * 4),
+                            tp.view(B, K * T)], 1).cpu().numpy()
+        sc = np.ascontiguousarray(packed[:, :4 * K]).view(np.float32)
+        label_dtype = torch.empty(0, dtype=labels.dtype).numpy().dtype  # pred_cls keeps the dtype update() appends
+        lb = np.ascontiguousarray(packed[:, 4 * K:8 * K]).view(np.int32).astype(label_dtype)
+        tpn = packed[:, 8 * K:].reshape(B, K, T).astype(bool)
+        for b, (_, gl) in enumerate(gts):
+            keep = sc[b] >= conf_thres
+            self.tp.append(tpn[b][keep])
+            self.conf.append(sc[b][keep])
+            self.pred_cls.append(lb[b][keep])
+            self.target_cls.append(gl)

@@ -103,8 +103,9 @@ class RTDETRMoE(nn.Module):
         return torch.stack([t.float() for t in terms]).sum() if terms else None
 
     @torch.no_grad()
-    def postprocess(self, outputs, orig_sizes, num_top=300):
-        """Boxes in pixels (xyxy), scores, labels per image (RT-DETR postprocessor)."""
+    def postprocess_batched(self, outputs, orig_sizes, num_top=300):
+        """RT-DETR postprocessor, stacked: (boxes [B, k, 4] xyxy pixels, scores
+        [B, k], labels [B, k]) on the outputs' device."""
         logits = outputs["pred_logits"].float()
         boxes = outputs["pred_boxes"].float()
         B, Q, C = logits.shape
@@ -118,4 +119,10 @@ class RTDETRMoE(nn.Module):
         xyxy = torch.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], -1)
         wh = torch.as_tensor(orig_sizes, dtype=xyxy.dtype, device=xyxy.device)  # [B, 2] (w, h)
         xyxy = xyxy * wh.repeat(1, 2)[:, None, :]
-        return [{"boxes": xyxy[i], "scores": sc[i], "labels": labels[i]} for i in range(B)]
+        return xyxy, sc, labels
+
+    @torch.no_grad()
+    def postprocess(self, outputs, orig_sizes, num_top=300):
+        """Boxes in pixels (xyxy), scores, labels per image (RT-DETR postprocessor)."""
+        xyxy, sc, labels = self.postprocess_batched(outputs, orig_sizes, num_top)
+        return [{"boxes": xyxy[i], "scores": sc[i], "labels": labels[i]} for i in range(xyxy.shape[0])]

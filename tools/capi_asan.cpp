@@ -79,6 +79,12 @@ int main() {
   expect_error("augment_boxes M=2048", train_augment_boxes(f32, reinterpret_cast<int64_t*>(buf), i32, f32, 1, 2048,
                                                            64, 64, 40, 60, f32 + 64, reinterpret_cast<int64_t*>(buf) + 64,
                                                            i32 + 8, f32 + 8, s));
+  const double* f64 = reinterpret_cast<const double*>(buf);
+  uint8_t* u8 = reinterpret_cast<uint8_t*>(buf);
+  expect_error("eval_match K=1025", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 1025, 4, 10, u8, s));
+  expect_error("eval_match T=17", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 4, 17, u8, s));
+  expect_error("eval_match M=0", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 0, 10, u8, s));
+  expect_error("eval_match tp=NULL", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 4, 10, nullptr, s));
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
