@@ -1005,6 +1005,40 @@ int train_augment_boxes(const float* boxes, const int64_t* labels, const int32_t
                         int B, int M, int Hp, int Wp, int h, int w, float* boxes_out, int64_t* labels_out,
                         int32_t* n_valid_out, float* total_out, hipStream_t stream);
 
+/* Mosaic augmentation (Ultralytics' _mosaic4 with border -s/2, partners taken
+ * from the step's own batch; semantics in src/rtdetr_moe/augment.py, whose
+ * mosaic_reference is the plain-torch form).  Four images of the batch are
+ * placed around an integer centre (xc, yc) on a 2w x 2h canvas filled with
+ * `fill`; the matrices of the table row map canvas <-> output.
+ * `table`: device fp32 [B, 24]: columns 0..15 as above, [16] xc, [17] yc,
+ * [18..21] the source indices of the top-left, top-right, bottom-left and
+ * bottom-right quadrant as integer-valued floats (-1, or any value outside
+ * [0, B_src): an empty quadrant -- a bad table reads nothing), [22..23] 0.
+ * Canvas pixel (X, Y), 0 <= X < 2w, 0 <= Y < 2h: right iff X >= xc, bottom iff
+ * Y >= yc; origin ox = right ? xc : xc - w, oy = bottom ? yc : yc - h; it reads
+ * pixel (X - ox, Y - oy) of the quadrant's image when that lies inside w x h,
+ * else -- and anywhere off the canvas -- `fill`.
+ *   train_mosaic_images   as train_augment_images with that tap rule; src holds
+ *       B_src images (strides as there), dst B images.  A pixel with no valid
+ *       tap is exactly `fill`.  A row with xc = w, yc = h and only the
+ *       top-left quadrant gives train_augment_images' bits for that image.
+ *   train_mosaic_boxes    per output image the quadrants in the order TL, TR,
+ *       BL, BR, within one the source's slots j < n_valid[src] (inputs
+ *       [B,M_in,...]): to content px, shifted by (ox, oy), clipped to the
+ *       canvas, then mapped and tested as in train_augment_boxes against the
+ *       clipped area.  Survivors are compacted in that order into outputs of
+ *       capacity M_out ([B,M_out,...]); past M_out they are dropped and
+ *       n_valid_out is M_out (no slot >= M_out is written).  M_in, M_out,
+ *       B <= 1024; outputs must not alias inputs.
+ * Both return non-zero (message in moe_last_error) before any launch on a bad
+ * argument. */
+int train_mosaic_images(const void* src, int src_dtype, long long sn, long long sc, long long sh, long long sw,
+                        int B_src, void* dst, int dst_dtype, const float* table, int B, int Hp, int Wp, int h, int w,
+                        float fill, hipStream_t stream);
+int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t* n_valid, const float* table, int B,
+                       int M_in, int M_out, int Hp, int Wp, int h, int w, float* boxes_out, int64_t* labels_out,
+                       int32_t* n_valid_out, float* total_out, hipStream_t stream);
+
 /* Launch profiler (measurement only; no reference counterpart).
  * While enabled, every kernel launch of the library carries a hipEvent pair
  * stamped by its own dispatch packet (hipExtLaunchKernel: kernel execution
@@ -1036,7 +1070,7 @@ enum moe_prof_kind {
   MOE_PROF_ATTN = 12,     /* multi-head self-attention (rtdetr_attn_fwd / rtdetr_attn_bwd) */
   MOE_PROF_CONV = 13,     /* implicit-GEMM convolutions (rtdetr_conv_*) */
   MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
-  MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_images / train_augment_boxes) */
+  MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
   MOE_PROF_EVAL = 16       /* validation: detections matched to ground truth (rtdetr_eval_match) */
 };
 int moe_profile_enable(int on);

@@ -33,7 +33,7 @@ enum ProfKind {
   PROF_ATTN = 12,      // multi-head self-attention (rtdetr_attn_fwd / _bwd)
   PROF_CONV = 13,      // implicit-GEMM convolutions (rtdetr_conv_*)
   PROF_ROUTER_WGRAD = 14,  // router weight / context-bias gradients (moe_router_wgrad)
-  PROF_AUGMENT = 15,       // training batch augmentation (train_augment_images / _boxes)
+  PROF_AUGMENT = 15,       // training batch augmentation (train_augment_* / train_mosaic_*)
   PROF_EVAL = 16           // validation: detections matched to ground truth (rtdetr_eval_match)
 };
 

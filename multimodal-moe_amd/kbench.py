@@ -172,13 +172,18 @@ def augment_leg(reps, rounds):
     the destination; boxes: the padded targets in and out), median over
     rounds, next to the same work done by augment_reference on GPU tensors
     (the torch-composition baseline, timed with events around the whole call,
-    its cast to bf16 channels_last included)."""
+    its cast to bf16 channels_last included).  The mosaic kernels run on the
+    same batch in the same process, each leg right after its plain
+    counterpart in every round (a [B, 24] table with mosaic on every row,
+    boxes compacted from M 16 into M_out 64)."""
     from src.rtdetr_moe import augment as A
     from src.rtdetr_moe.criterion import pad_targets
 
     B, hw, phw, M = 8, (720, 1280), (736, 1280), 16
     g = torch.Generator().manual_seed(0)
     table = A.draw_params(g, B, hw, phw).cuda()
+    mtable = A.draw_mosaic_params(torch.Generator().manual_seed(0), B, hw, phw, 1.0).cuda()
+    Mo = 64
     u8 = torch.zeros((B, 3, *phw), dtype=torch.uint8)
     u8[:, :, :hw[0]] = torch.randint(0, 256, (B, 3, *hw), generator=g, dtype=torch.uint8)
     u8 = u8.cuda()
@@ -190,15 +195,23 @@ def augment_leg(reps, rounds):
             for dt in (torch.bfloat16, torch.float32)}
     box_out = (torch.empty_like(tb), torch.empty_like(tl), torch.empty_like(nv),
                torch.empty((), dtype=torch.float32, device="cuda"))
+    mbox_out = (torch.empty((B, Mo, 4), device="cuda"), torch.empty((B, Mo), dtype=torch.int64, device="cuda"),
+                torch.empty_like(nv), torch.empty((), dtype=torch.float32, device="cuda"))
     px_src, px_dst = B * 3 * hw[0] * hw[1], B * 3 * phw[0] * phw[1]
     legs = [("augment_images u8_nchw->bf16", lambda: A.augment_images_hip(u8, table, outs[torch.bfloat16], hw),
              px_src + 2 * px_dst),
+            ("mosaic_images u8_nchw->bf16", lambda: A.mosaic_images_hip(u8, mtable, outs[torch.bfloat16], hw),
+             px_src + 2 * px_dst),
             ("augment_images f32_nhwc->bf16", lambda: A.augment_images_hip(f32, table, outs[torch.bfloat16], hw),
+             4 * px_src + 2 * px_dst),
+            ("mosaic_images f32_nhwc->bf16", lambda: A.mosaic_images_hip(f32, mtable, outs[torch.bfloat16], hw),
              4 * px_src + 2 * px_dst),
             ("augment_images f32_nhwc->f32", lambda: A.augment_images_hip(f32, table, outs[torch.float32], hw),
              4 * px_src + 4 * px_dst),
             ("augment_boxes (2 launches)", lambda: A.augment_boxes_hip(tb, tl, nv, table, hw, phw, out=box_out),
-             B * (M * 48 + 8 + 64) + 4 * B + 4)]
+             B * (M * 48 + 8 + 64) + 4 * B + 4),
+            ("mosaic_boxes (2 launches)", lambda: A.mosaic_boxes_hip(tb, tl, nv, mtable, hw, phw, out=mbox_out),
+             B * (4 * M * 24 + Mo * 24 + 8 + 96) + 4 * B + 4)]
 
     def torch_ref():
         img, *_ = A.augment_reference(f32, tb, tl, nv, table, hw)

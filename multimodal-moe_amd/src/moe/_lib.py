@@ -151,6 +151,8 @@ SIGNATURES = {
     "train_ema_update": (_I, [_P, _P, _I, _P, _F, _P]),
     "train_augment_images": (_I, [_P, _I, _LL, _LL, _LL, _LL, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "train_augment_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "train_mosaic_images": (_I, [_P, _I, _LL, _LL, _LL, _LL, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "train_mosaic_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "moe_profile_enable": (_I, [_I]),
     "moe_profile_count": (_I, []),
     "moe_profile_get": (_I, [_I, _P, _P, _P, _P]),

@@ -21,6 +21,10 @@ local architecture spec (no network fetch), e.g.::
                                   scale / translate jitter, horizontal flip and HSV jitter at Ultralytics'
                                   default magnitudes, images and boxes on the device.  The token takes no
                                   value (magnitudes: augment.AugmentParams); default: no augmentation
+    rtdetr-r50-moe8-top2-mosaic   the same with mosaic in front: four images of the batch per training
+                                  frame (Ultralytics' mosaic=1.0).  -mosaic<p> sets the probability per
+                                  image (-mosaic0.5), p in [0, 1]; the token implies -aug; the engine
+                                  turns it off for the last TrainArgs.close_mosaic epochs; default: none
 """
 from __future__ import annotations
 
@@ -92,6 +96,7 @@ class ModelSpec:
     ema_decay: float = 0.0         # EMA of the weights in training (-ema = 0.9999, -ema<d>; 0 = off)
     ema_tau: float = 2000.0        # EMA warm-up: d_t = ema_decay (1 - exp(-t / ema_tau)) (-ematau<N>)
     augment: bool = False          # GPU batch augmentation in training (-aug; rtdetr_moe/augment.py)
+    mosaic: float = 0.0            # mosaic probability per image (-mosaic = 1.0, -mosaic<p>; implies augment)
     raw: str = ""
 
 
@@ -99,8 +104,9 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug]``
-    (``-aug``: training batch augmentation, no value)."""
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]]``
+    (``-aug``: training batch augmentation, no value; ``-mosaic[<p>]``: four-image mosaic with
+    probability p, default 1.0, implies ``-aug``)."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
         raise ValueError(f"{spec!r} is a weights file, not an architecture spec")
@@ -113,6 +119,14 @@ def parse_moe_spec(spec: str) -> ModelSpec:
     moe = None
     for tok in [t for t in m.group(2).split("-") if t]:
         if tok == "aug":  # exact, ahead of every prefix match
+            out.augment = True
+        elif tok.startswith("mosaic"):  # ahead of the "moe" prefix
+            try:
+                out.mosaic = float(tok[6:]) if tok[6:] else 1.0
+            except ValueError:
+                raise ValueError(f"bad mosaic probability {tok[6:]!r} in model spec {spec!r}") from None
+            if not 0.0 <= out.mosaic <= 1.0:
+                raise ValueError(f"mosaic probability outside [0, 1] in model spec {spec!r}")
             out.augment = True
         elif tok.startswith("moe"):
             moe = moe or MoEConfig()

@@ -271,6 +271,8 @@ class TrainArgs:
     ema_decay: float | None = None  # weight average (ema.ModelEMA); None: the model spec's -ema token (0 = off)
     ema_tau: float | None = None
     augment: bool | None = None  # GPU batch augmentation (augment.BatchAugment); None: the model spec's -aug token
+    mosaic: float | None = None  # mosaic probability per image (implies augment); None: the spec's -mosaic token
+    close_mosaic: int = 10       # the last close_mosaic epochs run without mosaic (Ultralytics' close_mosaic)
 
 
 def _seed_all(seed: int):
@@ -312,7 +314,10 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
     With batch augmentation (an -aug spec token or ``augment``) the training
     batches -- never the validation ones -- go through augment.BatchAugment
     inside the step; on the GPU the file datasets then hand over uint8 images,
-    in the loader's layout (the kernel reads through strides)."""
+    in the loader's layout (the kernel reads through strides).
+    With mosaic (a -mosaic spec token or ``mosaic``) the probability is set to
+    0 from epoch ``epochs - close_mosaic`` on: the augmenter then draws
+    degenerate rows for the same kernels, so nothing is re-captured."""
     from .step import TrainStep
 
     on_gpu = local != "cpu"
@@ -339,7 +344,9 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         wdir.mkdir(parents=True, exist_ok=True)
     best_fit, best_epoch = -1.0, -1
     last_metrics = BoxMetrics()
-    augment = bool(getattr(getattr(core, "spec", None), "augment", False)) if a.augment is None else bool(a.augment)
+    mosaic = float(getattr(getattr(core, "spec", None), "mosaic", 0.0) if a.mosaic is None else a.mosaic)
+    augment = (bool(getattr(getattr(core, "spec", None), "augment", False)) or mosaic > 0) if a.augment is None \
+        else bool(a.augment)
     csv_rows = []
     epoch = 0
     step = None
@@ -369,8 +376,10 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
                                  precision="bf16" if on_gpu else "fp32",
                                  ddp_local=None, targets=tg if on_gpu else None,
                                  num_boxes=float(num_boxes), seed=a.seed, ema_decay=a.ema_decay,
-                                 ema_tau=a.ema_tau, augment=augment, content_hw=_hw(a.imgsz))
+                                 ema_tau=a.ema_tau, augment=augment, content_hw=_hw(a.imgsz), mosaic=mosaic)
                 shape = tuple(images.shape)
+            if mosaic > 0 and step.aug is not None:
+                step.aug.mosaic = 0.0 if epoch >= a.epochs - a.close_mosaic else mosaic
             if on_gpu and tuple(images.shape) != shape:
                 raise RuntimeError(f"batch shape {tuple(images.shape)} differs from the captured {shape}")
             loss = step(images, ctx, tg, num_boxes if on_gpu else float(num_boxes))

@@ -21,6 +21,9 @@ their gradients reach the router through the captured backward.
 Batch augmentation (an -aug model spec, augment.BatchAugment) runs in front of
 the step, outside every graph: with the whole-step graph its two HIP launches
 write the graph's static images, padded targets and box count directly.
+With mosaic (a -mosaic spec, TrainStep(mosaic=p)) an image carries the boxes
+of up to four, so the padding M is reserved from the augmenter's host bound
+(BatchAugment.need) before the launches.
 """
 from __future__ import annotations
 
@@ -380,12 +383,15 @@ class GraphedStep:
         if self.on_capture is not None:
             self.on_capture(self.static_grads)
 
-    def reserve(self, targets):
+    def reserve(self, targets, need=None):
         """Make room for this batch's targets: a batch with more boxes than the
-        captured padding re-captures at the next multiple of 16 (rare)."""
+        captured padding re-captures at the next multiple of 16 (rare).
+        ``need``: the boxes an image may hold when that is not the batch's
+        largest count (mosaic: BatchAugment.need)."""
         from .criterion import pad_targets
 
-        need = max((len(t["boxes"]) for t in targets), default=0)
+        if need is None:
+            need = max((len(t["boxes"]) for t in targets), default=0)
         if need > self.M:
             self.M = (need + 15) // 16 * 16
             self.tb, self.tl, self.nv = pad_targets(targets, self.M)
@@ -492,7 +498,7 @@ class TrainStep:
     def __init__(self, model: RTDETRMoE, criterion, images, ctx, *, lr=1e-4, lr_backbone=1e-5,
                  weight_decay=1e-4, clip_norm=0.1, graphs=True, ddp_local=None, world=1, precision="bf16",
                  targets=None, num_boxes=1.0, zero=None, seed=0, ema_decay=None, ema_tau=None, augment=None,
-                 content_hw=None):
+                 content_hw=None, mosaic=None):
         """seed: the run's seed (the denoising queries' noise generator, the
         augmentation parameters' generator).
         augment: batch augmentation (augment.BatchAugment: scale / translate
@@ -504,6 +510,14 @@ class TrainStep:
         inputs the kernels write; the forward / backward graph pair without
         targets is refused with a ValueError).  The eager / CPU step takes any
         batch size up to the first batch's.
+        mosaic: the probability that a training image becomes a four-image
+        mosaic of its batch (augment.py); None takes the model spec's -mosaic
+        token; a positive value implies ``augment`` unless that is False.
+        ``self.aug.mosaic`` may be changed between steps (the engine's
+        close_mosaic).  With graphs=True the first capture pads the targets to
+        max(16, 4 x the example batch's largest count rounded up to 16) -- a
+        heuristic start that spares re-captures, not a bound: every step
+        reserves the augmenter's bound and re-captures when it is larger.
         content_hw: the (h, w) of the image content inside the padded tensor
         (the augmentation's frame; default: the whole tensor).
         ema_decay / ema_tau: the weight average (ema.ModelEMA: updated once per
@@ -574,7 +588,10 @@ class TrainStep:
                     m.ep_grad_scale = 1.0
         spec = getattr(model, "spec", None)
         self.aug = None
-        if bool(getattr(spec, "augment", False)) if augment is None else bool(augment):
+        self._m_in = 16  # the mosaic path's raw-target padding: grows with the batches' counts
+        mosaic = float(getattr(spec, "mosaic", 0.0) if mosaic is None else mosaic)
+        max_boxes = None
+        if (bool(getattr(spec, "augment", False)) or mosaic > 0) if augment is None else bool(augment):
             from .augment import BatchAugment
 
             if graphs and targets is None:
@@ -583,7 +600,11 @@ class TrainStep:
             padded_hw = tuple(images.shape[-2:])
             self.aug = BatchAugment(images.shape[0], content_hw or padded_hw, padded_hw, images.device, seed=seed,
                                     rank=rank,
-                                    out_dtype=torch.bfloat16 if self.precision == "bf16" else torch.float32)
+                                    out_dtype=torch.bfloat16 if self.precision == "bf16" else torch.float32,
+                                    mosaic=mosaic)
+            if self.aug.mosaic_path and targets is not None:
+                most = max((len(t["boxes"]) for t in targets), default=0)
+                max_boxes = max(16, (4 * most + 15) // 16 * 16)   # a starting point, see ``mosaic`` above
             # the static image buffer is what the kernel writes: float, channels_last
             if images.dtype == torch.uint8:
                 images = images.float() / 255.0
@@ -599,7 +620,8 @@ class TrainStep:
             raise ValueError("a model with denoising queries needs targets= for graphs=True (the whole-step graph)")
         if graphs and targets is not None:  # whole step as one graph (GPU matcher)
             self.stepper = GraphedStep(self.flat, criterion, self.params, images, ctx, targets, num_boxes,
-                                       autocast=self.precision == "amp", on_capture=self._bind_grads, dn=self.dn)
+                                       autocast=self.precision == "amp", on_capture=self._bind_grads, dn=self.dn,
+                                       max_boxes=max_boxes)
             self.fn = None
             self.ddp = None
         elif graphs:
@@ -643,10 +665,23 @@ class TrainStep:
         from .criterion import pad_targets
 
         st = self.stepper
-        st.reserve(targets)
-        raw = self.aug.raw_targets(st.M)
-        pad_targets(targets, st.M, *raw)
-        _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images, out_targets=(st.tb, st.tl, st.nv))
+        if self.aug.mosaic_path:
+            # an image holds the boxes of up to four: reserve the host bound for this step's table, then
+            # compact from raw buffers of the batch's own padding (M_in) into the graph's (M_out = st.M)
+            counts = [len(t["boxes"]) for t in targets]
+            table = self.aug.draw(len(targets))
+            st.reserve(targets, need=self.aug.need(counts, table))
+            self._m_in = max(self._m_in, (max(counts, default=0) + 15) // 16 * 16)
+            raw = self.aug.raw_targets(self._m_in)
+            pad_targets(targets, self._m_in, *raw)
+            _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images,
+                                         out_targets=(st.tb, st.tl, st.nv), table=table)
+        else:
+            st.reserve(targets)
+            raw = self.aug.raw_targets(st.M)
+            pad_targets(targets, st.M, *raw)
+            _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images,
+                                         out_targets=(st.tb, st.tl, st.nv))
         self._box_count(total, st.nb)
 
     def _box_count(self, total, out):
@@ -667,7 +702,12 @@ class TrainStep:
         M = max(16, (need + 15) // 16 * 16)
         raw = self.aug.raw_targets(M, len(targets))  # a shorter batch (an epoch's last) uses the leading slots
         pad_targets(targets, M, *raw)
-        img, tb, tl, nv, total = self.aug(images, *raw)
+        if self.aug.mosaic_path:  # the output capacity from the same host bound as the graphed step's
+            table = self.aug.draw(len(targets))
+            bound = self.aug.need([len(t["boxes"]) for t in targets], table)
+            img, tb, tl, nv, total = self.aug(images, *raw, table=table, M_out=max(16, (bound + 15) // 16 * 16))
+        else:
+            img, tb, tl, nv, total = self.aug(images, *raw)
         nb = self._box_count(total, torch.empty_like(total))
         return img, targets_from_padded(tb, tl, nv), nb if img.is_cuda else float(nb)
 
