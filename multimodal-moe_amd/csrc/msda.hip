@@ -4,17 +4,34 @@
 //
 //   out[b,q,h,c] = sum_{l,p} attn[b,q,h,l,p] * bilinear(value_l[b,:,:,h,c], loc[b,q,h,l,p])
 //
-// with grid_sample's conventions (align_corners = False, zero padding):
-// pixel = loc * size - 0.5.  value is the flattened multi-level memory
-// [B, S, H, D] (level l occupies rows starts[l] .. starts[l] + h_l*w_l).
+// with grid_sample's conventions (align_corners = False, zero padding).
+// value is the flattened multi-level bf16 memory [B, S, H, D] (level l occupies
+// rows starts[l] .. starts[l] + h_l*w_l); the fused kernels take its row
+// stride ldv, so a layer can read its column slice of a wider buffer.
 //
-// Geometry: one (b, q, h) per group of D/2 lanes; each lane owns 2 adjacent
-// channels (4-B bf16x2 loads: a group reads a 64-B contiguous row segment per
-// corner), 256-thread blocks.  Forward: registers only.  Backward: per sample,
-// the group reduces <grad_out, value> terms with xor-shuffles for the
-// attention-weight and location gradients; the value gradient is scattered
-// with fp32 atomics into an fp32 buffer (each corner row segment is 64-256 B
-// contiguous per wave-instruction).
+// Every sampling kernel: one (b, q, h) per group of LPG = D/2 lanes; each lane
+// owns 2 adjacent channels (4-B bf16x2 loads: a group reads a 64-B contiguous
+// row segment per corner), 256-thread blocks.  Forward: registers only.
+// Backward: per sample, the group reduces <grad_out, value> terms with
+// xor-shuffles for the attention-weight and location gradients, and scatters
+// the value gradient.
+//   msda_fwd / msda_bwd<.., GV16>   loc and attn given (fp32); value gradient by
+//       packed bf16 atomics, or (GV16 = false, the tests' reference) fp32 atomics
+//   msda_fused_fwd / _bwd           loc and softmax formed in the kernel from the
+//       raw linear outputs, any L * P <= 16; packed bf16 atomics
+//   msda_fused_fwd_lp / _bwd_lp     the same, level-batched for a fixed L x P
+//   msda_fused_bwd_lp<.., REC> + msda_vgrad_sort / _tile   deterministic value
+//       gradient: contributions recorded, then summed in a fixed order in fp32
+//
+// The arithmetic the families share is written once, in the helpers below:
+// the bilinear tap and its in-map corners (msda_tap .. msda_load_corner), a
+// sample's forward value (msda_bilinear) and backward terms
+// (msda_sample_grad), the packed bf16 atomic add (msda_vgrad_add), and the
+// fused location rule with its gradient (msda_fused_tap, msda_fused_grad_off;
+// tests/test_gpu_msda.py's _vgrad_reference restates that rule).
+// Corners are numbered c = 0..3: bit 0 is x + 1, bit 1 is y + 1.
+#include <type_traits>
+
 #include "moe_common.h"
 #include "prof.h"
 
@@ -35,9 +52,116 @@ __device__ __forceinline__ MsdaLevels load_levels(const int32_t* shapes, const i
   return lv;
 }
 
-__device__ __forceinline__ float2 ld_bf16x2(const uint16_t* p) {
-  const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+// a lane's 2 adjacent bf16 channels (or a sample's x, y offsets) as one 4-B word
+__device__ __forceinline__ uint32_t ld_pair(const uint16_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
+
+__device__ __forceinline__ float2 unpack_bf16x2(uint32_t v) {
   return make_float2(__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u));
+}
+
+// A sample's bilinear tap on a level of Hl x Wl pixels: the top-left corner
+// and the fractions towards the next column / row.
+struct MsdaTap {
+  int x0, y0;
+  float fx, fy;
+};
+
+__device__ __forceinline__ MsdaTap msda_tap(float lx, float ly, int Hl, int Wl) {
+  const float x = lx * Wl - 0.5f, y = ly * Hl - 0.5f;
+  const float xf = floorf(x), yf = floorf(y);
+  return {(int)xf, (int)yf, x - xf, y - yf};
+}
+
+// Whether pixel (xi, yi) lies inside a level of Hl x Wl pixels.  A macro, and
+// msda_level_geo and the REC path write a corner's (xi, yi) and row out: as
+// calls these are simplified on their own before inlining (to bitwise ANDs),
+// and the level-batched kernels then compile to other, slower code.
+#define MSDA_IN_MAP(xi, yi, Hl, Wl) ((xi) >= 0 && (xi) < (Wl) && (yi) >= 0 && (yi) < (Hl))
+
+__device__ __forceinline__ bool msda_corner_in(const MsdaTap& t, int c, int Hl, int Wl) {
+  const int xi = t.x0 + (c & 1), yi = t.y0 + (c >> 1);
+  return MSDA_IN_MAP(xi, yi, Hl, Wl);
+}
+
+// row of corner c within its level
+__device__ __forceinline__ int msda_corner_row(const MsdaTap& t, int c, int Wl) {
+  const int xi = t.x0 + (c & 1), yi = t.y0 + (c >> 1);
+  return yi * Wl + xi;
+}
+
+// The lane's channel pair at corner c (vb: the level's first row at the lane's
+// channels, `stride` elements per row) and whether the corner is inside the
+// map: zeros and false outside, and for a lane without work (!valid).
+__device__ __forceinline__ bool msda_load_corner(const MsdaTap& t, int c, int Hl, int Wl, const uint16_t* vb,
+                                                 size_t stride, bool valid, float2& v) {
+  const bool in = msda_corner_in(t, c, Hl, Wl) && valid;
+  v = in ? unpack_bf16x2(ld_pair(vb + (size_t)msda_corner_row(t, c, Wl) * stride)) : make_float2(0.f, 0.f);
+  return in;
+}
+
+// A sample's forward value: the weighted sum over the corners inside the map
+// (corner weights as w00 .. w11 of msda_sample_grad: the two must agree).
+// inside(c) says whether corner c is inside, load(c) returns the lane's channel
+// pair there (the generic kernels load it at that point, the level-batched
+// ones have it in registers).
+template <class Inside, class Load>
+__device__ __forceinline__ float2 msda_bilinear(float fx, float fy, Inside&& inside, Load&& load) {
+  float2 s = make_float2(0.f, 0.f);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (!inside(c)) continue;
+    const float wgt = ((c & 1) ? fx : 1.f - fx) * ((c >> 1) ? fy : 1.f - fy);
+    const float2 v = load(c);
+    s.x += wgt * v.x;
+    s.y += wgt * v.y;
+  }
+  return s;
+}
+
+// A sample's backward terms from the lane's 4 corner values (0 outside the
+// map) and its grad_out pair g: the corner weights, and -- summed over the
+// group's channels -- ga = d out / d attn and gx, gy = d out / d pixel x, y
+// per unit attn.  Every lane of the group must call it (shuffles).
+template <int LPG>
+__device__ __forceinline__ void msda_sample_grad(const float2 (&v)[2][2], float fx, float fy, float2 g,
+                                                 float (&w)[4], float& ga, float& gx, float& gy) {
+  const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
+  const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+  // sampled value and its spatial derivatives (per channel)
+  const float sx = w00 * v[0][0].x + w01 * v[0][1].x + w10 * v[1][0].x + w11 * v[1][1].x;
+  const float sy = w00 * v[0][0].y + w01 * v[0][1].y + w10 * v[1][0].y + w11 * v[1][1].y;
+  const float dxa = (1.f - fy) * (v[0][1].x - v[0][0].x) + fy * (v[1][1].x - v[1][0].x);
+  const float dxb = (1.f - fy) * (v[0][1].y - v[0][0].y) + fy * (v[1][1].y - v[1][0].y);
+  const float dya = (1.f - fx) * (v[1][0].x - v[0][0].x) + fx * (v[1][1].x - v[0][1].x);
+  const float dyb = (1.f - fx) * (v[1][0].y - v[0][0].y) + fx * (v[1][1].y - v[0][1].y);
+  ga = g.x * sx + g.y * sy;           // d out / d attn
+  gx = g.x * dxa + g.y * dxb;         // d out / d x (per unit attn)
+  gy = g.x * dya + g.y * dyb;
+  ga = group_sum<LPG>(ga);
+  gx = group_sum<LPG>(gx);
+  gy = group_sum<LPG>(gy);
+  w[0] = w00; w[1] = w01; w[2] = w10; w[3] = w11;
+}
+
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+// One corner's value-gradient contribution into a bf16 grad_value: a lane's 2
+// channels (packed bf16, e.g. msda_vgrad_pair(s, g)) in one
+// global_atomic_pk_add_bf16 -- half the atomics and half the zero-fill of an
+// fp32 buffer, and no fp32 -> bf16 pass afterwards.  Each (token, head) row
+// receives < 1 contribution per step on average (230K samples x 4 corners over
+// 1.2M rows at C2), so the per-add bf16 rounding stays at the level of the
+// final cast it replaces (tests/test_gpu_msda.py).
+__device__ __forceinline__ uint32_t msda_vgrad_pair(float s, float2 g) {
+  bf16x2_t t;
+  t.x = (__bf16)(s * g.x);
+  t.y = (__bf16)(s * g.y);
+  return __builtin_bit_cast(uint32_t, t);
+}
+
+__device__ __forceinline__ void msda_vgrad_add(uint16_t* dst, uint32_t pair) {
+  __builtin_amdgcn_global_atomic_fadd_v2bf16((__attribute__((address_space(1))) bf16x2_t*)dst,
+                                             __builtin_bit_cast(bf16x2_t, pair));
 }
 
 template <int LPG>  // lanes per (b,q,h) group = D / 2
@@ -63,41 +187,19 @@ __global__ __launch_bounds__(256) void msda_fwd_kernel(const uint16_t* __restric
       const uint16_t* vb = value + ((size_t)b * S + lv.start[l]) * H * D + h * D + 2 * sub;
       for (int p = 0; p < P; ++p) {
         const int sp = l * P + p;
-        const float x = lp[2 * sp] * Wl - 0.5f;
-        const float y = lp[2 * sp + 1] * Hl - 0.5f;
+        const MsdaTap t = msda_tap(lp[2 * sp], lp[2 * sp + 1], Hl, Wl);
         const float a = ap[sp];
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = (int)xf, y0 = (int)yf;
-        const float fx = x - xf, fy = y - yf;
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int cy = 0; cy < 2; ++cy) {
-#pragma unroll
-          for (int cx = 0; cx < 2; ++cx) {
-            const int xi = x0 + cx, yi = y0 + cy;
-            if (xi < 0 || xi >= Wl || yi < 0 || yi >= Hl) continue;
-            const float wgt = (cx ? fx : 1.f - fx) * (cy ? fy : 1.f - fy);
-            const float2 v = ld_bf16x2(vb + (size_t)(yi * Wl + xi) * H * D);
-            s0 += wgt * v.x;
-            s1 += wgt * v.y;
-          }
-        }
-        acc0 += a * s0;
-        acc1 += a * s1;
+        const float2 s = msda_bilinear(
+            t.fx, t.fy, [&](int c) { return msda_corner_in(t, c, Hl, Wl); },
+            [&](int c) { return unpack_bf16x2(ld_pair(vb + (size_t)msda_corner_row(t, c, Wl) * H * D)); });
+        acc0 += a * s.x;
+        acc1 += a * s.y;
       }
     }
     *reinterpret_cast<uint32_t*>(out + (size_t)gidx * D + 2 * sub) = pack2bf(acc0, acc1);
   }
 }
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-// GV16: grad_value is bf16 and accumulated with packed bf16 atomics
-// (global_atomic_pk_add_bf16: a lane's 2 channels in one operation) -- half
-// the atomics, half the zero-fill, and no fp32 -> bf16 pass afterwards.  Each
-// (token, head) row receives < 1 contribution per step on average (230K
-// samples x 4 corners over 1.2M rows at C2), so the per-add bf16 rounding
-// stays at the level of the final cast it replaces (tests/test_gpu_msda.py).
 template <int LPG, bool GV16>
 __global__ __launch_bounds__(256) void msda_bwd_kernel(
     const uint16_t* __restrict__ value, const int32_t* __restrict__ shapes,
@@ -120,7 +222,7 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(
     const int b = gi / (Q * H);
     const float* lp = loc + (size_t)gi * L * P * 2;
     const float* ap = attn + (size_t)gi * L * P;
-    const float2 g = valid ? ld_bf16x2(grad_out + (size_t)gi * D + 2 * sub) : make_float2(0.f, 0.f);
+    const float2 g = valid ? unpack_bf16x2(ld_pair(grad_out + (size_t)gi * D + 2 * sub)) : make_float2(0.f, 0.f);
     for (int l = 0; l < L; ++l) {
       const int Hl = lv.h[l], Wl = lv.w[l];
       const size_t row0 = (size_t)b * S + lv.start[l];
@@ -128,62 +230,33 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(
       const size_t gofs = row0 * H * D + h * D + 2 * sub;
       for (int p = 0; p < P; ++p) {
         const int sp = l * P + p;
-        const float x = lp[2 * sp] * Wl - 0.5f;
-        const float y = lp[2 * sp + 1] * Hl - 0.5f;
         const float a = ap[sp];
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = (int)xf, y0 = (int)yf;
-        const float fx = x - xf, fy = y - yf;
+        const MsdaTap t = msda_tap(lp[2 * sp], lp[2 * sp + 1], Hl, Wl);
         float2 v[2][2];
-        bool in[2][2];
+        bool in[4];
 #pragma unroll
-        for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-          for (int cx = 0; cx < 2; ++cx) {
-            const int xi = x0 + cx, yi = y0 + cy;
-            in[cy][cx] = valid && xi >= 0 && xi < Wl && yi >= 0 && yi < Hl;
-            v[cy][cx] = in[cy][cx] ? ld_bf16x2(vb + (size_t)(yi * Wl + xi) * H * D) : make_float2(0.f, 0.f);
-          }
-        // sampled value and its spatial derivatives (per channel)
-        const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-        const float w10 = (1.f - fx) * fy, w11 = fx * fy;
-        const float sx = w00 * v[0][0].x + w01 * v[0][1].x + w10 * v[1][0].x + w11 * v[1][1].x;
-        const float sy = w00 * v[0][0].y + w01 * v[0][1].y + w10 * v[1][0].y + w11 * v[1][1].y;
-        const float dxa = (1.f - fy) * (v[0][1].x - v[0][0].x) + fy * (v[1][1].x - v[1][0].x);
-        const float dxb = (1.f - fy) * (v[0][1].y - v[0][0].y) + fy * (v[1][1].y - v[1][0].y);
-        const float dya = (1.f - fx) * (v[1][0].x - v[0][0].x) + fx * (v[1][1].x - v[0][1].x);
-        const float dyb = (1.f - fx) * (v[1][0].y - v[0][0].y) + fx * (v[1][1].y - v[0][1].y);
-        float ga = g.x * sx + g.y * sy;           // d out / d attn
-        float gx = g.x * dxa + g.y * dxb;         // d out / d x (per unit attn)
-        float gy = g.x * dya + g.y * dyb;
-        ga = group_sum<LPG>(ga);
-        gx = group_sum<LPG>(gx);
-        gy = group_sum<LPG>(gy);
+        for (int c = 0; c < 4; ++c)
+          in[c] = msda_load_corner(t, c, Hl, Wl, vb, (size_t)H * D, valid, v[c >> 1][c & 1]);
+        float wc[4], ga, gx, gy;
+        msda_sample_grad<LPG>(v, t.fx, t.fy, g, wc, ga, gx, gy);
         if (valid && sub == 0) {
           grad_attn[(size_t)gi * L * P + sp] = ga;
           grad_loc[((size_t)gi * L * P + sp) * 2] = a * gx * Wl;
           grad_loc[((size_t)gi * L * P + sp) * 2 + 1] = a * gy * Hl;
         }
-        const float wc[2][2] = {{w00, w01}, {w10, w11}};
 #pragma unroll
-        for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-          for (int cx = 0; cx < 2; ++cx) {
-            if (!in[cy][cx]) continue;
-            const float s = a * wc[cy][cx];
-            const size_t o = gofs + (size_t)((y0 + cy) * Wl + (x0 + cx)) * H * D;
-            if constexpr (GV16) {
-              bf16x2_t pv;
-              pv.x = (__bf16)(s * g.x);
-              pv.y = (__bf16)(s * g.y);
-              __builtin_amdgcn_global_atomic_fadd_v2bf16(
-                  (__attribute__((address_space(1))) bf16x2_t*)(static_cast<uint16_t*>(grad_value_) + o), pv);
-            } else {
-              float* dst = static_cast<float*>(grad_value_) + o;
-              atomicAdd(dst, s * g.x);
-              atomicAdd(dst + 1, s * g.y);
-            }
+        for (int c = 0; c < 4; ++c) {
+          if (!in[c]) continue;
+          const float s = a * wc[c];
+          const size_t o = gofs + (size_t)msda_corner_row(t, c, Wl) * H * D;
+          if constexpr (GV16) {
+            msda_vgrad_add(static_cast<uint16_t*>(grad_value_) + o, msda_vgrad_pair(s, g));
+          } else {
+            float* dst = static_cast<float*>(grad_value_) + o;
+            atomicAdd(dst, s * g.x);
+            atomicAdd(dst + 1, s * g.y);
           }
+        }
       }
     }
   }
@@ -192,12 +265,11 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(
 // ---------------------------------------------------------------------------
 // Fused variant (decoder cross-attention, TrainStep): the sampling locations
 // and attention weights are formed inside the kernel from the raw linear
-// outputs -- loc = ref.xy + bf16(off / P) * ref.wh * offset_scale and
-// attn = softmax over the L*P logits of the (b, q, h) group -- and the
-// backward returns the gradients of those linear outputs (softmax backward
-// and the location chain rule fused).  Replaces ~14 element-wise launches per
-// decoder layer.  ref carries no gradient (RT-DETR detaches the reference
-// boxes).  L*P <= 16.
+// outputs -- loc by msda_fused_tap below and attn = softmax over the L*P
+// logits of the (b, q, h) group -- and the backward returns the gradients of
+// those linear outputs (softmax backward and the location chain rule fused).
+// Replaces ~14 element-wise launches per decoder layer.  ref carries no
+// gradient (RT-DETR detaches the reference boxes).  L*P <= 16.
 // ---------------------------------------------------------------------------
 constexpr int MSDA_LP_MAX = 16;
 
@@ -236,6 +308,28 @@ __device__ __forceinline__ float msda_pick(const float (&v)[MSDA_LP_MAX], int i)
   return r;
 }
 
+// The fused location rule: a sample's offset (oxy: the bf16 linear outputs for
+// x and y, as one 4-B word) is divided by P and rounded to bf16 again -- as the
+// unfused decoder's bf16 `off / P` -- and then scales the reference box in fp32:
+//   loc = ref.xy + bf16(off / P) * ref.wh * offset_scale        (invP = 1 / P)
+// Returns the sample's tap on a level of Hl x Wl pixels.
+__device__ __forceinline__ MsdaTap msda_fused_tap(uint32_t oxy, const MsdaPrep& pr, float offset_scale, float invP,
+                                                  int Hl, int Wl) {
+  const float ox = bf2f(f2bf(bf2f((uint16_t)(oxy & 0xffffu)) * invP));
+  const float oy = bf2f(f2bf(bf2f((uint16_t)(oxy >> 16)) * invP));
+  const float lx = pr.rx + ox * pr.rw * offset_scale;
+  const float ly = pr.ry + oy * pr.rh * offset_scale;
+  return msda_tap(lx, ly, Hl, Wl);
+}
+
+// ... and its backward, from the location gradient (glx, gly) to the packed
+// bf16 offset gradient: d loc / d off = ref.wh * offset_scale / P, straight
+// through the bf16 rounding.
+__device__ __forceinline__ uint32_t msda_fused_grad_off(float glx, float gly, const MsdaPrep& pr, float offset_scale,
+                                                        float invP) {
+  return pack2bf(glx * pr.rw * offset_scale * invP, gly * pr.rh * offset_scale * invP);
+}
+
 template <int LPG>
 __global__ __launch_bounds__(256) void msda_fused_fwd_kernel(
     const uint16_t* __restrict__ value, const int32_t* __restrict__ shapes, const int32_t* __restrict__ starts,
@@ -261,29 +355,13 @@ __global__ __launch_bounds__(256) void msda_fused_fwd_kernel(
       const uint16_t* vb = value + row0 * ldv + h * D + 2 * sub;
       for (int p = 0; p < P; ++p) {
         const int sp = l * P + p;
-        const float ox = bf2f(f2bf(bf2f(op[2 * sp]) * invP)), oy = bf2f(f2bf(bf2f(op[2 * sp + 1]) * invP));
-        const float lx = pr.rx + ox * pr.rw * offset_scale;
-        const float ly = pr.ry + oy * pr.rh * offset_scale;
+        const MsdaTap t = msda_fused_tap(op[2 * sp] | (uint32_t)op[2 * sp + 1] << 16, pr, offset_scale, invP, Hl, Wl);
         const float a = msda_pick(pr.a, sp);
-        const float x = lx * Wl - 0.5f, y = ly * Hl - 0.5f;
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = (int)xf, y0 = (int)yf;
-        const float fx = x - xf, fy = y - yf;
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int cy = 0; cy < 2; ++cy) {
-#pragma unroll
-          for (int cx = 0; cx < 2; ++cx) {
-            const int xi = x0 + cx, yi = y0 + cy;
-            if (xi < 0 || xi >= Wl || yi < 0 || yi >= Hl) continue;
-            const float wgt = (cx ? fx : 1.f - fx) * (cy ? fy : 1.f - fy);
-            const float2 v = ld_bf16x2(vb + (size_t)(yi * Wl + xi) * ldv);
-            s0 += wgt * v.x;
-            s1 += wgt * v.y;
-          }
-        }
-        acc0 += a * s0;
-        acc1 += a * s1;
+        const float2 s = msda_bilinear(
+            t.fx, t.fy, [&](int c) { return msda_corner_in(t, c, Hl, Wl); },
+            [&](int c) { return unpack_bf16x2(ld_pair(vb + (size_t)msda_corner_row(t, c, Wl) * ldv)); });
+        acc0 += a * s.x;
+        acc1 += a * s.y;
       }
     }
     *reinterpret_cast<uint32_t*>(out + (size_t)gidx * D + 2 * sub) = pack2bf(acc0, acc1);
@@ -315,7 +393,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_kernel(
     MsdaPrep pr;
     msda_prep(logits, ref, gi, H, LP, pr);
     const uint16_t* op = off + (size_t)gi * LP * 2;
-    const float2 g = valid ? ld_bf16x2(grad_out + (size_t)gi * D + 2 * sub) : make_float2(0.f, 0.f);
+    const float2 g = valid ? unpack_bf16x2(ld_pair(grad_out + (size_t)gi * D + 2 * sub)) : make_float2(0.f, 0.f);
     float gaa[MSDA_LP_MAX];
 #pragma unroll
     for (int i = 0; i < MSDA_LP_MAX; ++i) gaa[i] = 0.f;
@@ -327,62 +405,27 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_kernel(
       const size_t gofs = row0 * ldv + h * D + 2 * sub;
       for (int p = 0; p < P; ++p) {
         const int sp = l * P + p;
-        const float ox = bf2f(f2bf(bf2f(op[2 * sp]) * invP)), oy = bf2f(f2bf(bf2f(op[2 * sp + 1]) * invP));
-        const float lx = pr.rx + ox * pr.rw * offset_scale;
-        const float ly = pr.ry + oy * pr.rh * offset_scale;
+        const MsdaTap t = msda_fused_tap(op[2 * sp] | (uint32_t)op[2 * sp + 1] << 16, pr, offset_scale, invP, Hl, Wl);
         const float a = msda_pick(pr.a, sp);
-        const float x = lx * Wl - 0.5f, y = ly * Hl - 0.5f;
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = (int)xf, y0 = (int)yf;
-        const float fx = x - xf, fy = y - yf;
         float2 v[2][2];
-        bool in[2][2];
+        bool in[4];
 #pragma unroll
-        for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-          for (int cx = 0; cx < 2; ++cx) {
-            const int xi = x0 + cx, yi = y0 + cy;
-            in[cy][cx] = valid && xi >= 0 && xi < Wl && yi >= 0 && yi < Hl;
-            v[cy][cx] = in[cy][cx] ? ld_bf16x2(vb + (size_t)(yi * Wl + xi) * ldv) : make_float2(0.f, 0.f);
-          }
-        const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-        const float w10 = (1.f - fx) * fy, w11 = fx * fy;
-        const float sx = w00 * v[0][0].x + w01 * v[0][1].x + w10 * v[1][0].x + w11 * v[1][1].x;
-        const float sy = w00 * v[0][0].y + w01 * v[0][1].y + w10 * v[1][0].y + w11 * v[1][1].y;
-        const float dxa = (1.f - fy) * (v[0][1].x - v[0][0].x) + fy * (v[1][1].x - v[1][0].x);
-        const float dxb = (1.f - fy) * (v[0][1].y - v[0][0].y) + fy * (v[1][1].y - v[1][0].y);
-        const float dya = (1.f - fx) * (v[1][0].x - v[0][0].x) + fx * (v[1][1].x - v[0][1].x);
-        const float dyb = (1.f - fx) * (v[1][0].y - v[0][0].y) + fx * (v[1][1].y - v[0][1].y);
-        float ga = g.x * sx + g.y * sy;
-        float gx = g.x * dxa + g.y * dxb;
-        float gy = g.x * dya + g.y * dyb;
-        ga = group_sum<LPG>(ga);
-        gx = group_sum<LPG>(gx);
-        gy = group_sum<LPG>(gy);
+        for (int c = 0; c < 4; ++c) in[c] = msda_load_corner(t, c, Hl, Wl, vb, ldv, valid, v[c >> 1][c & 1]);
+        float wc[4], ga, gx, gy;
+        msda_sample_grad<LPG>(v, t.fx, t.fy, g, wc, ga, gx, gy);
 #pragma unroll
         for (int i = 0; i < MSDA_LP_MAX; ++i)
           if (i == sp) gaa[i] = ga;
         dot += a * ga;
-        if (valid && sub == 0) {  // d loc / d off = wh * offset_scale / P (straight through the bf16 rounding)
-          const float glx = a * gx * Wl, gly = a * gy * Hl;
-          const uint32_t o = pack2bf(glx * pr.rw * offset_scale * invP, gly * pr.rh * offset_scale * invP);
-          *reinterpret_cast<uint32_t*>(grad_off + ((size_t)gi * LP + sp) * 2) = o;
+        if (valid && sub == 0)
+          *reinterpret_cast<uint32_t*>(grad_off + ((size_t)gi * LP + sp) * 2) =
+              msda_fused_grad_off(a * gx * Wl, a * gy * Hl, pr, offset_scale, invP);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (!in[c]) continue;
+          const float s = a * wc[c];
+          msda_vgrad_add(grad_value + gofs + (size_t)msda_corner_row(t, c, Wl) * ldv, msda_vgrad_pair(s, g));
         }
-        const float wc[2][2] = {{w00, w01}, {w10, w11}};
-#pragma unroll
-        for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-          for (int cx = 0; cx < 2; ++cx) {
-            if (!in[cy][cx]) continue;
-            const float s = a * wc[cy][cx];
-            bf16x2_t pv;
-            pv.x = (__bf16)(s * g.x);
-            pv.y = (__bf16)(s * g.y);
-            __builtin_amdgcn_global_atomic_fadd_v2bf16(
-                (__attribute__((address_space(1))) bf16x2_t*)(grad_value + gofs +
-                                                              (size_t)((y0 + cy) * Wl + (x0 + cx)) * ldv),
-                pv);
-          }
       }
     }
     // softmax backward: d logit_sp = a_sp (ga_sp - sum_j a_j ga_j); lane `sub` writes sample sub
@@ -392,7 +435,6 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_kernel(
     }
   }
 }
-
 
 // ---------------------------------------------------------------------------
 // Level-batched fused kernels for the RT-DETR decoder's fixed L = LL, P = PP
@@ -425,30 +467,19 @@ __device__ __forceinline__ void msda_level_geo(const MsdaLevels& lv, int l, cons
   g.in = 0u;
 #pragma unroll
   for (int p = 0; p < PP; ++p) {
-    const int sp = l * PP + p;
-    const uint32_t ow = offw[sp];
-    const float ox = bf2f(f2bf(bf2f((uint16_t)(ow & 0xffffu)) * invP));
-    const float oy = bf2f(f2bf(bf2f((uint16_t)(ow >> 16)) * invP));
-    const float lx = pr.rx + ox * pr.rw * offset_scale;
-    const float ly = pr.ry + oy * pr.rh * offset_scale;
-    const float x = lx * Wl - 0.5f, y = ly * Hl - 0.5f;
-    const float xf = floorf(x), yf = floorf(y);
-    g.x0[p] = (int)xf;
-    g.y0[p] = (int)yf;
-    g.fx[p] = x - xf;
-    g.fy[p] = y - yf;
+    const MsdaTap t = msda_fused_tap(offw[l * PP + p], pr, offset_scale, invP, Hl, Wl);
+    g.x0[p] = t.x0;
+    g.y0[p] = t.y0;
+    g.fx[p] = t.fx;
+    g.fy[p] = t.fy;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const int xi = g.x0[p] + (c & 1), yi = g.y0[p] + (c >> 1);
-      const bool in = valid && xi >= 0 && xi < Wl && yi >= 0 && yi < Hl;
+      const int xi = t.x0 + (c & 1), yi = t.y0 + (c >> 1);
+      const bool in = valid && MSDA_IN_MAP(xi, yi, Hl, Wl);
       g.in |= in ? (1u << (4 * p + c)) : 0u;
-      g.raw[p][c] = in ? *reinterpret_cast<const uint32_t*>(vb + (size_t)(yi * Wl + xi) * ldv) : 0u;
+      g.raw[p][c] = in ? ld_pair(vb + (size_t)(yi * Wl + xi) * ldv) : 0u;
     }
   }
-}
-
-__device__ __forceinline__ float2 unpack_bf16x2(uint32_t v) {
-  return make_float2(__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u));
 }
 
 template <int LPG, int LL, int PP>
@@ -479,19 +510,12 @@ __global__ __launch_bounds__(256) void msda_fused_fwd_lp_kernel(
       msda_level_geo<LPG, LL, PP>(lv, l, pr, offw, offset_scale, vb, ldv, true, g);
 #pragma unroll
       for (int p = 0; p < PP; ++p) {
-        const float fx = g.fx[p], fy = g.fy[p];
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (!(g.in & (1u << (4 * p + c)))) continue;
-          const float wgt = ((c & 1) ? fx : 1.f - fx) * ((c >> 1) ? fy : 1.f - fy);
-          const float2 v = unpack_bf16x2(g.raw[p][c]);
-          s0 += wgt * v.x;
-          s1 += wgt * v.y;
-        }
+        const float2 s = msda_bilinear(
+            g.fx[p], g.fy[p], [&](int c) { return (g.in & (1u << (4 * p + c))) != 0; },
+            [&](int c) { return unpack_bf16x2(g.raw[p][c]); });
         const float a = pr.a[l * PP + p];
-        acc0 += a * s0;
-        acc1 += a * s1;
+        acc0 += a * s.x;
+        acc1 += a * s.y;
       }
     }
     *reinterpret_cast<uint32_t*>(out + (size_t)gidx * D + 2 * sub) = pack2bf(acc0, acc1);
@@ -531,7 +555,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_lp_kernel(
     for (int i = 0; i < LP; ++i) offw[i] = op[i];
     MsdaPrep pr;
     msda_prep(logits, ref, gi, H, LP, pr);
-    const float2 g = valid ? ld_bf16x2(grad_out + (size_t)gi * D + 2 * sub) : make_float2(0.f, 0.f);
+    const float2 g = valid ? unpack_bf16x2(ld_pair(grad_out + (size_t)gi * D + 2 * sub)) : make_float2(0.f, 0.f);
     float my_ga = 0.f;        // ga of sample `sub`
     uint32_t my_goff = 0u;    // packed offset gradient of sample `sub`
     float dot = 0.f;          // sum_sp a_sp ga_sp (softmax backward)
@@ -549,39 +573,21 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_lp_kernel(
 #pragma unroll
       for (int p = 0; p < PP; ++p) {
         const int sp = l * PP + p;
-        const float fx = cur.fx[p], fy = cur.fy[p];
+        const float fx = cur.fx[p], fy = cur.fy[p];  // (read before the unpack: the REC code depends on the order)
         float2 v[2][2];
 #pragma unroll
         for (int c = 0; c < 4; ++c) v[c >> 1][c & 1] = unpack_bf16x2(cur.raw[p][c]);
-        const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-        const float w10 = (1.f - fx) * fy, w11 = fx * fy;
-        const float sx = w00 * v[0][0].x + w01 * v[0][1].x + w10 * v[1][0].x + w11 * v[1][1].x;
-        const float sy = w00 * v[0][0].y + w01 * v[0][1].y + w10 * v[1][0].y + w11 * v[1][1].y;
-        const float dxa = (1.f - fy) * (v[0][1].x - v[0][0].x) + fy * (v[1][1].x - v[1][0].x);
-        const float dxb = (1.f - fy) * (v[0][1].y - v[0][0].y) + fy * (v[1][1].y - v[1][0].y);
-        const float dya = (1.f - fx) * (v[1][0].x - v[0][0].x) + fx * (v[1][1].x - v[0][1].x);
-        const float dyb = (1.f - fx) * (v[1][0].y - v[0][0].y) + fx * (v[1][1].y - v[0][1].y);
-        float ga = g.x * sx + g.y * sy;
-        float gx = g.x * dxa + g.y * dxb;
-        float gy = g.x * dya + g.y * dyb;
-        ga = group_sum<LPG>(ga);
-        gx = group_sum<LPG>(gx);
-        gy = group_sum<LPG>(gy);
+        float wc[4], ga, gx, gy;
+        msda_sample_grad<LPG>(v, fx, fy, g, wc, ga, gx, gy);
         const float a = pr.a[sp];
         dot += a * ga;
-        if (sub == sp) {  // d loc / d off = wh * offset_scale / P (straight through the bf16 rounding)
+        if (sub == sp) {
           my_ga = ga;
-          const float glx = a * gx * Wl, gly = a * gy * Hl;
-          my_goff = pack2bf(glx * pr.rw * offset_scale * invP, gly * pr.rh * offset_scale * invP);
+          my_goff = msda_fused_grad_off(a * gx * Wl, a * gy * Hl, pr, offset_scale, invP);
         }
-        const float wc[4] = {w00, w01, w10, w11};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const float s = a * wc[c];
-          bf16x2_t t;
-          t.x = (__bf16)(s * g.x);
-          t.y = (__bf16)(s * g.y);
-          pv[p][c] = *reinterpret_cast<uint32_t*>(&t);
+          pv[p][c] = msda_vgrad_pair(a * wc[c], g);
         }
       }
       if (l + 1 < LL) {  // next level's corner loads go out before this level's atomics
@@ -600,6 +606,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_lp_kernel(
               fxp = cur.fx[pp]; fyp = cur.fy[pp]; x0p = cur.x0[pp]; y0p = cur.y0[pp];
               ap = pr.a[l * PP + pp];
             }
+          // (the corner weight of msda_bilinear, for a run-time c)
           const float wcn = ((c & 1) ? fxp : 1.f - fxp) * ((c >> 1) ? fyp : 1.f - fyp);
           const int row = (cur.in & (1u << sub)) ? (y0p + (c >> 1)) * Wl + x0p + (c & 1) : -1;
           const int q = (gi / H) % Q;
@@ -615,9 +622,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_lp_kernel(
           for (int c = 0; c < 4; ++c) {
             if (!(cur.in & (1u << (4 * p + c)))) continue;
             const int xi = cur.x0[p] + (c & 1), yi = cur.y0[p] + (c >> 1);
-            bf16x2_t t = *reinterpret_cast<const bf16x2_t*>(&pv[p][c]);
-            __builtin_amdgcn_global_atomic_fadd_v2bf16(
-                (__attribute__((address_space(1))) bf16x2_t*)(grad_value + gofs + (size_t)(yi * Wl + xi) * ldv), t);
+            msda_vgrad_add(grad_value + gofs + (size_t)(yi * Wl + xi) * ldv, pv[p][c]);
           }
       }
     }
@@ -910,10 +915,33 @@ static int msda_check(int B, int S, int Q, int H, int D, int L, int P) {
   return 0;
 }
 
+// The argument checks of the fused (atomic) entry points: the shape, L * P
+// samples within a group's registers, and a value row stride that holds a row
+// and keeps the 4-B channel-pair accesses aligned.
+static int msda_fused_check(int B, int S, int Q, int H, int D, int L, int P, long long ldv) {
+  if (msda_check(B, S, Q, H, D, L, P)) return -1;
+  if (L * P > MSDA_LP_MAX) return fail("msda_fused: L * P must be <= 16");
+  if (ldv < (long long)H * D || ldv % 2 != 0) return fail("msda_fused: ldv must be >= H * D and even");
+  return 0;
+}
+
 static int msda_grid(long long groups, int lpg) {
   long long g = (groups * lpg + 255) / 256;
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
 }
+
+// The kernels are instantiated for the two head dims msda_check admits: calls
+// f with LPG = D / 2 (lanes per group) as a std::integral_constant.
+template <class F>
+static void msda_with_lpg(int D, F&& f) {
+  if (D == 32)
+    f(std::integral_constant<int, 16>{});
+  else
+    f(std::integral_constant<int, 32>{});
+}
+
+static const uint16_t* bf(const void* p) { return static_cast<const uint16_t*>(p); }
+static uint16_t* bf(void* p) { return static_cast<uint16_t*>(p); }
 
 extern "C" int rtdetr_msda_fwd(const void* value, const int32_t* shapes, const int32_t* starts,
                                const float* loc, const float* attn, int B, int S, int Q, int H, int D, int L,
@@ -921,17 +949,14 @@ extern "C" int rtdetr_msda_fwd(const void* value, const int32_t* shapes, const i
   if (msda_check(B, S, Q, H, D, L, P)) return -1;
   if (Q == 0) return 0;
   const long long groups = (long long)B * Q * H;
-  const uint16_t* v = static_cast<const uint16_t*>(value);
-  uint16_t* o = static_cast<uint16_t*>(out);
   // bytes: 4 bilinear corners of D bf16 per sample, loc+attn per sample, output rows
   const double samples = (double)groups * L * P;
   ProfScope prof(stream, PROF_MSDA, samples * (8.0 * D + 12.0) + 2.0 * groups * D);
-  if (D == 32)
-    MOE_LAUNCH(prof, msda_fwd_kernel<16>, dim3(msda_grid(groups, 16)), dim3(256), 0, stream, v, shapes, starts,
-                       loc, attn, B, S, Q, H, L, P, o);
-  else
-    MOE_LAUNCH(prof, msda_fwd_kernel<32>, dim3(msda_grid(groups, 32)), dim3(256), 0, stream, v, shapes, starts,
-                       loc, attn, B, S, Q, H, L, P, o);
+  msda_with_lpg(D, [&](auto lpg) {
+    constexpr int LPG = decltype(lpg)::value;
+    MOE_LAUNCH(prof, msda_fwd_kernel<LPG>, dim3(msda_grid(groups, LPG)), dim3(256), 0, stream, bf(value), shapes,
+               starts, loc, attn, B, S, Q, H, L, P, bf(out));
+  });
   return check_launch("rtdetr_msda_fwd");
 }
 
@@ -944,20 +969,15 @@ static int msda_bwd_impl(const void* value, const int32_t* shapes, const int32_t
   if (e != hipSuccess) return fail(std::string("rtdetr_msda_bwd: memset: ") + hipGetErrorString(e));
   if (Q == 0) return 0;
   const long long groups = (long long)B * Q * H;
-  const uint16_t* v = static_cast<const uint16_t*>(value);
-  const uint16_t* go = static_cast<const uint16_t*>(grad_out);
   // bytes: forward's gathers + 4 corner read-modify-writes of D per sample, grad_loc/attn, grad_out
   const double samples = (double)groups * L * P;
   ProfScope prof(stream, PROF_MSDA, samples * (8.0 * D + (gv16 ? 8.0 : 16.0) * D + 24.0) + 2.0 * groups * D);
-#define MSDA_BWD(LPG, G16)                                                                                 \
-  MOE_LAUNCH(prof, (msda_bwd_kernel<LPG, G16>), dim3(msda_grid(groups, LPG)), dim3(256), 0, stream, v, shapes, \
-             starts, loc, attn, go, B, S, Q, H, L, P, grad_value, grad_loc, grad_attn)
-  if (D == 32) {
-    if (gv16) MSDA_BWD(16, true); else MSDA_BWD(16, false);
-  } else {
-    if (gv16) MSDA_BWD(32, true); else MSDA_BWD(32, false);
-  }
-#undef MSDA_BWD
+  msda_with_lpg(D, [&](auto lpg) {
+    constexpr int LPG = decltype(lpg)::value;
+    const auto kern = gv16 ? msda_bwd_kernel<LPG, true> : msda_bwd_kernel<LPG, false>;
+    MOE_LAUNCH(prof, kern, dim3(msda_grid(groups, LPG)), dim3(256), 0, stream, bf(value), shapes, starts, loc, attn,
+               bf(grad_out), B, S, Q, H, L, P, grad_value, grad_loc, grad_attn);
+  });
   return check_launch("rtdetr_msda_bwd");
 }
 
@@ -986,30 +1006,24 @@ extern "C" int rtdetr_msda_fused_fwd_ld(const void* value, long long ldv, const 
                                         const int32_t* starts, const void* off, const float* ref, const void* logits,
                                         float offset_scale, int B, int S, int Q, int H, int D, int L, int P, void* out,
                                         hipStream_t stream) {
-  if (msda_check(B, S, Q, H, D, L, P)) return -1;
-  if (L * P > MSDA_LP_MAX) return fail("msda_fused: L * P must be <= 16");
-  if (ldv < (long long)H * D || ldv % 2 != 0) return fail("msda_fused: ldv must be >= H * D and even");
+  if (msda_fused_check(B, S, Q, H, D, L, P, ldv)) return -1;
   if (Q == 0) return 0;
   const long long groups = (long long)B * Q * H;
   const double samples = (double)groups * L * P;
   ProfScope prof(stream, PROF_MSDA, samples * (8.0 * D + 6.0) + groups * (2.0 * D + 16.0 / H));
-  const uint16_t* v = static_cast<const uint16_t*>(value);
-  const uint16_t* o = static_cast<const uint16_t*>(off);
-  const uint16_t* lg = static_cast<const uint16_t*>(logits);
-  uint16_t* y = static_cast<uint16_t*>(out);
+  const uint16_t *v = bf(value), *o = bf(off), *lg = bf(logits);
+  uint16_t* y = bf(out);
   const bool lp34 = L == 3 && P == 4 && !(g_msda_generic & 1);
-  if (D == 32 && lp34)
-    MOE_LAUNCH(prof, (msda_fused_fwd_lp_kernel<16, 3, 4>), dim3(msda_grid(groups, 16)), dim3(256), 0, stream, v,
-               shapes, starts, o, ref, lg, offset_scale, B, S, Q, H, ldv, y);
-  else if (D == 64 && lp34)
-    MOE_LAUNCH(prof, (msda_fused_fwd_lp_kernel<32, 3, 4>), dim3(msda_grid(groups, 32)), dim3(256), 0, stream, v,
-               shapes, starts, o, ref, lg, offset_scale, B, S, Q, H, ldv, y);
-  else if (D == 32)
-    MOE_LAUNCH(prof, msda_fused_fwd_kernel<16>, dim3(msda_grid(groups, 16)), dim3(256), 0, stream, v, shapes, starts,
-               o, ref, lg, offset_scale, B, S, Q, H, L, P, ldv, y);
-  else
-    MOE_LAUNCH(prof, msda_fused_fwd_kernel<32>, dim3(msda_grid(groups, 32)), dim3(256), 0, stream, v, shapes, starts,
-               o, ref, lg, offset_scale, B, S, Q, H, L, P, ldv, y);
+  msda_with_lpg(D, [&](auto lpg) {
+    constexpr int LPG = decltype(lpg)::value;
+    const dim3 grid(msda_grid(groups, LPG));
+    if (lp34)
+      MOE_LAUNCH(prof, (msda_fused_fwd_lp_kernel<LPG, 3, 4>), grid, dim3(256), 0, stream, v, shapes, starts, o, ref,
+                 lg, offset_scale, B, S, Q, H, ldv, y);
+    else
+      MOE_LAUNCH(prof, msda_fused_fwd_kernel<LPG>, grid, dim3(256), 0, stream, v, shapes, starts, o, ref, lg,
+                 offset_scale, B, S, Q, H, L, P, ldv, y);
+  });
   return check_launch("rtdetr_msda_fused_fwd");
 }
 
@@ -1018,9 +1032,7 @@ extern "C" int rtdetr_msda_fused_bwd_ld(const void* value, long long ldv, const 
                                         float offset_scale, const void* grad_out, int B, int S, int Q, int H, int D,
                                         int L, int P, void* grad_value, int zero_grad_value, void* grad_off,
                                         void* grad_logits, hipStream_t stream) {
-  if (msda_check(B, S, Q, H, D, L, P)) return -1;
-  if (L * P > MSDA_LP_MAX) return fail("msda_fused: L * P must be <= 16");
-  if (ldv < (long long)H * D || ldv % 2 != 0) return fail("msda_fused: ldv must be >= H * D and even");
+  if (msda_fused_check(B, S, Q, H, D, L, P, ldv)) return -1;
   if (zero_grad_value) {
     if (ldv != (long long)H * D) return fail("msda_fused: zero_grad_value needs a dense grad_value (ldv == H * D)");
     const hipError_t e = hipMemsetAsync(grad_value, 0, (size_t)B * S * H * D * 2, stream);
@@ -1030,26 +1042,19 @@ extern "C" int rtdetr_msda_fused_bwd_ld(const void* value, long long ldv, const 
   const long long groups = (long long)B * Q * H;
   const double samples = (double)groups * L * P;
   ProfScope prof(stream, PROF_MSDA, samples * (16.0 * D + 10.0) + groups * (2.0 * D + 16.0 / H));
-  const uint16_t* v = static_cast<const uint16_t*>(value);
-  const uint16_t* o = static_cast<const uint16_t*>(off);
-  const uint16_t* lg = static_cast<const uint16_t*>(logits);
-  const uint16_t* go = static_cast<const uint16_t*>(grad_out);
-  uint16_t* gv = static_cast<uint16_t*>(grad_value);
-  uint16_t* gof = static_cast<uint16_t*>(grad_off);
-  uint16_t* glg = static_cast<uint16_t*>(grad_logits);
+  const uint16_t *v = bf(value), *o = bf(off), *lg = bf(logits), *go = bf(grad_out);
+  uint16_t *gv = bf(grad_value), *gof = bf(grad_off), *glg = bf(grad_logits);
   const bool lp34 = L == 3 && P == 4 && !(g_msda_generic & 2);
-  if (D == 32 && lp34)
-    MOE_LAUNCH(prof, (msda_fused_bwd_lp_kernel<16, 3, 4>), dim3(msda_grid(groups, 16)), dim3(256), 0, stream, v,
-               shapes, starts, o, ref, lg, offset_scale, go, B, S, Q, H, ldv, gv, gof, glg, static_cast<int2*>(nullptr));
-  else if (D == 64 && lp34)
-    MOE_LAUNCH(prof, (msda_fused_bwd_lp_kernel<32, 3, 4>), dim3(msda_grid(groups, 32)), dim3(256), 0, stream, v,
-               shapes, starts, o, ref, lg, offset_scale, go, B, S, Q, H, ldv, gv, gof, glg, static_cast<int2*>(nullptr));
-  else if (D == 32)
-    MOE_LAUNCH(prof, msda_fused_bwd_kernel<16>, dim3(msda_grid(groups, 16)), dim3(256), 0, stream, v, shapes, starts,
-               o, ref, lg, offset_scale, go, B, S, Q, H, L, P, ldv, gv, gof, glg);
-  else
-    MOE_LAUNCH(prof, msda_fused_bwd_kernel<32>, dim3(msda_grid(groups, 32)), dim3(256), 0, stream, v, shapes, starts,
-               o, ref, lg, offset_scale, go, B, S, Q, H, L, P, ldv, gv, gof, glg);
+  msda_with_lpg(D, [&](auto lpg) {
+    constexpr int LPG = decltype(lpg)::value;
+    const dim3 grid(msda_grid(groups, LPG));
+    if (lp34)
+      MOE_LAUNCH(prof, (msda_fused_bwd_lp_kernel<LPG, 3, 4>), grid, dim3(256), 0, stream, v, shapes, starts, o, ref,
+                 lg, offset_scale, go, B, S, Q, H, ldv, gv, gof, glg, static_cast<int2*>(nullptr));
+    else
+      MOE_LAUNCH(prof, msda_fused_bwd_kernel<LPG>, grid, dim3(256), 0, stream, v, shapes, starts, o, ref, lg,
+                 offset_scale, go, B, S, Q, H, L, P, ldv, gv, gof, glg);
+  });
   return check_launch("rtdetr_msda_fused_bwd");
 }
 
@@ -1121,22 +1126,17 @@ extern "C" int rtdetr_msda_fused_bwd_det(const void* value, long long ldv, const
   int4* sorted = reinterpret_cast<int4*>(static_cast<char*>(work) + n_all * 8);
   int32_t* toff = reinterpret_cast<int32_t*>(static_cast<char*>(work) + n_all * 24);
   const long long groups = (long long)B * Q * H;
-  const uint16_t* v = static_cast<const uint16_t*>(value);
-  const uint16_t* o = static_cast<const uint16_t*>(off);
-  const uint16_t* lg = static_cast<const uint16_t*>(logits);
-  const uint16_t* go = static_cast<const uint16_t*>(grad_out);
-  uint16_t* gv = static_cast<uint16_t*>(grad_value);
+  const uint16_t* go = bf(grad_out);
+  uint16_t* gv = bf(grad_value);
   {
     const double samples = (double)groups * L * P;
     ProfScope prof(stream, PROF_MSDA, samples * (8.0 * D + 32.0 + 10.0) + groups * (2.0 * D + 16.0 / H));
-    if (D == 32)
-      MOE_LAUNCH(prof, (msda_fused_bwd_lp_kernel<16, 3, 4, true>), dim3(msda_grid(groups, 16)), dim3(256), 0, stream,
-                 v, shapes, starts, o, ref, lg, offset_scale, go, B, S, Q, H, ldv, gv,
-                 static_cast<uint16_t*>(grad_off), static_cast<uint16_t*>(grad_logits), rec);
-    else
-      MOE_LAUNCH(prof, (msda_fused_bwd_lp_kernel<32, 3, 4, true>), dim3(msda_grid(groups, 32)), dim3(256), 0, stream,
-                 v, shapes, starts, o, ref, lg, offset_scale, go, B, S, Q, H, ldv, gv,
-                 static_cast<uint16_t*>(grad_off), static_cast<uint16_t*>(grad_logits), rec);
+    msda_with_lpg(D, [&](auto lpg) {
+      constexpr int LPG = decltype(lpg)::value;
+      MOE_LAUNCH(prof, (msda_fused_bwd_lp_kernel<LPG, 3, 4, true>), dim3(msda_grid(groups, LPG)), dim3(256), 0,
+                 stream, bf(value), shapes, starts, bf(off), ref, bf(logits), offset_scale, go, B, S, Q, H, ldv, gv,
+                 bf(grad_off), bf(grad_logits), rec);
+    });
     if (int rc = check_launch("rtdetr_msda_fused_bwd_det (samples)")) return rc;
   }
   {
@@ -1155,20 +1155,16 @@ extern "C" int rtdetr_msda_fused_bwd_det(const void* value, long long ldv, const
   double rows = 0;
   for (int l = 0; l < L; ++l) rows += hw_host[l];
   ProfScope prof(stream, PROF_MSDA, (double)n_all * (16.0 + 2.0 * D) + rows * B * H * D * 2.0);
-  if (D == 32) {
-    static unsigned long long a32 = 0;  // per-device bitmask
-    if (int rc = allow_dyn_lds(reinterpret_cast<const void*>(msda_vgrad_tile_kernel<32>), (int)lds, &a32,
-                               "msda_fused_bwd_det: LDS attribute"))
-      return rc;
-    MOE_LAUNCH(prof, msda_vgrad_tile_kernel<32>, dim3(B * H * tiles_bh), dim3(256), lds, stream, sorted, toff, lv, go,
+  int rc = 0;
+  msda_with_lpg(D, [&](auto lpg) {
+    constexpr int DD = 2 * decltype(lpg)::value;
+    static unsigned long long allowed = 0;  // per-device bitmask (one per instantiation)
+    rc = allow_dyn_lds(reinterpret_cast<const void*>(msda_vgrad_tile_kernel<DD>), (int)lds, &allowed,
+                       "msda_fused_bwd_det: LDS attribute");
+    if (rc) return;
+    MOE_LAUNCH(prof, msda_vgrad_tile_kernel<DD>, dim3(B * H * tiles_bh), dim3(256), lds, stream, sorted, toff, lv, go,
                S, Q, H, L, P, tiles_bh, ldv, gv);
-  } else {
-    static unsigned long long a64 = 0;  // per-device bitmask
-    if (int rc = allow_dyn_lds(reinterpret_cast<const void*>(msda_vgrad_tile_kernel<64>), (int)lds, &a64,
-                               "msda_fused_bwd_det: LDS attribute"))
-      return rc;
-    MOE_LAUNCH(prof, msda_vgrad_tile_kernel<64>, dim3(B * H * tiles_bh), dim3(256), lds, stream, sorted, toff, lv, go,
-               S, Q, H, L, P, tiles_bh, ldv, gv);
-  }
+  });
+  if (rc) return rc;
   return check_launch("rtdetr_msda_fused_bwd_det");
 }

@@ -75,18 +75,25 @@ def test_msda_bwd_bf16_atomics_vs_fp32(hip_lib):
     assert rel < 4e-3, rel
 
 
-def test_msda_fused_prep_matches_unfused(hip_lib):
+@pytest.mark.parametrize("B,Q,H,D,P,shapes", [
+    (4, 300, 8, 32, 4, [(92, 160), (46, 80), (23, 40)]),     # C2 decoder: the level-batched 3 x 4 kernels
+    (1, 3, 2, 32, 4, [(10, 12), (8, 8), (7, 7), (6, 8)]),    # L P = 16: every lane of a group writes a logit
+    #                                                          gradient; 6 groups leave lanes without work
+    (2, 5, 4, 64, 2, [(12, 10), (6, 5)]),                    # D 64 generic fused kernels
+    (1, 3, 2, 32, 1, [(7, 7)]),                              # one sample per group
+])
+def test_msda_fused_prep_matches_unfused(hip_lib, B, Q, H, D, P, shapes):
     """rtdetr_msda_fused_fwd/bwd (locations + softmax formed in the kernel)
-    against the unfused decoder formulation (torch prep + rtdetr_msda_*) on the
-    C2 decoder shapes: output and the gradients of value, sampling offsets and
-    attention logits."""
+    against the unfused decoder formulation (torch prep + rtdetr_msda_*):
+    output and the gradients of value, sampling offsets and attention logits,
+    on the C2 decoder shapes and on small shapes that take the generic fused
+    kernels (L P = 16, D 64, one sample per group)."""
     import torch.nn.functional as F
 
     from src.rtdetr_moe.decoder import _MSDAFusedHip, _level_tensors, deformable_attention
 
     g = torch.Generator().manual_seed(2)
-    shapes = [(92, 160), (46, 80), (23, 40)]
-    B, Q, H, D, L, P = 4, 300, 8, 32, 3, 4
+    L = len(shapes)
     S = sum(h * w for h, w in shapes)
     dev = "cuda"
     value = torch.randn(B, S, H, D, generator=g).to(torch.bfloat16).to(dev)
