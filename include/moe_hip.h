@@ -969,6 +969,21 @@ int train_adamw_ema_step(const void* tensors, const int32_t* chunks, int n_chunk
 int train_ema_update(const void* tensors, const int32_t* chunks, int n_chunks, float* ema, float ema_decay,
                      hipStream_t stream);
 
+/* Gradient accumulation over micro-steps (reference: Ultralytics' trainer
+ * accumulates nbs / batch batches per optimizer step).  The step graph
+ * overwrites its gradient buffers on every replay, so the sum is kept in
+ * `acc`: a flat fp32 buffer laid out like `master` (same records, same
+ * flat_offset, 16-B aligned).  Per element e of record t:
+ *   acc[t.flat_offset + e] = (first ? 0 : acc[t.flat_offset + e]) + float(grad[e])
+ * A record with grad_dtype 2 (no gradient this micro-step) is written as zeros
+ * when `first` is set and not touched otherwise.  One thread owns each element
+ * and the sums happen in call order, so the result is bit-equal to
+ * acc = g1.float(); acc += g2.float(); ...  The optimizer entry points above
+ * then read acc as fp32 gradients (grad_dtype 1) with inv_world = 1 / (world *
+ * micro-steps).  n_chunks == 0 returns 0 without a launch. */
+int train_grad_accum(const void* tensors, const int32_t* chunks, int n_chunks, float* acc, int first,
+                     hipStream_t stream);
+
 /* Training batch augmentation (reference: the defaults of Ultralytics'
  * RTDETR.train -- random_perspective with scale / translate only, fliplr,
  * HSV jitter -- src/models/vision/rtdetr.py:82-94; semantics restated in

@@ -23,6 +23,11 @@
 //   train_ema_update        the same blend from any bf16 / fp32 source: the
 //                           floating-point buffers (BatchNorm statistics), and
 //                           the unfused A/B path over the masters
+//
+// Gradient accumulation (TrainStep accumulate > 1): a fifth flat fp32 buffer,
+// the sum of the micro-steps' gradients, which the three launches above then
+// read as fp32 gradients.
+//   train_grad_accum        acc = (first ? 0 : acc) + grad, one launch per micro-step
 #include "moe_common.h"
 #include "prof.h"
 
@@ -94,6 +99,44 @@ __global__ __launch_bounds__(256) void grad_pack_kernel(const OptTensor* __restr
 #pragma unroll
     for (int i = 0; i < 8; ++i)
       if (e + i < t.numel) dst[i] = g[i];
+  }
+}
+
+// Gradient accumulation over micro-steps (train_grad_accum): the step graph
+// overwrites its static gradient buffers on every replay, so the running sum
+// lives in a flat fp32 buffer laid out like the masters.  One thread owns each
+// element (no atomics, no LDS) and the sums happen in micro-step order:
+// bit-equal to acc = g1.float(); acc += g2.float(); ...  FIRST starts a cycle
+// (the old contents are not read; a tensor without a gradient becomes zeros);
+// otherwise a tensor without a gradient is left as it is.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void grad_accum_kernel(const OptTensor* __restrict__ tens,
+                                                         const int2* __restrict__ chunks, float* __restrict__ acc) {
+  const int2 ch = chunks[blockIdx.x];
+  const OptTensor t = tens[ch.x];
+  const long long e = (long long)ch.y * OPT_CHUNK + threadIdx.x * 8;
+  if (e >= t.numel) return;
+  if (!FIRST && t.gdtype == 2) return;
+  const bool full = e + 8 <= t.numel;
+  float g[8];
+  if (t.gdtype == 2) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g[i] = 0.f;
+  } else {
+    load_grad8(t, e, full, g);
+  }
+  float* dst = acc + t.moff + e;
+  if (full) {
+    if (!FIRST) {
+      const float4 a = reinterpret_cast<const float4*>(dst)[0], b = reinterpret_cast<const float4*>(dst)[1];
+      g[0] += a.x; g[1] += a.y; g[2] += a.z; g[3] += a.w; g[4] += b.x; g[5] += b.y; g[6] += b.z; g[7] += b.w;
+    }
+    reinterpret_cast<float4*>(dst)[0] = make_float4(g[0], g[1], g[2], g[3]);
+    reinterpret_cast<float4*>(dst)[1] = make_float4(g[4], g[5], g[6], g[7]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (e + i < t.numel) dst[i] = FIRST ? g[i] : dst[i] + g[i];
   }
 }
 
@@ -325,6 +368,24 @@ extern "C" int train_grad_pack(const void* tensors, const int32_t* chunks, int n
   MOE_LAUNCH(prof, grad_pack_kernel, dim3(n_chunks), dim3(256), 0, stream, static_cast<const OptTensor*>(tensors),
              reinterpret_cast<const int2*>(chunks), flat);
   return check_launch("train_grad_pack");
+}
+
+extern "C" int train_grad_accum(const void* tensors, const int32_t* chunks, int n_chunks, float* acc, int first,
+                                hipStream_t stream) {
+  if (n_chunks < 0 || (n_chunks > 0 && (tensors == nullptr || chunks == nullptr || acc == nullptr)))
+    return fail("train_grad_accum: bad arguments");
+  if (reinterpret_cast<uintptr_t>(acc) % 16) return fail("train_grad_accum: accumulator must be 16-B aligned");
+  if (n_chunks == 0) return 0;
+  // bytes per element: gradient read (<= 4) + accumulator written (4) [+ accumulator read (4) when adding]
+  ProfScope prof(stream, PROF_OPTIM, (first ? 8.0 : 12.0) * OPT_CHUNK * n_chunks);
+  if (first) {
+    MOE_LAUNCH(prof, grad_accum_kernel<true>, dim3(n_chunks), dim3(256), 0, stream,
+               static_cast<const OptTensor*>(tensors), reinterpret_cast<const int2*>(chunks), acc);
+  } else {
+    MOE_LAUNCH(prof, grad_accum_kernel<false>, dim3(n_chunks), dim3(256), 0, stream,
+               static_cast<const OptTensor*>(tensors), reinterpret_cast<const int2*>(chunks), acc);
+  }
+  return check_launch("train_grad_accum");
 }
 
 extern "C" int train_grad_norm_finalize(const float* partials, int n, float max_norm, float inv_world, float* coef,

@@ -8,6 +8,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py [--reps 50] [--rounds 5] [--variants 1,2] [--stages 3,4]
   python multimodal-moe_amd/kbench.py --augment     the batch-augmentation kernels at C2's batch
   python multimodal-moe_amd/kbench.py --eval-match  the validation matcher against the host loop
+  python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
 
@@ -319,8 +320,49 @@ def eval_match_leg(reps, rounds):
         print(json.dumps(out), flush=True)
 
 
+def grad_accum_leg(reps, rounds):
+    """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
+    convolution operands in bf16 as in the training step): us per launch
+    (dispatch-stamped kernel time) and GB/s of the bytes it must move -- the
+    gradient read, the accumulator written, and in add mode the accumulator
+    read -- in ``first`` and add mode, interleaved in each round.  With --cold
+    every launch starts from HBM, as after a step's forward and backward."""
+    from src.rtdetr_moe.model import RTDETRMoE
+    from src.rtdetr_moe.optim import GradAccumulator
+    from src.rtdetr_moe.step import gemm_params
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last)
+    for p in gemm_params(model):
+        p.data = p.data.to(torch.bfloat16)
+    params = [p for p in model.parameters() if p.requires_grad]
+    grads = [torch.randn_like(p) for p in params]
+    acc = GradAccumulator(params)
+    n = sum(p.numel() for p in params)
+    gbytes = sum(g.numel() * g.element_size() for g in grads)
+    byts = {"first": gbytes + 4 * n, "add": gbytes + 8 * n}
+
+    def launch(first):
+        acc.count = 0 if first else 1
+        acc.add(grads)
+
+    res = {"first": [], "add": []}
+    for _ in range(rounds):
+        for mode in res:
+            res[mode].append(timed(lambda: launch(mode == "first"), reps))
+    for mode, v in res.items():
+        us = statistics.median(v)
+        print(json.dumps({"kernel": "train_grad_accum", "mode": mode, "shape": f"C2 {len(params)} tensors {n} elements "
+                          f"{acc.n_chunks} chunks", "cold": _FLUSH is not None, "us": round(us, 2),
+                          "us_min": round(min(v), 2), "us_max": round(max(v), 2), "MB": round(byts[mode] / 1e6, 1),
+                          "GBs": round(byts[mode] / us / 1e3, 1),
+                          "hbm_peak_share": round(byts[mode] / us / 1e3 / L.PEAK_HBM_GBS, 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grad-accum", action="store_true",
+                    help="time the gradient-accumulation kernel over C2's parameter list (first / add mode) and exit")
     ap.add_argument("--augment", action="store_true", help="time the batch-augmentation kernels (C2's batch) and exit")
     ap.add_argument("--eval-match", action="store_true",
                     help="time the validation matcher (B 16, K 300, M 20 / 64) against the host loop and exit")
@@ -352,12 +394,15 @@ def main():
     if a.eval_match:
         eval_match_leg(a.reps, a.rounds)
         return
-    for kv in a.tune:
-        key, val = kv.split("=", 1)
-        L.set_tuning(key, int(val))
     if a.cold:
         global _FLUSH
         _FLUSH = torch.zeros(128 << 20, device="cuda", dtype=torch.float32)
+    if a.grad_accum:
+        grad_accum_leg(a.reps, a.rounds)
+        return
+    for kv in a.tune:
+        key, val = kv.split("=", 1)
+        L.set_tuning(key, int(val))
     configs = [(v, s, dbg, bm, xm, ks, pr, wg) for v in map(int, a.variants.split(",")) for s in map(int, a.stages.split(","))
                for dbg in map(int, a.debug.split(",")) for bm in map(int, a.bm.split(","))
                for xm in map(int, a.xcd.split(",")) for ks in map(int, a.ksplit.split(","))

@@ -25,6 +25,14 @@ local architecture spec (no network fetch), e.g.::
                                   frame (Ultralytics' mosaic=1.0).  -mosaic<p> sets the probability per
                                   image (-mosaic0.5), p in [0, 1]; the token implies -aug; the engine
                                   turns it off for the last TrainArgs.close_mosaic epochs; default: none
+    rtdetr-r50-moe8-top2-nbs64    C2 trained at a nominal batch size of 64: the optimizer steps on the mean
+                                  gradient of round(64 / (batch x world)) micro-batches (TrainStep accumulate;
+                                  Ultralytics' nbs).  Default 0 = a step on every batch
+    rtdetr-r50-moe8-top2-warm-lrf0.01-cos   learning-rate schedule (src/rtdetr_moe/schedule.py, Ultralytics'):
+                                  -warm[<E>] ramps the rate from 0 (and the accumulation count from 1) over
+                                  the first E epochs, bare = 3, at least 100 iterations; -lrf<f> decays the
+                                  rate linearly to f x lr over the run, f in (0, 1]; -cos makes the decay
+                                  half a cosine.  Default: constant rate, no warm-up
 """
 from __future__ import annotations
 
@@ -97,6 +105,10 @@ class ModelSpec:
     ema_tau: float = 2000.0        # EMA warm-up: d_t = ema_decay (1 - exp(-t / ema_tau)) (-ematau<N>)
     augment: bool = False          # GPU batch augmentation in training (-aug; rtdetr_moe/augment.py)
     mosaic: float = 0.0            # mosaic probability per image (-mosaic = 1.0, -mosaic<p>; implies augment)
+    nbs: int = 0                   # nominal batch size: accumulate round(nbs / (batch world)) micro-batches (-nbs<N>; 0 = off)
+    warmup_epochs: float = 0.0     # LR / accumulation warm-up in epochs, at least 100 iterations (-warm = 3, -warm<E>; 0 = off)
+    lrf: float = 1.0               # final learning-rate factor of the decay, in (0, 1] (-lrf<f>; 1 = constant)
+    cos_lr: bool = False           # cosine instead of linear decay (-cos)
     raw: str = ""
 
 
@@ -104,9 +116,10 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]]``
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]][-nbs<N>][-warm[<E>]][-lrf<f>][-cos]``
     (``-aug``: training batch augmentation, no value; ``-mosaic[<p>]``: four-image mosaic with
-    probability p, default 1.0, implies ``-aug``)."""
+    probability p, default 1.0, implies ``-aug``; ``-nbs<N>``: nominal batch size for gradient
+    accumulation; ``-warm[<E>]`` / ``-lrf<f>`` / ``-cos``: the learning-rate schedule)."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
         raise ValueError(f"{spec!r} is a weights file, not an architecture spec")
@@ -128,6 +141,29 @@ def parse_moe_spec(spec: str) -> ModelSpec:
             if not 0.0 <= out.mosaic <= 1.0:
                 raise ValueError(f"mosaic probability outside [0, 1] in model spec {spec!r}")
             out.augment = True
+        elif tok == "cos":  # exact, ahead of every prefix match
+            out.cos_lr = True
+        elif tok.startswith("nbs"):
+            try:
+                out.nbs = int(tok[3:])
+            except ValueError:
+                raise ValueError(f"bad nominal batch size {tok[3:]!r} in model spec {spec!r}") from None
+            if out.nbs < 0:
+                raise ValueError(f"negative nominal batch size in model spec {spec!r}")
+        elif tok.startswith("warm"):
+            try:
+                out.warmup_epochs = float(tok[4:]) if tok[4:] else 3.0
+            except ValueError:
+                raise ValueError(f"bad warm-up length {tok[4:]!r} in model spec {spec!r}") from None
+            if not out.warmup_epochs >= 0.0:
+                raise ValueError(f"negative warm-up length in model spec {spec!r}")
+        elif tok.startswith("lrf"):
+            try:
+                out.lrf = float(tok[3:])
+            except ValueError:
+                raise ValueError(f"bad final learning-rate factor {tok[3:]!r} in model spec {spec!r}") from None
+            if not 0.0 < out.lrf <= 1.0:
+                raise ValueError(f"final learning-rate factor outside (0, 1] in model spec {spec!r}")
         elif tok.startswith("moe"):
             moe = moe or MoEConfig()
             moe.num_experts = int(tok[3:])

@@ -33,6 +33,7 @@ from .criterion import SetCriterion
 from .data import CocoDataset, SyntheticZOD, YoloDataset, collate
 from .metrics import BoxMetrics, DetectionEvaluator, DeviceDetectionEvaluator, gt_xyxy_pixels
 from .model import RTDETRMoE
+from .schedule import accumulate_count, schedule_at, warmup_iters
 
 
 # ---------------------------------------------------------------------------
@@ -247,6 +248,22 @@ def _batches(data, split, imgsz, batch, workers, seed, rank, world, epoch, drop_
     yield from dl
 
 
+def _num_batches(data, split, imgsz, batch, world, drop_last=False) -> int:
+    """How many batches ``_batches`` yields per epoch on one rank (the
+    schedule's warm-up length is a number of iterations)."""
+    if _is_synthetic(data):
+        return _synthetic_steps(data)
+    h, w = _hw(imgsz)
+    if isinstance(data, dict):
+        n = len(CocoDataset(data[split]["img_folder"], data[split]["ann_file"], imgsz=(h, w)))
+    else:
+        n = len(YoloDataset(data, split=split, imgsz=(h, w)))
+    drop = drop_last and n >= batch * world
+    if world > 1:  # DistributedSampler pads every rank to the same length
+        n = math.ceil(n / world)
+    return n // batch if drop else math.ceil(n / batch)
+
+
 # ---------------------------------------------------------------------------
 # training
 # ---------------------------------------------------------------------------
@@ -273,6 +290,11 @@ class TrainArgs:
     augment: bool | None = None  # GPU batch augmentation (augment.BatchAugment); None: the model spec's -aug token
     mosaic: float | None = None  # mosaic probability per image (implies augment); None: the spec's -mosaic token
     close_mosaic: int = 10       # the last close_mosaic epochs run without mosaic (Ultralytics' close_mosaic)
+    # gradient accumulation and the learning-rate schedule (schedule.py); None: the model spec's token
+    nbs: int | None = None              # nominal batch size (-nbs<N>): round(nbs / (batch world)) batches per step
+    warmup_epochs: float | None = None  # LR / accumulation warm-up (-warm[<E>]); 0 = off
+    lrf: float | None = None            # final LR factor of the decay (-lrf<f>); 1 = constant
+    cos_lr: bool | None = None          # cosine decay (-cos)
 
 
 def _seed_all(seed: int):
@@ -317,7 +339,14 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
     in the loader's layout (the kernel reads through strides).
     With mosaic (a -mosaic spec token or ``mosaic``) the probability is set to
     0 from epoch ``epochs - close_mosaic`` on: the augmenter then draws
-    degenerate rows for the same kernels, so nothing is re-captured."""
+    degenerate rows for the same kernels, so nothing is re-captured.
+    With a nominal batch size or a learning-rate schedule (-nbs / -warm / -lrf /
+    -cos spec tokens or the TrainArgs of the same names; schedule.py) the loop
+    counts micro-batches and sets the step's learning-rate factor and
+    accumulation count before every call; accumulation cycles carry across
+    epoch boundaries (no flush), so validation sees the weights of the last
+    completed optimizer step, and results.csv gains the columns lr/pg0, lr/pg1,
+    train/accumulate and train/opt_steps."""
     from .step import TrainStep
 
     on_gpu = local != "cpu"
@@ -347,6 +376,19 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
     mosaic = float(getattr(getattr(core, "spec", None), "mosaic", 0.0) if a.mosaic is None else a.mosaic)
     augment = (bool(getattr(getattr(core, "spec", None), "augment", False)) or mosaic > 0) if a.augment is None \
         else bool(a.augment)
+    # gradient accumulation and the learning-rate schedule (schedule.py): off unless a token / argument asks
+    spec = getattr(core, "spec", None)
+    nbs = int(getattr(spec, "nbs", 0) if a.nbs is None else a.nbs)
+    warmup_epochs = float(getattr(spec, "warmup_epochs", 0.0) if a.warmup_epochs is None else a.warmup_epochs)
+    lrf = float(getattr(spec, "lrf", 1.0) if a.lrf is None else a.lrf)
+    cos_lr = bool(getattr(spec, "cos_lr", False) if a.cos_lr is None else a.cos_lr)
+    if nbs < 0 or warmup_epochs < 0 or not 0.0 < lrf <= 1.0:
+        raise ValueError(f"nbs {nbs} / warmup_epochs {warmup_epochs} must be >= 0 and lrf {lrf} in (0, 1]")
+    scheduled = nbs > 0 or warmup_epochs > 0 or lrf != 1.0 or cos_lr
+    nw = -1
+    if warmup_epochs > 0:
+        nw = warmup_iters(warmup_epochs, _num_batches(a.data, "train", a.imgsz, a.batch, world, drop_last=on_gpu))
+    ni = 0  # micro-batches since the start of the run
     csv_rows = []
     epoch = 0
     step = None
@@ -376,8 +418,14 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
                                  precision="bf16" if on_gpu else "fp32",
                                  ddp_local=None, targets=tg if on_gpu else None,
                                  num_boxes=float(num_boxes), seed=a.seed, ema_decay=a.ema_decay,
-                                 ema_tau=a.ema_tau, augment=augment, content_hw=_hw(a.imgsz), mosaic=mosaic)
+                                 ema_tau=a.ema_tau, augment=augment, content_hw=_hw(a.imgsz), mosaic=mosaic,
+                                 accumulate=accumulate_count(nbs, a.batch, world))
                 shape = tuple(images.shape)
+            if scheduled:
+                f, step.accumulate = schedule_at(ni, epoch, nw=nw, epochs=a.epochs, lrf=lrf, cos=cos_lr, nbs=nbs,
+                                                 batch=a.batch, world=world)
+                step.set_lr_scale([f, f])
+            ni += 1
             if mosaic > 0 and step.aug is not None:
                 step.aug.mosaic = 0.0 if epoch >= a.epochs - a.close_mosaic else mosaic
             if on_gpu and tuple(images.shape) != shape:
@@ -416,6 +464,10 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
                 save_checkpoint(wdir / "best.pt", core, epoch, fit, state_dict=sd, ema=ema_info)
             row = {"epoch": epoch + 1, "train/loss": float(tot) / max(n, 1), "time_s": time.perf_counter() - t_ep,
                    **_results_dict(metrics)}
+            if scheduled:  # the values of the epoch's last micro-batch
+                pg = step.lrs()
+                row.update({"lr/pg0": pg[0], "lr/pg1": pg[1], "train/accumulate": step.accumulate,
+                            "train/opt_steps": step.opt_steps})
             row.update(_moe_stats(core))
             csv_rows.append(row)
         stop = torch.tensor([0.0], device=device)

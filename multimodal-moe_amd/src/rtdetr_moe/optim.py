@@ -21,6 +21,10 @@ ModelEMA, src/rtdetr_moe/ema.py): a fourth flat fp32 buffer laid out like the
 masters, blended inside the AdamW launch (``train_adamw_ema_step``) when
 ``step`` is given the step's decay.  ``MOE_EMA_FUSED=0`` is the A/B switch:
 the plain AdamW launch followed by ``train_ema_update`` over the masters.
+
+Gradient accumulation (``GradAccumulator``): a flat fp32 sum of the
+micro-steps' gradients, one ``train_grad_accum`` launch per micro-step, which
+the optimizers read as fp32 gradients and average through ``inv_world``.
 """
 from __future__ import annotations
 
@@ -49,6 +53,25 @@ def _storage_flat(t: torch.Tensor) -> torch.Tensor:
             raise ValueError(f"FlatAdamW: tensor with strides {t.stride()} is not dense")
         expect *= t.size(i)
     return t.as_strided((t.numel(),), (1,))
+
+
+def _grad_source(who, staged, i, p, g):
+    """The tensor a kernel reads the gradient ``g`` of parameter ``p`` (index
+    ``i``) from: ``g`` itself when it has the parameter's strides and a 16-B
+    aligned address, else a copy staged in the parameter's layout (kept in
+    ``staged[i]``).  None (no gradient: gdtype 2) stays None.  The gradient has
+    the parameter's shape and its dtype or fp32 (a reduced or accumulated sum)."""
+    if g is None:
+        return None
+    if g.shape != p.shape or g.dtype not in (p.dtype, torch.float32):
+        raise ValueError(f"{who}: gradient must have the parameter's shape and dtype (or fp32)")
+    if g.stride() != p.stride() or g.data_ptr() % 16:
+        buf = staged.get(i)
+        if buf is None or buf.dtype != g.dtype:
+            buf = staged[i] = torch.empty_strided(p.shape, p.stride(), dtype=g.dtype, device=p.device)
+        buf.copy_(g)
+        return buf
+    return g
 
 
 def _ema_fused() -> bool:
@@ -160,18 +183,8 @@ class FlatAdamW:
                                            self.device)
 
     # -- gradient table ---------------------------------------------------
-    def _grad_source(self, i, p, g):
-        if g is None:  # skipped this step (torch.optim semantics): gdtype 2
-            return None
-        if g.shape != p.shape or g.dtype not in (p.dtype, torch.float32):
-            raise ValueError("FlatAdamW: gradient must have the parameter's shape and dtype (or fp32)")
-        if g.stride() != p.stride() or g.data_ptr() % 16:  # stage in the parameter's layout, 16-B aligned
-            buf = self._staged.get(i)
-            if buf is None or buf.dtype != g.dtype:
-                buf = self._staged[i] = torch.empty_strided(p.shape, p.stride(), dtype=g.dtype, device=p.device)
-            buf.copy_(g)
-            return buf
-        return g
+    def _grad_source(self, i, p, g):  # None: skipped this step (torch.optim semantics), gdtype 2
+        return _grad_source("FlatAdamW", self._staged, i, p, g)
 
     def _build_table(self, srcs):
         rec = np.zeros(len(self.params), dtype=_REC)
@@ -268,12 +281,84 @@ class FlatAdamW:
                     _storage_flat(p).copy_(self.master[o:o + p.numel()])
 
 
+class GradAccumulator:
+    """Sum of the gradients of several micro-steps in fp32 (TrainStep
+    ``accumulate`` > 1; Ultralytics accumulates nbs / batch batches per
+    optimizer step).  The step graph overwrites its static gradient buffers
+    (bf16 for GEMM / convolution operands) on every replay, so autograd's
+    ``+=`` cannot do it: ``add`` is ONE ``train_grad_accum`` launch after each
+    micro-step into a flat fp32 buffer laid out like FlatAdamW's masters
+    (segments start at multiples of 8 elements), reading the gradients where
+    they are through a record table rebuilt only when an address changes (a
+    re-capture rebinds ``p.grad``).  The sums happen in micro-step order, one
+    thread per element: bit-equal to ``acc = g1.float(); acc += g2.float()``.
+    ``take`` hands the optimizer fp32 views in the parameters' layouts; it
+    divides by the count inside its kernels (``inv_world``)."""
+
+    def __init__(self, params):
+        self.params = list(params)
+        self.offsets, off = [], 0
+        for p in self.params:
+            if p.dtype not in (torch.float32, torch.bfloat16) or not p.is_cuda:
+                raise ValueError("GradAccumulator: CUDA fp32/bf16 parameters only")
+            self.offsets.append(off)
+            off += (p.numel() + 7) // 8 * 8
+        dev = self.params[0].device
+        self.flat = torch.zeros(max(off, 8), dtype=torch.float32, device=dev)
+        self.views = [self.flat[o:o + p.numel()].as_strided(p.shape, p.stride())
+                      for p, o in zip(self.params, self.offsets)]
+        chunks = [(i, c) for i, p in enumerate(self.params) for c in range((p.numel() + CHUNK - 1) // CHUNK)]
+        self.chunks = torch.tensor(chunks if chunks else [(0, 0)], dtype=torch.int32, device=dev).reshape(-1, 2)
+        self.n_chunks = len(chunks)
+        self._staged = {}
+        self._ptrs = None
+        self._table = None
+        self.count = 0  # micro-steps added in the current cycle
+        self._seen = [False] * len(self.params)  # had a gradient in any micro-step of the cycle
+
+    @torch.no_grad()
+    def add(self, grads):
+        """Add one micro-step's gradients (aligned with the parameters; None:
+        no gradient this micro-step).  The first call of a cycle overwrites."""
+        srcs = [_grad_source("GradAccumulator", self._staged, i, p, g)
+                for i, (p, g) in enumerate(zip(self.params, grads))]
+        ptrs = tuple(s.data_ptr() if s is not None else 0 for s in srcs)
+        if ptrs != self._ptrs:
+            rec = np.zeros(max(len(self.params), 1), dtype=_REC)
+            for i, (p, g) in enumerate(zip(self.params, srcs)):
+                rec[i]["grad"] = g.data_ptr() if g is not None else 0
+                rec[i]["numel"] = p.numel()
+                rec[i]["moff"] = self.offsets[i]
+                rec[i]["gdtype"] = 2 if g is None else (0 if g.dtype == torch.bfloat16 else 1)
+            self._table = torch.from_numpy(rec.view(np.uint8).copy()).to(self.flat.device)
+            self._ptrs = ptrs
+        L._check(L.lib().train_grad_accum(self._table.data_ptr(), self.chunks.data_ptr(), self.n_chunks,
+                                          self.flat.data_ptr(), 1 if self.count == 0 else 0, L._stream()),
+                 "train_grad_accum")
+        self.count += 1
+        for i, s in enumerate(srcs):
+            if s is not None:
+                self._seen[i] = True
+
+    def take(self):
+        """(grads, count) of the finished cycle, and start a new one: grads[i]
+        is the fp32 sum of parameter i in its layout (valid until the next
+        ``add``), or None when it had no gradient in the whole cycle (the
+        optimizer then skips it, torch.optim semantics); count the micro-steps."""
+        if self.count == 0:
+            raise RuntimeError("GradAccumulator.take() without an add()")
+        grads = [v if h else None for v, h in zip(self.views, self._seen)]
+        count = self.count
+        self.count = 0
+        self._seen = [False] * len(self.params)
+        return grads, count
+
 
 class DPGradReducer:
     """Data-parallel gradient sum in fp32.
 
     The replicated parameters' gradients (bf16 for GEMM / convolution
-    operands, fp32 otherwise) are widened into ONE flat fp32 buffer by one HIP
+    operands, fp32 otherwise; or a GradAccumulator's fp32 sums) are widened into ONE flat fp32 buffer by one HIP
     launch (``train_grad_pack``; a tensor without a gradient contributes
     zeros) and summed over the ranks with ONE all-reduce, so no ring hop
     rounds a partial sum to bf16.  ``__call__`` returns fp32 views of the
@@ -305,17 +390,7 @@ class DPGradReducer:
         self._table = None
 
     def _source(self, i, p, g):
-        if g is None:
-            return None
-        if g.shape != p.shape or g.dtype != p.dtype:
-            raise ValueError("DPGradReducer: gradient must have the parameter's shape and dtype")
-        if g.stride() != p.stride() or g.data_ptr() % 16:
-            buf = self._staged.get(i)
-            if buf is None:
-                buf = self._staged[i] = torch.empty_strided(p.shape, p.stride(), dtype=p.dtype, device=p.device)
-            buf.copy_(g)
-            return buf
-        return g
+        return _grad_source("DPGradReducer", self._staged, i, p, g)
 
     def _world(self):
         return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
@@ -556,18 +631,7 @@ class ShardedDPAdamW:
         return torch.tensor(ch if ch else [(0, 0)], dtype=torch.int32, device=self.device).reshape(-1, 2)
 
     def _source(self, i, g):
-        p = self.params[i]
-        if g is None:
-            return None
-        if g.shape != p.shape or g.dtype not in (p.dtype, torch.float32):
-            raise ValueError("ShardedDPAdamW: gradient must have the parameter's shape and dtype (or fp32)")
-        if g.stride() != p.stride() or g.data_ptr() % 16:
-            buf = self._staged.get(i)
-            if buf is None or buf.dtype != g.dtype:
-                buf = self._staged[i] = torch.empty_strided(p.shape, p.stride(), dtype=g.dtype, device=p.device)
-            buf.copy_(g)
-            return buf
-        return g
+        return _grad_source("ShardedDPAdamW", self._staged, i, self.params[i], g)
 
     def _agree_has_grad(self, srcs):
         local = torch.tensor([0 if s is None else 1 for s in srcs], dtype=torch.int32)

@@ -24,6 +24,11 @@ write the graph's static images, padded targets and box count directly.
 With mosaic (a -mosaic spec, TrainStep(mosaic=p)) an image carries the boxes
 of up to four, so the padding M is reserved from the augmenter's host bound
 (BatchAugment.need) before the launches.
+
+Gradient accumulation (an -nbs<N> spec, TrainStep(accumulate=K)): a replay
+overwrites the static gradient buffers, so after each one a HIP launch adds
+them to an fp32 sum (optim.GradAccumulator); every K-th call runs the
+data-parallel exchange and the optimizer once, on the mean gradient.
 """
 from __future__ import annotations
 
@@ -37,6 +42,7 @@ from torch import nn
 from .conv import check_grad_slots
 from .linear import TokenSelfAttention, deferred_weight_grads, merge_deferred
 from .model import RTDETRMoE
+from .schedule import accumulate_count
 
 _FUSED_CRIT = os.environ.get("MOE_FUSED_CRITERION", "1") != "0"  # A/B switch
 # MOE_ZERO=0: GPU data parallelism through the flat fp32 all-reduce + replicated
@@ -498,8 +504,20 @@ class TrainStep:
     def __init__(self, model: RTDETRMoE, criterion, images, ctx, *, lr=1e-4, lr_backbone=1e-5,
                  weight_decay=1e-4, clip_norm=0.1, graphs=True, ddp_local=None, world=1, precision="bf16",
                  targets=None, num_boxes=1.0, zero=None, seed=0, ema_decay=None, ema_tau=None, augment=None,
-                 content_hw=None, mosaic=None):
-        """seed: the run's seed (the denoising queries' noise generator, the
+                 content_hw=None, mosaic=None, accumulate=None):
+        """accumulate: micro-steps (calls) per optimizer step, K.  None takes
+        the model spec's nominal batch size (-nbs<N>): K = max(1, round(nbs /
+        (batch * world))), 1 without the token.  With K = 1 the step is
+        unchanged (no accumulator, the same launches).  With K > 1 every call
+        adds its gradients to an fp32 sum on the device (optim.GradAccumulator,
+        one HIP launch after the graph replay) and the K-th call runs the
+        data-parallel exchange, the clip and AdamW (and the weight average)
+        once on the mean gradient over micro-steps and ranks; every call
+        returns its own loss.  ``self.accumulate`` may be changed between calls
+        (the engine's warm-up ramp); ``micro_steps`` / ``opt_steps`` count the
+        calls and the optimizer steps.  ``set_lr_scale`` scales the learning
+        rates given here (the engine's schedule).
+        seed: the run's seed (the denoising queries' noise generator, the
         augmentation parameters' generator).
         augment: batch augmentation (augment.BatchAugment: scale / translate
         jitter, flip, HSV jitter of images and boxes, on the GPU two HIP
@@ -577,6 +595,18 @@ class TrainStep:
                                          weight_decay=weight_decay)
         self.flat = FlatOutputs(model)
         self.reducer = getattr(self, "reducer", None)
+        self.base_lrs = [float(lr_backbone), float(lr)]  # per LR group (backbone, rest): set_lr_scale scales these
+        if accumulate is None:
+            accumulate = accumulate_count(int(getattr(getattr(model, "spec", None), "nbs", 0)), images.shape[0], world)
+        if int(accumulate) < 1:
+            raise ValueError(f"accumulate must be >= 1, got {accumulate}")
+        self.accumulate = int(accumulate)
+        self.micro_steps = 0  # calls
+        self.opt_steps = 0    # optimizer steps
+        self.acc = None       # optim.GradAccumulator (GPU), allocated when a cycle of more than one micro-step starts
+        self._pending = 0     # CPU: backward passes summed in .grad since the last optimizer step
+        if self.accumulate > 1 and self.opt_params is None:
+            self._accumulator()
         if world > 1 and images.is_cuda:
             from ..moe.layer import MoEFFN
 
@@ -726,15 +756,20 @@ class TrainStep:
                 p.grad = None
             _drop_autograd_graphs(self.model)  # the captures' AccumulateGrad nodes (side stream) go too
 
-    def _allreduce_grads(self):
+    def _allreduce_grads(self, grads=None):
         """Data-parallel gradient sum (GPU, world > 1): the replicated
         parameters' gradients summed in fp32 by one all-reduce
         (optim.DPGradReducer).  Returns the gradient list in the optimizer's
         parameter order: the summed fp32 views for replicated parameters, the
         local gradients for expert-parallel ones; the optimizer divides by the
-        world size inside its kernels."""
-        red = {id(p): v for p, v in zip(self.dp_params, self.reducer([p.grad for p in self.dp_params]))}
-        return [red.get(id(p), p.grad) for p in self.opt.params]
+        world size inside its kernels.  ``grads``: the local gradients in the
+        optimizer's parameter order (an accumulation cycle's fp32 sums);
+        default: each parameter's ``.grad``."""
+        if grads is None:
+            grads = [p.grad for p in self.opt.params]
+        local = {id(p): g for p, g in zip(self.opt.params, grads)}
+        red = {id(p): v for p, v in zip(self.dp_params, self.reducer([local[id(p)] for p in self.dp_params]))}
+        return [red.get(id(p), local[id(p)]) for p in self.opt.params]
 
     def _mark(self, name):
         if self.phases is not None:
@@ -759,7 +794,7 @@ class TrainStep:
             self._optimizer_step()
             self._mark("optimizer")
             return loss
-        if self.runner is None:
+        if self.runner is None and self._pending == 0:  # (CPU, inside a cycle: autograd accumulates in .grad)
             for p in self.params:
                 p.grad = None
         dn_pack = None
@@ -801,20 +836,68 @@ class TrainStep:
         self._mark("optimizer")
         return loss.detach()
 
+    def _accumulator(self):
+        if self.acc is None:
+            from .optim import GradAccumulator
+
+            self.acc = GradAccumulator(self.opt.params)
+        return self.acc
+
+    def set_lr_scale(self, scales):
+        """Learning rates = the construction's (backbone, rest) times ``scales``
+        (one factor per LR group); they reach the next optimizer launch by value."""
+        if len(scales) != len(self.base_lrs):
+            raise ValueError(f"set_lr_scale: {len(self.base_lrs)} LR groups, got {len(scales)} factors")
+        lrs = [b * float(s) for b, s in zip(self.base_lrs, scales)]
+        if self.opt_params is None:
+            self.opt.lrs = lrs
+        else:
+            for g, v in zip(self.opt.param_groups, lrs):
+                g["lr"] = v
+
+    def lrs(self):
+        """The current learning rate of every LR group (backbone, rest)."""
+        return list(self.opt.lrs) if self.opt_params is None else [g["lr"] for g in self.opt.param_groups]
+
     def _optimizer_step(self):
+        self.micro_steps += 1
         if self.opt_params is None:  # GPU: FlatAdamW / ShardedDPAdamW (reduction + clip inside)
             # with a weight average, ModelEMA.update runs the optimizer step with this update's decay
             opt_step = self.opt.step if self.ema is None else self.ema.update
+            if self.accumulate <= 1 and (self.acc is None or self.acc.count == 0):
+                if self.reducer is not None:
+                    opt_step(self._allreduce_grads(), inv_world=1.0 / self.world)
+                else:
+                    opt_step()
+                self.opt_steps += 1
+                return
+            # accumulation: this micro-step's gradients into the fp32 sum; on the last one of the
+            # cycle the exchange + clip + AdamW once, on the mean over micro-steps and ranks
+            acc = self._accumulator()
+            acc.add([p.grad for p in self.opt.params])
+            if acc.count < self.accumulate:
+                return
+            grads, count = acc.take()
             if self.reducer is not None:
-                opt_step(self._allreduce_grads(), inv_world=1.0 / self.world)
-            else:
-                opt_step()
+                grads = self._allreduce_grads(grads)
+            opt_step(grads, inv_world=1.0 / (self.world * count))
+            self.opt_steps += 1
         else:
+            self._pending += 1
+            if self._pending < self.accumulate:
+                return
+            if self._pending > 1:  # autograd summed the cycle's backward passes: the mean
+                with torch.no_grad():
+                    for p in self.opt_params:
+                        if p.grad is not None:
+                            p.grad.div_(self._pending)
+            self._pending = 0
             if self.clip_norm > 0:
                 clip_grad_norm_sharded(self.dp_params, self.ep_params, self.clip_norm, self.ep_group)
             self.opt.step()
             if self.ema is not None:
                 self.ema.update()
+            self.opt_steps += 1
 
     def phase_summary(self):
         """{phase: (gpu ms, host ms)} averaged over the marked steps (syncs)."""

@@ -74,6 +74,9 @@ int main() {
                                                               0.999f, 1e-8f, f32, 1.0f, s));
   expect_error("ema_update misaligned ema", train_ema_update(p, i32, 1, f32 + 1, 0.5f, s));
   expect_error("ema_update decay<0", train_ema_update(p, i32, 1, f32, -0.1f, s));
+  expect_error("grad_accum misaligned acc", train_grad_accum(p, i32, 1, f32 + 1, 1, s));
+  expect_error("grad_accum acc=NULL", train_grad_accum(p, i32, 1, nullptr, 0, s));
+  expect_error("grad_accum n_chunks<0", train_grad_accum(p, i32, -1, f32, 0, s));
   expect_error("augment_images Wp=62", train_augment_images(p, 0, 3 * 64 * 62, 64 * 62, 62, 1, p, 0, f32, 1, 64, 62, 40,
                                                             60, 0.447f, s));
   expect_error("augment_boxes M=2048", train_augment_boxes(f32, reinterpret_cast<int64_t*>(buf), i32, f32, 1, 2048,
