@@ -102,6 +102,32 @@ int moe_route_dispatch(const int32_t* block_counts, int nblk, int T, int k, int 
                        int32_t* pos, int32_t* src_tok, float* row_gate, float* aux_out3, float* wcoef,
                        hipStream_t stream);
 
+/* Per-context routing statistics of one layer forward (validation's context
+ * report; no reference counterpart).  Tokens are image-major: token t belongs
+ * to image t / tokens_per_image, whose context is c = ctx_img[image] (ctx_img
+ * NULL: c = 0 and n_ctx must be 1).  ADDS to stats, int64 [n_ctx, E, 5]
+ * (never zeroes it: calls accumulate, graph replays included):
+ *   stats[c][e][0]  assignments  #{(t, j): topk_idx[t,j] == e}
+ *   stats[c][e][1]  top-1        #{t: topk_idx[t,0] == e}
+ *   stats[c][e][2]  dropped      #{(t, j): topk_idx[t,j] == e, pos[t,j] < 0}
+ *                                (0 when pos is NULL)
+ *   stats[c][e][3]  gate mass    sum of fix(topk_w[t,j]) where topk_idx[t,j] == e
+ *   stats[c][e][4]  prob mass    sum over t of fix(probs[t,e])
+ * over the tokens t of the images of context c, with fix(x) = (int64)
+ * rint((double) x * 2^32), round-half-even.  All sums are integers, so the
+ * table is bitwise reproducible whatever the order of arrival.  Tokens per
+ * context = sum_e stats[c][e][1].  An image whose context id is outside
+ * [0, n_ctx) and an expert index outside [0, E) contribute nothing and write
+ * nothing.  topk_idx / topk_w / pos [T, k], probs [T, E] as the router and the
+ * dispatch wrote them.  One workgroup per <= 128 tokens of one image: sums in
+ * registers and LDS, then at most 5 E 64-bit integer atomic adds.  T == 0:
+ * success, no launch.  Non-zero return for T % tokens_per_image != 0, E
+ * outside 1..64, k outside 1..8 or k > E, n_ctx < 1, NULL ctx_img with
+ * n_ctx != 1. */
+int moe_route_stats(const int32_t* topk_idx, const float* topk_w, const int32_t* pos, const float* probs,
+                    const int32_t* ctx_img, int n_ctx, int tokens_per_image, int T, int E, int k,
+                    long long* stats, hipStream_t stream);
+
 /* a6: y[t] = sum_j topk_w[t,j] * yp[pos[t,j]] (pos<0 skipped),
  * fp32 accumulation, bf16 out. */
 int moe_combine_fwd(const void* yp, const int32_t* pos, const float* topk_w,
@@ -1066,7 +1092,7 @@ int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t*
  * 9 Hungarian matching, 10 fp8 grouped GEMM, 11 dense linear weight gradients,
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
  * context-bias gradients, 15 training batch augmentation, 16 validation
- * matching.
+ * matching, 17 routing statistics.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1086,7 +1112,8 @@ enum moe_prof_kind {
   MOE_PROF_CONV = 13,     /* implicit-GEMM convolutions (rtdetr_conv_*) */
   MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
   MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
-  MOE_PROF_EVAL = 16       /* validation: detections matched to ground truth (rtdetr_eval_match) */
+  MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match) */
+  MOE_PROF_ROUTE_STATS = 17 /* validation: per-context routing statistics (moe_route_stats) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

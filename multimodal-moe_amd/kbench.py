@@ -8,6 +8,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py [--reps 50] [--rounds 5] [--variants 1,2] [--stages 3,4]
   python multimodal-moe_amd/kbench.py --augment     the batch-augmentation kernels at C2's batch
   python multimodal-moe_amd/kbench.py --eval-match  the validation matcher against the host loop
+  python multimodal-moe_amd/kbench.py --route-stats the routing-statistics kernel against its torch reference
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -320,6 +321,63 @@ def eval_match_leg(reps, rounds):
         print(json.dumps(out), flush=True)
 
 
+def route_stats_leg(reps, rounds):
+    """moe_route_stats at C2's eval shapes (batch 16: encoder T = 16 x 920,
+    decoder T = 16 x 300; E 8, k 2, 6 contexts) against
+    stats.route_stats_reference on the same device tensors (checked equal
+    first).  kernel_us: the kernel's dispatch-stamped execution time.
+    kernel_stream_us / reference_stream_us: stream time per call, from one
+    event pair around ``reps`` back-to-back calls (launch gaps included: what
+    the torch form's dozen launches cost in an eager pass).  Median, min and max
+    over the rounds, the two sides interleaved in each round."""
+    from src.moe.stats import route_stats_reference
+
+    B, E, k, n_ctx = 16, 8, 2, 6
+    g = torch.Generator().manual_seed(0)
+    for name, tpi in (("encoder", 920), ("decoder", 300)):
+        T = B * tpi
+        probs = torch.softmax(2.0 * torch.randn((T, E), generator=g), -1).cuda()
+        idx = torch.rand((T, E), generator=g).argsort(1)[:, :k].to(torch.int32).contiguous().cuda()
+        w = torch.softmax(torch.randn((T, k), generator=g), -1).cuda()
+        pos = torch.arange(T * k, dtype=torch.int32).view(T, k).clone()
+        pos[torch.rand((T, k), generator=g) < 0.1] = -1
+        pos = pos.cuda()
+        ci = torch.randint(n_ctx, (B,), generator=g).to(torch.int32).cuda()
+        table = torch.zeros((n_ctx, E, 5), dtype=torch.int64, device="cuda")
+        L.route_stats(idx, w, pos, probs, ci, n_ctx, tpi, table)
+        if not torch.equal(table, route_stats_reference(idx, w, pos, probs, ci, tpi, n_ctx)):
+            raise SystemExit("route_stats differs from route_stats_reference")
+
+        def kernel():
+            L.route_stats(idx, w, pos, probs, ci, n_ctx, tpi, table)
+
+        def reference():
+            table.add_(route_stats_reference(idx, w, pos, probs, ci, tpi, n_ctx))
+
+        def stream_us(fn, n):
+            fn()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return 1e3 * e0.elapsed_time(e1) / n
+
+        res = {"kernel_us": [], "kernel_stream_us": [], "reference_stream_us": []}
+        for _ in range(rounds):
+            res["kernel_us"].append(timed(kernel, reps))
+            res["kernel_stream_us"].append(stream_us(kernel, reps))
+            res["reference_stream_us"].append(stream_us(reference, reps))
+        out = {"kernel": "moe_route_stats", "shape": f"{name} T{T} E{E} k{k} C{n_ctx}"}
+        for key, v in res.items():
+            out[key] = round(statistics.median(v), 2)
+            out[key + "_min"] = round(min(v), 2)
+            out[key + "_max"] = round(max(v), 2)
+        print(json.dumps(out), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -366,6 +424,8 @@ def main():
     ap.add_argument("--augment", action="store_true", help="time the batch-augmentation kernels (C2's batch) and exit")
     ap.add_argument("--eval-match", action="store_true",
                     help="time the validation matcher (B 16, K 300, M 20 / 64) against the host loop and exit")
+    ap.add_argument("--route-stats", action="store_true",
+                    help="time moe_route_stats (C2's eval shapes, batch 16) against its torch reference and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -393,6 +453,9 @@ def main():
         return
     if a.eval_match:
         eval_match_leg(a.reps, a.rounds)
+        return
+    if a.route_stats:
+        route_stats_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

@@ -53,6 +53,7 @@ SIGNATURES = {
     "rtdetr_linear_narrow_fwd": (_I, [_P, _P, _P, _I, _P, _LL, _I, _I, _I, _P]),
     "rtdetr_linear_narrow_dgrad": (_I, [_P, _P, _P, _P, _LL, _I, _I, _P]),
     "moe_route_index": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "moe_route_stats": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "moe_route_dispatch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "moe_grouped_gemm_gather": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "moe_grouped_gemm_scatter": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
@@ -206,7 +207,7 @@ def lib() -> ctypes.CDLL:
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
               11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
-              16: "eval_match"}
+              16: "eval_match", 17: "route_stats"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -525,6 +526,44 @@ def route_dispatch(block_counts, topk_idx, local_rank, topk_w, aux_partials, T, 
                                     _ptr(pos), _ptr(tok), _ptr(gate), _ptr(out3), _ptr(wcoef), _stream()),
            "moe_route_dispatch")
     return pos, tok, hist, offsets, gate, out3, wcoef
+
+
+ROUTE_STATS_FIELDS = ("assignments", "top1", "dropped", "gate_mass", "prob_mass")  # stats[c][e][f]
+
+
+def route_stats(topk_idx, topk_w, pos, probs, ctx_img, n_ctx, tokens_per_image, stats):
+    """ADD one forward's per-context routing statistics to ``stats`` (int64
+    [n_ctx, E, 5], moe_route_stats: assignments, top-1, dropped, gate mass and
+    prob mass in 2^-32 fixed point).  topk_idx int32 / topk_w fp32 [T, k], pos
+    int32 [T, k] or None, probs fp32 [T, E], ctx_img int32 [T / tokens_per_image]
+    or None (then n_ctx must be 1).  One launch on the current stream."""
+    _need(topk_idx, torch.int32, "topk_idx")
+    _need(topk_w, torch.float32, "topk_w")
+    _need(probs, torch.float32, "probs")
+    _need(stats, torch.int64, "stats")
+    if topk_idx.dim() != 2 or probs.dim() != 2 or topk_w.shape != topk_idx.shape or probs.shape[0] != topk_idx.shape[0]:
+        raise MoEKernelError("route_stats: topk_idx / topk_w [T, k] and probs [T, E] expected")
+    T, k = (int(v) for v in topk_idx.shape)
+    E = int(probs.shape[1])
+    tensors = [topk_idx, topk_w, probs, stats]
+    if pos is not None:
+        _need(pos, torch.int32, "pos")
+        if pos.shape != topk_idx.shape:
+            raise MoEKernelError("route_stats: pos must be [T, k]")
+        tensors.append(pos)
+    if tuple(stats.shape) != (int(n_ctx), E, len(ROUTE_STATS_FIELDS)):
+        raise MoEKernelError(f"route_stats: stats must be int64 [{int(n_ctx)}, {E}, {len(ROUTE_STATS_FIELDS)}], "
+                             f"got {tuple(stats.shape)}")
+    tpi = int(tokens_per_image)
+    if ctx_img is not None:
+        _need(ctx_img, torch.int32, "ctx_img")
+        if tpi <= 0 or ctx_img.numel() * tpi < T:
+            raise MoEKernelError("ctx_img does not cover every token")
+        tensors.append(ctx_img)
+    if any(t.device != topk_idx.device for t in tensors):
+        raise MoEKernelError("route_stats: all tensors must be on one device")
+    _check(lib().moe_route_stats(_ptr(topk_idx), _ptr(topk_w), _ptr(pos), _ptr(probs), _ptr(ctx_img), int(n_ctx),
+                                 tpi, T, E, k, _ptr(stats), _stream()), "moe_route_stats")
 
 
 def grouped_gemm_gather(x, src_tok, b, offsets, G, max_rows, N, K, trans_b, epilogue, bias=None, aux=None):

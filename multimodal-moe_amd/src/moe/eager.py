@@ -47,12 +47,16 @@ def dispatch_positions(idx, E, cap):
     return pos, hist, offsets
 
 
-def route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap):
+def route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=None):
     """-> (xp [rows, d], w [T, k], lb, z, pos [T, k], hist [E], offsets [E+1], rows)."""
     T, d = x.shape
     E = wg.shape[0]
     probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize)
     pos, hist, offsets = dispatch_positions(idx, E, cap)
+    if route_stats is not None:
+        from .stats import record
+
+        record(route_stats[0], idx.detach(), w.detach(), pos, probs.detach(), route_stats[1], tokens_per_image)
     rows = int(offsets[-1])
     keep = pos >= 0
     t_idx = torch.arange(T, device=x.device).unsqueeze(1).expand(T, k)[keep]
@@ -149,10 +153,12 @@ def combine_eager(yp, w, pos, T):
 
 
 def moe_ffn_eager(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                  expert_dtype="bf16"):
+                  expert_dtype="bf16", route_stats=None):
+    """route_stats = (table, context ids): add this forward's per-context
+    routing statistics to the table (stats.route_stats_reference)."""
     T = x.shape[0]
     xp, w, lb, z, pos, hist, offsets, rows = route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k,
-                                                                  normalize, cap)
+                                                                  normalize, cap, route_stats=route_stats)
     if expert_dtype == "fp8":
         yp = expert_ffn_mx_eager(xp, w1, b1, w2, b2, offsets)
     else:

@@ -56,6 +56,9 @@ class MoEFFN(nn.Module):
         self.last_tokens = 0   # T of the last forward (bench: EP exchange bytes)
         self.y_has_residual = False  # EP: the residual was folded into the combine
         self.ep_aux_weighted = None  # EP on the GPU: lb_coef lb + z_coef z from the fused kernel
+        # routing statistics sink (stats.RouteStats.attach): an int64 table [n_ctx, E, 5] every forward
+        # adds to with one more launch after the dispatch; None (always, in training): nothing is launched
+        self.route_stats = None
 
     def forward(self, x: torch.Tensor, ctx_img: torch.Tensor | None, residual: bool = False) -> torch.Tensor:
         """x [B, L, d] (image-major tokens), ctx_img int [B] -> [B, L, d].
@@ -69,6 +72,8 @@ class MoEFFN(nn.Module):
         cap = cfg.capacity(T)
         cb = self.ctx_bias if (self.ctx_bias is not None and ctx_img is not None) else None
         ci = ctx_img.to(torch.int32).contiguous() if cb is not None else None
+        # the statistics are per context whether or not the router has a context bias
+        rs = (self.route_stats, ci if ci is not None else ctx_img) if self.route_stats is not None else None
         if self.ep_size > 1 or cfg.expert_parallel:  # C4: experts sharded over ranks, all-to-all exchange
             from .ep import moe_ffn_ep
 
@@ -84,7 +89,7 @@ class MoEFFN(nn.Module):
 
             y, aux, raw, hist = moe_ffn_hip(flat, self.wg, cb, self.w1, self.b1, self.w2, self.b2,
                                             ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype,
-                                            aux_coefs=(cfg.lb_coef, cfg.z_coef), residual=residual)
+                                            aux_coefs=(cfg.lb_coef, cfg.z_coef), residual=residual, route_stats=rs)
             self.last_aux = (raw[0], raw[1])
             self.last_aux_weighted = aux
             self.last_hist = hist
@@ -93,7 +98,7 @@ class MoEFFN(nn.Module):
             from .eager import moe_ffn_eager
 
             y, lb, z, hist = moe_ffn_eager(flat, self.wg, cb, self.w1, self.b1, self.w2, self.b2,
-                                           ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype)
+                                           ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype, route_stats=rs)
         y = y.to(x.dtype)
         if residual:
             y = flat + y

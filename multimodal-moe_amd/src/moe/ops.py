@@ -41,6 +41,7 @@ import os
 import torch
 
 from . import _lib as L
+from .stats import record as _record_stats
 
 
 def _bias(b):
@@ -146,7 +147,7 @@ class _RouteDispatchMX(torch.autograd.Function):
     that dXp (from _ExpertFFNMX.backward) reaches the dispatch transpose."""
 
     @staticmethod
-    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0):
+    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, stats=None):
         T, d = x.shape
         E = wg.shape[0]
         xb = x.to(torch.bfloat16).contiguous()
@@ -158,6 +159,8 @@ class _RouteDispatchMX(torch.autograd.Function):
         if pad:
             offsets, cap = _padded_offsets(E, pad, x.device), pad
         xq, xs, pos = L.permute_fwd_mx(xb, idx, lrank, rank_base, offsets, E, cap, rows)
+        if stats is not None:  # (table, context ids): the layer's routing statistics sink (stats.py)
+            _record_stats(stats[0], idx, w, pos, probs, stats[1], tokens_per_image)
         carrier = torch.zeros((1, 1), dtype=torch.bfloat16, device=x.device).expand(xq.shape[0], d)
         ctx.save_for_backward(xb, wg32, idx, w, probs, lse, pos,
                               ctx_img if ctx_img is not None else torch.empty(0))
@@ -169,7 +172,7 @@ class _RouteDispatchMX(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_xp, d_w, d_auxp, _p, _h, _o, _q, _s):
-        return _RouteDispatch.backward(ctx, d_xp, d_w, d_auxp, _p, _h, _o)
+        return _RouteDispatch.backward(ctx, d_xp, d_w, d_auxp, _p, _h, _o) + (None,)
 
 
 class _RouteIndex(torch.autograd.Function):
@@ -423,13 +426,14 @@ def route_dispatch_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize,
                                 rows, int(pad)) + (rows,)
 
 
-def route_dispatch_mx_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0):
-    """-> (carrier, w, auxp, pos, hist, offsets, xq, xs, rows): MXFP8 dispatch."""
+def route_dispatch_mx_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, route_stats=None):
+    """-> (carrier, w, auxp, pos, hist, offsets, xq, xs, rows): MXFP8 dispatch.
+    route_stats = (table, context ids): add this forward's routing statistics."""
     T = x.shape[0]
     E = wg.shape[0]
     rows = E * pad if pad else (T * k if cap <= 0 else min(T * k, E * cap))
     return _RouteDispatchMX.apply(x, wg, ctx_bias, ctx_img, int(tokens_per_image), int(k), bool(normalize),
-                                  int(cap), rows, int(pad)) + (rows,)
+                                  int(cap), rows, int(pad), route_stats) + (rows,)
 
 
 # MOE_FUSE_RESIDUAL=0: the residual add stays a torch add (A/B switch)
@@ -459,7 +463,7 @@ class _MoELayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tpi, k, normalize, cap, lb_coef, z_coef, weighted,
-                residual=False):
+                residual=False, stats=None):
         T, d = x.shape
         E = wg.shape[0]
         G, F, _ = w1.shape
@@ -470,6 +474,8 @@ class _MoELayer(torch.autograd.Function):
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tpi, k, normalize)
         pos, tok, hist, offsets, gate, out3, wcoef = L.route_dispatch(bcnt, idx, lrank, w, auxp, T, E, cap, rows,
                                                                       lb_coef, z_coef, row_gate=True)
+        if stats is not None:  # (table, context ids): the layer's routing statistics sink (stats.py)
+            _record_stats(stats[0], idx, w, pos, probs, stats[1], tpi)
         w1b = w1.to(torch.bfloat16).contiguous()
         w2b = w2.to(torch.bfloat16).contiguous()
         h, yp = _ffn_forward(xb, tok, w1b, b1, w2b, b2, offsets, G, rows)
@@ -525,20 +531,21 @@ class _MoELayer(torch.autograd.Function):
                                         dres=dyb if ctx.residual else None)
         # router weight + context-bias gradients: one HIP launch, fixed-order sums
         dwg, dcb = L.router_wgrad(dlogits, xb, ctx_img if has_ctx else None, tpi, C if has_ctx else 0)
-        return (dx.to(xdtype), dwg, dcb, dW1, db1, dW2, db2) + (None,) * 9
+        return (dx.to(xdtype), dwg, dcb, dW1, db1, dW2, db2) + (None,) * 10
 
 
 def moe_layer_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap, aux_coefs=None,
-                  residual=False):
+                  residual=False, route_stats=None):
     """_MoELayer: -> (y, lb_coef lb + z_coef z, raw (lb, z), hist) with aux_coefs,
     else (y, lb, z, hist); residual=True returns x + y (fused for bf16 x)."""
     fuse = bool(residual) and x.dtype == torch.bfloat16 and _FUSE_RESIDUAL
     if aux_coefs is not None:
         out = _MoELayer.apply(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, int(tokens_per_image), int(k),
-                              bool(normalize), int(cap), float(aux_coefs[0]), float(aux_coefs[1]), True, fuse)
+                              bool(normalize), int(cap), float(aux_coefs[0]), float(aux_coefs[1]), True, fuse,
+                              route_stats)
     else:
         out = _MoELayer.apply(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, int(tokens_per_image), int(k),
-                              bool(normalize), int(cap), 1.0, 1.0, False, fuse)
+                              bool(normalize), int(cap), 1.0, 1.0, False, fuse, route_stats)
     if residual and not fuse:  # fp32 activations (amp): keep the residual add in x's precision
         out = (x + out[0],) + tuple(out[1:])
     return out
@@ -592,7 +599,7 @@ def combine_hip(yp, w, pos, T, resid=None):
 
 
 def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                expert_dtype="bf16", aux_coefs=None, residual=False):
+                expert_dtype="bf16", aux_coefs=None, residual=False, route_stats=None):
     """Routed expert FFN of one layer on the GPU.
 
     x [T, d] (tokens of ``T // tokens_per_image`` images, image-major),
@@ -604,6 +611,9 @@ def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, n
     instead, aux = lb_coef lb + z_coef z from the fused aux-loss kernel.
     residual=True: the first output is x + y (the layer's residual branch;
     fused into combine / token_bwd on the bf16 path).
+    route_stats = (table int64 [n_ctx, E, 5], context ids [images] or None):
+    one more launch after the dispatch adds this forward's per-context routing
+    statistics to the table (moe_route_stats); None: nothing is launched.
     """
     if not x.is_cuda:
         raise L.MoEKernelError("moe_ffn_hip needs GPU tensors")
@@ -614,11 +624,11 @@ def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, n
     T = x.shape[0]
     if expert_dtype == "fp8":
         carrier, w, auxp, pos, hist, offsets, xq, xs, rows = route_dispatch_mx_hip(
-            x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap)
+            x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=route_stats)
         yp = expert_ffn_mx_hip(carrier, xq, xs, w1, b1, w2, b2, offsets, rows)
     else:
         return moe_layer_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                             aux_coefs, residual=residual)
+                             aux_coefs, residual=residual, route_stats=route_stats)
     y = combine_hip(yp, w, pos, T)
     if residual:
         y = x + y.to(x.dtype)

@@ -13,6 +13,7 @@ RCCL gradient all-reduce; fp32 eager on CPU (config C1).
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import json
 import math
@@ -100,6 +101,7 @@ class DetMetrics:
     model: ModelHandle | None
     save_dir: Path | None = None
     moe: dict = field(default_factory=dict)
+    context: dict | None = None  # the per-context report (validate(context_report=True)), else None
 
 
 def _results_dict(box: BoxMetrics) -> dict:
@@ -295,6 +297,8 @@ class TrainArgs:
     warmup_epochs: float | None = None  # LR / accumulation warm-up (-warm[<E>]); 0 = off
     lrf: float | None = None            # final LR factor of the decay (-lrf<f>); 1 = constant
     cos_lr: bool | None = None          # cosine decay (-cos)
+    # per-context validation report (mAP and expert routing per solar bin); None: MOE_CONTEXT_REPORT=1
+    context_report: bool | None = None
 
 
 def _seed_all(seed: int):
@@ -390,6 +394,7 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         nw = warmup_iters(warmup_epochs, _num_batches(a.data, "train", a.imgsz, a.batch, world, drop_last=on_gpu))
     ni = 0  # micro-batches since the start of the run
     csv_rows = []
+    want_report = _context_report_on(a.context_report)
     epoch = 0
     step = None
     shape = None
@@ -437,6 +442,7 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         # model's forward holds all-to-alls, so every rank runs the same
         # validation batches in lockstep (rank 0 keeps the metrics)
         metrics = None
+        report = {} if want_report else None
         ema = getattr(step, "ema", None)
         sharded = getattr(getattr(step, "opt", None), "W", 1) > 1
         # with a weight average the averaged model is validated; entering is a
@@ -444,9 +450,10 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
         if ema is not None and (rank == 0 or ep or sharded):
             with ema.applied():
                 if rank == 0 or ep:
-                    metrics = _evaluate(core, a.data, "val", a.imgsz, a.batch, device, a.workers, a.seed)
+                    metrics = _evaluate(core, a.data, "val", a.imgsz, a.batch, device, a.workers, a.seed,
+                                        report=report)
         elif rank == 0 or ep:
-            metrics = _evaluate(core, a.data, "val", a.imgsz, a.batch, device, a.workers, a.seed)
+            metrics = _evaluate(core, a.data, "val", a.imgsz, a.batch, device, a.workers, a.seed, report=report)
         # checkpoint state: fp32 masters (the fp32 averages with a weight average); expert
         # shards gathered to [E, ...] (collective)
         # (a sharded data-parallel optimizer gathers masters collectively: every rank joins)
@@ -469,6 +476,8 @@ def _train_worker(a: TrainArgs, rank: int, world: int, local: int | str) -> Trai
                 row.update({"lr/pg0": pg[0], "lr/pg1": pg[1], "train/accumulate": step.accumulate,
                             "train/opt_steps": step.opt_steps})
             row.update(_moe_stats(core))
+            if report is not None:
+                row.update(_context_columns(report))
             csv_rows.append(row)
         stop = torch.tensor([0.0], device=device)
         if rank == 0 and epoch - best_epoch >= a.patience:
@@ -500,6 +509,24 @@ def _moe_stats(model: RTDETRMoE) -> dict:
         if m.last_aux is not None:
             out[f"moe/l{i}_lb"] = float(m.last_aux[0].detach())
             out[f"moe/l{i}_z"] = float(m.last_aux[1].detach())
+    return out
+
+
+def _context_report_on(flag: bool | None) -> bool:
+    """The context-report switch: an explicit argument, else MOE_CONTEXT_REPORT=1."""
+    return os.environ.get("MOE_CONTEXT_REPORT") == "1" if flag is None else bool(flag)
+
+
+def _context_columns(report: dict) -> dict:
+    """results.csv columns of one epoch's context report: mAP50-95 per solar
+    bin (an empty cell for a bin without targets) and, per MoE layer, the mutual
+    information between context and expert (empty for an expert-parallel layer)."""
+    out = {}
+    for label in report["bins"]:
+        d = report["detection"].get(label)
+        out[f"metrics/mAP50-95(B)/{label}"] = d["mAP50-95"] if d is not None and d["targets"] > 0 else ""
+    for i, r in enumerate(report["routing"]):
+        out[f"moe/l{i}_ctx_mi"] = r["mi_bits"] if "mi_bits" in r else ""
     return out
 
 
@@ -569,6 +596,10 @@ class EvalForward:
         self.graphs = {}
         self.max_shapes = max_shapes
         self.enabled = os.environ.get("MOE_EVAL_GRAPHS", "1") != "0"
+        # stats.RouteStats attached to the model, if any: the warm-ups and prepare()'s replay run the
+        # layers' route_stats launches too, so its tables are put back after them -- a batch then adds
+        # to them exactly once, by the replay (or the eager run) that produces its outputs
+        self.route_stats = None
 
     def _run(self, images, ctx):
         with torch.autocast(images.device.type, dtype=torch.bfloat16, enabled=images.is_cuda, cache_enabled=False):
@@ -583,7 +614,10 @@ class EvalForward:
         """Capture the graph for this input shape now (outside any timed span)."""
         if images.is_cuda and self.enabled and self._key(images, ctx) not in self.graphs \
                 and len(self.graphs) < self.max_shapes:
+            snap = self.route_stats.snapshot() if self.route_stats is not None else None
             self(images, ctx)
+            if snap is not None:
+                self.route_stats.restore(snap)
 
     @torch.no_grad()
     def __call__(self, images, ctx):
@@ -595,6 +629,7 @@ class EvalForward:
             if len(self.graphs) >= self.max_shapes:
                 return self._run(images, ctx)
             si, sc = images.clone(), ctx.clone()
+            snap = self.route_stats.snapshot() if self.route_stats is not None else None
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):  # warm-up: convolution search, lazy library state, allocator
@@ -610,6 +645,8 @@ class EvalForward:
             with torch.cuda.graph(g, stream=side, capture_error_mode=CAPTURE_MODE):
                 out = self._run(si, sc)
             torch.cuda.synchronize()
+            if snap is not None:  # the two warm-ups added to the tables; the capture itself ran nothing
+                self.route_stats.restore(snap)
             ent = self.graphs[key] = (g, si, sc, out)
         g, si, sc, out = ent
         si.copy_(images)
@@ -620,56 +657,99 @@ class EvalForward:
 
 @torch.no_grad()
 def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed, speed: dict | None = None,
-              ev_out: list | None = None):
+              ev_out: list | None = None, report: dict | None = None):
+    """report: a dict to fill with the per-context report (``_fill_report``):
+    detection metrics per solar bin and each MoE layer's routing table, summed
+    over the split by one more HIP launch per layer forward.  None: the pass
+    launches and returns exactly what it does without the feature."""
     model.eval()
     on_gpu = device.type == "cuda"
     fwd = EvalForward(model)
+    stats = None
+    if report is not None:
+        from ..moe.stats import RouteStats
+
+        stats = fwd.route_stats = RouteStats(model)
     # on the GPU the per-image matching is one HIP launch per batch (MOE_EVAL_MATCH=0: the host loop)
     ev = DeviceDetectionEvaluator() if on_gpu else DetectionEvaluator()
     if ev_out is not None:
         ev_out.append(ev)
     t_pre = t_inf = t_post = 0.0
     n_img = 0
-    for images, targets, ctx in _batches(data, split, imgsz, batch, workers, seed, 0, 1, 0):
-        t0 = time.perf_counter()
-        images = images.to(device, non_blocking=True)
-        ctx = ctx.to(device)
-        t_cap = 0.0
-        if on_gpu:
-            images = images.contiguous(memory_format=torch.channels_last)
-            tc = time.perf_counter()
-            fwd.prepare(images, ctx)  # first batch of a shape: graph capture, untimed
-            t_cap = time.perf_counter() - tc
-            torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        out = fwd(images, ctx)
-        if on_gpu:
-            torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        H, W = images.shape[-2:]
-        if on_gpu:
-            ev.update_batch(*model.postprocess_batched(out, [(W, H)] * images.shape[0]), targets, size=(W, H))
-            torch.cuda.synchronize()
-        else:
-            dets = model.postprocess(out, [(W, H)] * images.shape[0])
-            for det, t in zip(dets, targets):
-                gt_xyxy = gt_xyxy_pixels(t["boxes"].numpy().astype(np.float64), W, H)
-                ev.update(det["boxes"].float().cpu().numpy(), det["scores"].float().cpu().numpy(),
-                          det["labels"].cpu().numpy(), gt_xyxy, t["labels"].numpy())
-        t3 = time.perf_counter()
-        t_pre += t1 - t0 - t_cap
-        t_inf += t2 - t1
-        t_post += t3 - t2
-        n_img += images.shape[0]
+    with stats.attach(model) if stats is not None else contextlib.nullcontext():
+        for images, targets, ctx in _batches(data, split, imgsz, batch, workers, seed, 0, 1, 0):
+            t0 = time.perf_counter()
+            ids = [int(c) for c in ctx.tolist()] if report is not None else None  # on the host, before the upload
+            images = images.to(device, non_blocking=True)
+            ctx = ctx.to(device)
+            t_cap = 0.0
+            if on_gpu:
+                images = images.contiguous(memory_format=torch.channels_last)
+                tc = time.perf_counter()
+                fwd.prepare(images, ctx)  # first batch of a shape: graph capture, untimed
+                t_cap = time.perf_counter() - tc
+                torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            out = fwd(images, ctx)
+            if on_gpu:
+                torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            H, W = images.shape[-2:]
+            if on_gpu:
+                ev.update_batch(*model.postprocess_batched(out, [(W, H)] * images.shape[0]), targets, size=(W, H),
+                                ctx=ids)
+                torch.cuda.synchronize()
+            else:
+                dets = model.postprocess(out, [(W, H)] * images.shape[0])
+                for i, (det, t) in enumerate(zip(dets, targets)):
+                    gt_xyxy = gt_xyxy_pixels(t["boxes"].numpy().astype(np.float64), W, H)
+                    ev.update(det["boxes"].float().cpu().numpy(), det["scores"].float().cpu().numpy(),
+                              det["labels"].cpu().numpy(), gt_xyxy, t["labels"].numpy(),
+                              ctx=ids[i] if ids is not None else None)
+            t3 = time.perf_counter()
+            t_pre += t1 - t0 - t_cap
+            t_inf += t2 - t1
+            t_post += t3 - t2
+            n_img += images.shape[0]
     model.train()
     if speed is not None and n_img:
         speed.update({"preprocess": 1e3 * t_pre / n_img, "inference": 1e3 * t_inf / n_img,
                       "loss": 0.0, "postprocess": 1e3 * t_post / n_img})
+    if report is not None:
+        _fill_report(report, model, ev, stats)
     return ev.compute()
 
 
+def _fill_report(report: dict, model: RTDETRMoE, ev: DetectionEvaluator, stats) -> None:
+    """The per-context report of one validation pass (context_report.json):
+    {"bins": the context labels, "detection": {bin: images, targets, precision,
+    recall, mAP50, mAP50-95} for the bins that had images, "routing": per MoE
+    layer its stats.routing_summary, or "routing": null for a layer without a
+    table}."""
+    from ..moe.context import CONTEXT_LABELS
+    from ..moe.stats import layer_names, routing_summary
+
+    report["bins"] = list(CONTEXT_LABELS)
+    report["detection"] = {
+        label: {"images": d["images"], "targets": d["targets"], "precision": d["box"].mp, "recall": d["box"].mr,
+                "mAP50": d["box"].map50, "mAP50-95": d["box"].map}
+        for label, d in ev.compute_by_context(CONTEXT_LABELS).items()}
+    tables = stats.tables()
+    report["routing"] = []
+    for name in layer_names(model):
+        if name in tables:
+            meta = stats.meta[name]
+            report["routing"].append({"layer": name, "experts": meta["experts"],
+                                      **routing_summary(tables[name], meta["top_k"], CONTEXT_LABELS)})
+        else:
+            report["routing"].append({"layer": name, "routing": None, "why": stats.skipped[name]})
+
+
 def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0", project=None, name=None,
-             workers=4, seed=0) -> DetMetrics:
+             workers=4, seed=0, context_report: bool | None = None) -> DetMetrics:
+    """context_report: also build the per-context report (``DetMetrics.context``
+    and, with a save directory, context_report.json there); None reads
+    MOE_CONTEXT_REPORT=1.  Off by default."""
     devices = parse_device(device)
     dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
     if dev.type == "cuda":
@@ -681,9 +761,12 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
     if dev.type == "cuda":
         model = model.to(memory_format=torch.channels_last)
     speed = {}
-    box = _evaluate(model, data, split, imgsz, batch, dev, workers, seed, speed)
+    report = {} if _context_report_on(context_report) else None
+    box = _evaluate(model, data, split, imgsz, batch, dev, workers, seed, speed, report=report)
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
         save_dir.mkdir(parents=True, exist_ok=True)
+        if report is not None:
+            (save_dir / "context_report.json").write_text(json.dumps(report, indent=1))
     return DetMetrics(results_dict=_results_dict(box), box=box, speed=speed, model=ModelHandle(model),
-                      save_dir=save_dir, moe=_moe_stats(model))
+                      save_dir=save_dir, moe=_moe_stats(model), context=report)

@@ -126,14 +126,17 @@ class DetectionEvaluator:
 
     def __init__(self):
         self.tp, self.conf, self.pred_cls, self.target_cls = [], [], [], []
+        self.image_ctx = []  # per image: its context id, or None when the update gave none
 
-    def update(self, pred_boxes, pred_scores, pred_labels, gt_boxes, gt_labels, conf_thres=0.001):
+    def update(self, pred_boxes, pred_scores, pred_labels, gt_boxes, gt_labels, conf_thres=0.001, *, ctx=None):
+        """ctx: the image's context id (moe.context), for compute_by_context()."""
         keep = pred_scores >= conf_thres
         pb, ps, pl = pred_boxes[keep], pred_scores[keep], pred_labels[keep]
         self.tp.append(match_predictions(pb, ps, pl, gt_boxes, gt_labels))
         self.conf.append(ps)
         self.pred_cls.append(pl)
         self.target_cls.append(gt_labels)
+        self.image_ctx.append(None if ctx is None else int(ctx))
 
     def average_recall(self, max_det: int = 100) -> float:
         """COCO AR@max_det (all classes, area "all"): per image the max_det
@@ -155,11 +158,36 @@ class DetectionEvaluator:
         return float(np.mean([(hits[c] / n_gt[c]).mean() for c in n_gt]))
 
     def compute(self) -> BoxMetrics:
+        return self._reduce(self.tp, self.conf, self.pred_cls, self.target_cls)
+
+    def compute_by_context(self, labels=None) -> dict:
+        """{context label: {"images", "targets", "box": BoxMetrics}} for every
+        context with at least one image: compute()'s reduction over that
+        context's images only, so each entry equals what a fresh evaluator fed
+        just those images returns.  labels: names by context id (default
+        moe.context.CONTEXT_LABELS; an id past them is named by its number).
+        Needs every update to have carried ``ctx``."""
+        if labels is None:
+            from ..moe.context import CONTEXT_LABELS as labels
+        if len(self.image_ctx) != len(self.tp) or any(c is None for c in self.image_ctx):
+            raise ValueError("compute_by_context: an update carried no context id (ctx=...)")
+        out = {}
+        for c in sorted(set(self.image_ctx)):
+            rows = [i for i, ci in enumerate(self.image_ctx) if ci == c]
+            pick = lambda xs: [xs[i] for i in rows]  # noqa: E731
+            tc = pick(self.target_cls)
+            out[labels[c] if 0 <= c < len(labels) else str(c)] = {
+                "images": len(rows), "targets": int(sum(len(t) for t in tc)),
+                "box": self._reduce(pick(self.tp), pick(self.conf), pick(self.pred_cls), tc)}
+        return out
+
+    @staticmethod
+    def _reduce(tps, confs, pred_clss, target_clss) -> BoxMetrics:
         cat = lambda xs, d: np.concatenate(xs, 0) if xs else np.zeros((0,) + d)  # noqa: E731
-        tp = cat(self.tp, (len(IOU_THRESHOLDS),))
-        conf = cat(self.conf, ())
-        pred_cls = cat(self.pred_cls, ())
-        target_cls = cat(self.target_cls, ())
+        tp = cat(tps, (len(IOU_THRESHOLDS),))
+        conf = cat(confs, ())
+        pred_cls = cat(pred_clss, ())
+        target_cls = cat(target_clss, ())
         box = BoxMetrics()
         if len(target_cls) == 0:
             return box
@@ -215,12 +243,13 @@ class DeviceDetectionEvaluator(DetectionEvaluator):
         return (1 <= K <= L.EVAL_MATCH_MAX_K and max_gt <= L.EVAL_MATCH_MAX_M
                 and 1 <= len(IOU_THRESHOLDS) <= L.EVAL_MATCH_MAX_T)
 
-    def update_batch(self, boxes, scores, labels, targets, conf_thres=0.001, *, size):
+    def update_batch(self, boxes, scores, labels, targets, conf_thres=0.001, *, size, ctx=None):
         """boxes [B, K, 4] xyxy pixels, scores [B, K], labels [B, K]: the stacked
         tensors of the postprocessor (``RTDETRMoE.postprocess_batched``).
         targets: per image a dict with ``boxes`` (normalised cxcywh [n, 4]) and
         ``labels`` [n] on the CPU, as the loader yields them.  size: (W, H), the
-        pixel size the predictions are scaled to.
+        pixel size the predictions are scaled to.  ctx: the batch's context ids
+        (a host sequence of B ints), for compute_by_context().
 
         Device path: one host-to-device copy (the padded truth), one launch and
         one device-to-host copy (tp, scores and labels packed) per batch."""
@@ -232,12 +261,15 @@ class DeviceDetectionEvaluator(DetectionEvaluator):
                for t in targets]
         if len(gts) != B:
             raise ValueError(f"update_batch: {B} images of predictions, {len(gts)} targets")
+        ctx = [None] * B if ctx is None else [int(c) for c in ctx]
+        if len(ctx) != B:
+            raise ValueError(f"update_batch: {B} images of predictions, {len(ctx)} context ids")
         max_gt = max((len(g) for g, _ in gts), default=0)
         boxes, scores = boxes.float(), scores.float()
         if B == 0 or not self._device_path(boxes, K, max_gt):
             for b, (g, gl) in enumerate(gts):
                 self.update(boxes[b].cpu().numpy(), scores[b].cpu().numpy(), labels[b].cpu().numpy(), g, gl,
-                            conf_thres)
+                            conf_thres, ctx=ctx[b])
             return
         from ..moe import _lib as L
 
@@ -274,3 +306,4 @@ class DeviceDetectionEvaluator(DetectionEvaluator):
             self.conf.append(sc[b][keep])
             self.pred_cls.append(lb[b][keep])
             self.target_cls.append(gl)
+            self.image_ctx.append(ctx[b])

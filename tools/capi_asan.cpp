@@ -88,6 +88,14 @@ int main() {
   expect_error("eval_match T=17", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 4, 17, u8, s));
   expect_error("eval_match M=0", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 0, 10, u8, s));
   expect_error("eval_match tp=NULL", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 4, 10, nullptr, s));
+  auto* i64 = reinterpret_cast<long long*>(buf);
+  expect_error("route_stats T%tpi", moe_route_stats(i32, f32, i32, f32, i32, 6, 5, 12, 8, 2, i64, s));
+  expect_error("route_stats E=65", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 65, 2, i64, s));
+  expect_error("route_stats k>E", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 2, 3, i64, s));
+  expect_error("route_stats k=9", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 16, 9, i64, s));
+  expect_error("route_stats n_ctx=0", moe_route_stats(i32, f32, i32, f32, i32, 0, 6, 12, 8, 2, i64, s));
+  expect_error("route_stats ctx=NULL n_ctx=6", moe_route_stats(i32, f32, i32, f32, nullptr, 6, 6, 12, 8, 2, i64, s));
+  expect_error("route_stats stats=NULL", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 8, 2, nullptr, s));
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
