@@ -925,6 +925,16 @@ int rtdetr_conv_wgrad_part(const void* dy, const void* x, float* part, int nspli
                            int W, int C, int N, int KS, int stride, hipStream_t stream);
 int rtdetr_conv_wgrad_reduce_batch(int n, const float* const* parts, const int* nsplits, const long long* nws,
                                    void* const* dws, int out_bf16, hipStream_t stream);
+/* The whole backward of a 1x1 stride-1 convolution with {C, N} = {64, 256}
+ * (either order: the ResNet stage-1 layers) in ONE launch that reads dy and x
+ * once: dx as rtdetr_conv_dgrad writes it (dx += add when given, then zeroed
+ * where x <= 0 when mask_input) and the nsplit fp32 slices of dW as
+ * rtdetr_conv_wgrad_part writes them (same slice bounds and summation order:
+ * both bitwise), for rtdetr_conv_wgrad_reduce_batch or any other slice sum.
+ * Any other shape returns an error (take the two launches). */
+int rtdetr_conv1x1_bwd(const void* dy, const void* x, const void* w, void* dx, float* part, int nsplit,
+                       const void* zero, int B, int H, int W, int C, int N, const void* add, int mask_input,
+                       hipStream_t stream);
 /* Measurement / A-B knobs (0, or -1 for conv_dgrad_flip, = automatic):
  * "conv_bm" forward pixel-tile rows 64 / 128 / 256; "conv_wg_stages"
  * weight-gradient LDS ring depth 2..4; "conv_wg_splits" weight-gradient pixel

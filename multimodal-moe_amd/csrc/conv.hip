@@ -29,6 +29,9 @@
 //                      GEMM M = Cout, N = KS^2 Cin, K = pixels, split over S
 //                      slices of the pixels (fp32 partials) and summed in a
 //                      fixed order by conv_wgrad_reduce_kernel (deterministic).
+//   conv1x1_bwd_kernel both of the above for the 1x1 stride-1 layers of ResNet
+//                      stage 1 ({C, N} = {64, 256}) in one launch that reads dY
+//                      and X once (HBM-bound layers); bitwise the two launches.
 // Tiles 128 x 128 x 64, 4 waves (2 x 2), an S-deep LDS-DMA ring (one
 // global_load_lds_dwordx4 per lane per 1 KiB, counted vmcnt waits, raw
 // s_barrier), K-contiguous operand images (fwd) or MN-contiguous ones read by
@@ -1283,6 +1286,292 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_batch_kernel(WgRedBatch
   wgrad_reduce_body(b.part[lo], b.nsplit[lo], b.n[lo], b.dw[lo], b.out_bf16, bid - b.base[lo], red);
 }
 
+// ---------------------------------------------------------------------------
+// 1x1 stride-1 backward in one launch: data gradient + weight-gradient slices
+// ---------------------------------------------------------------------------
+// The stage-1 1x1 layers ({C, N} = {64, 256}) are HBM-bound, and the two
+// launches of their backward (conv_fwd_kernel over dY, conv_wgrad_kernel) read
+// dY twice and X twice (once as the ReLU mask).  Here a workgroup owns one
+// pixel slice of rtdetr_conv_wgrad_splits and ALL of N x C:
+//   dW slice  16 K fp32 accumulators (64 registers per lane; wave w owns the
+//             64 x 64 block w of dW), written as conv_wgrad_kernel's partial;
+//   dX        per 64-pixel K-tile of the slice, from the same dY tile: C = 64:
+//             wave w computes pixels 16 w .. 16 w + 15 x 64 channels over
+//             K = 256; C = 256: all 64 pixels x channels 64 w .. 64 w + 63 over
+//             K = 64.  Same MFMA operand roles and K order (ascending 32-deep
+//             steps from a zero accumulator) as conv_fwd_kernel, same epilogue
+//             arithmetic as conv_epilogue (resid = add, mask = X), so both
+//             outputs are bitwise those of the two launches.
+// LDS: the 32 KiB weight W [N][C] stays resident; dY and X K-tiles stream
+// through a 3-deep LDS-DMA ring of 40 KiB stages (152 KiB, one workgroup per
+// CU: two stages = 80 KiB per CU in flight).  Every operand is a set of
+// [64 rows][64 bf16] sub-images (128-B rows, 8 KiB): dY N / 64 of them, X
+// C / 64, W 4, with one chunk swizzle (sub_swz) that serves both reads of the
+// dY tile -- pixel rows as the k of dW (ds_read_b64_tr_b16) and as the rows of
+// dX's operand (ds_read_b128 along n).  The X tile is the dW operand and then
+// the ReLU mask; the bf16 dX tile is staged in place over it (each wave over
+// the rows it owns) to leave as whole 128-B rows.  `add` has no room in the
+// ring: it is loaded to registers by loads the compiler does not count (an
+// ordinary load's use would drain the ring with vmcnt(0)), issued ahead of
+// the stage's DMA and waited for with the ring's own counted wait.
+struct Conv1x1BwdArgs {
+  const uint16_t* g;     // dY [P][N]
+  const uint16_t* x;     // X [P][C]
+  const uint16_t* w;     // W [N][C]
+  uint16_t* dx;          // [P][C]
+  float* part;           // [gridDim.x][N][C]
+  const uint16_t* add;   // [P][C] (ADD)
+  const uint16_t* zero;
+  int P, kt_per, mask;
+};
+
+// dma16 as an asm statement, which the compiler's wait-count pass does not see: behind the builtin it puts a
+// vmcnt(0) in front of the first LDS read that follows a DMA issue -- with one workgroup per CU that wait
+// would empty the ring in every iteration.  Completion is counted by hand (wait_vm) as for dma16.  M0 (the
+// DMA's LDS address) is saved and restored inside the statement.
+__device__ __forceinline__ void dma16_uncounted(const uint16_t* src, char* lds) {
+  const uint32_t dst =
+      __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds);
+  uint32_t keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(src), "s"(dst)
+               : "memory");
+}
+
+constexpr int kC1Stages = 3;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// chunk swizzle of a [64][64] bf16 sub-image: a bijection of row bits 1-3, so
+// 16 consecutive rows at one logical chunk fill 16 distinct 16-B slots
+// (ds_read_b128), and bits 1, 3 land in the chunk-pair index as mimg_swz<64>
+// has them (ds_read_b64_tr_b16: rows {0..3, 8..11} x 2 chunks, 16 slots)
+__device__ __forceinline__ int sub_swz(int r) { return (r & 2) | ((r >> 1) & 4) | ((r >> 2) & 1); }
+__device__ __forceinline__ int sub_off(int r, int c) { return r * 128 + ((c ^ sub_swz(r)) << 4); }
+// fragment whose k runs along the image's rows (read_frag<64, false> on this swizzle)
+__device__ __forceinline__ bf16x8 sub_frag_tr(const char* img, int col_base, int ks, int lane) {
+  const int i = lane & 15;
+  const int kr = ks * 32 + 8 * (lane >> 4) + (i >> 2);
+  const int col = col_base + 4 * (i & 3);
+  const int half = (col & 7) * 2;
+  char* base = const_cast<char*>(img);
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + sub_off(kr, col >> 3) + half));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(base + sub_off(kr + 4, col >> 3) + half));
+  bf16x8 v;
+  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
+  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
+  return v;
+}
+// fragment whose k runs along the image's columns
+__device__ __forceinline__ bf16x8 sub_frag_k(const char* img, int row_base, int ks, int lane) {
+  return *reinterpret_cast<const bf16x8*>(img + sub_off(row_base + (lane & 15), ks * 4 + (lane >> 4)));
+}
+
+template <int C, int N, bool ADD>
+__global__ __launch_bounds__(256) void conv1x1_bwd_kernel(Conv1x1BwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert((C == 64 && N == 256) || (C == 256 && N == 64), "stage-1 1x1 shapes");
+  constexpr int GS = N / 64, XS = C / 64;   // sub-images of a dY / X K-tile
+  constexpr int SUB = 64 * 128;
+  constexpr int STAGE = (GS + XS) * SUB;
+  constexpr int S = kC1Stages;
+  constexpr int GW = (GS + XS) * 2;         // DMA instructions per wave per stage
+  constexpr int WOFF = S * STAGE;           // the weight: sub-image (n block, c block) at (nb XS + cb) SUB
+  constexpr int DM = C == 64 ? 1 : 4;       // 16-pixel row blocks of dX per wave
+  constexpr int NCH = 2 * DM;               // 16-B chunks of the wave's dX rows per lane
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ktot = (a.P + 63) / 64;
+  const int kt0 = blockIdx.x * a.kt_per;
+  const int nk = max(0, min(a.kt_per, ktot - kt0));
+  float* out = a.part + (size_t)blockIdx.x * (N * C);
+  if (nk == 0) {  // a slice with no pixels
+    for (int i = tid; i < N * C / 4; i += 256) reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  // DMA instruction t = wave + 4 j covers rows 8 (t % 8) .. + 7 of sub-image t / 8 = j / 2: this lane's row is
+  // rowA (j even) or rowA + 32 (j odd), its source chunk the same for both (the swizzle has no bit 5)
+  const int rowA = 8 * wave + (lane >> 3);
+  const int c8 = ((lane & 7) ^ sub_swz(rowA)) * 8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int img = j >> 1, row = (img / XS) * 64 + rowA + 32 * (j & 1);
+    dma16_uncounted(a.w + (size_t)row * C + (img % XS) * 64 + c8,
+                    smem + WOFF + img * SUB + (wave + 4 * (j & 1)) * 1024);
+  }
+  auto issue = [&](int kt, int slot) {
+    char* buf = smem + slot * STAGE;
+    const long long p0 = (long long)(kt0 + kt) * 64 + rowA;
+#pragma unroll
+    for (int j = 0; j < GW; ++j) {
+      const int sub = j >> 1;
+      const long long p = p0 + 32 * (j & 1);
+      const uint16_t* src = sub < GS ? a.g + (size_t)p * N + sub * 64 + c8 : a.x + (size_t)p * C + (sub - GS) * 64 + c8;
+      dma16_uncounted(p < a.P ? src : a.zero + c8, buf + sub * SUB + (wave + 4 * (j & 1)) * 1024);
+    }
+  };
+  // dW: wave w owns output channels 64 w .. (N = 256) or input channels 64 w .. (C = 256)
+  const int nb = N == 256 ? wave : 0, cb = C == 256 ? wave : 0;
+  // dX: the wave's rows of the X sub-image xs (its mask, then its staged output)
+  const int xs = C == 256 ? wave : 0, row0 = C == 64 ? 16 * wave : 0;
+  f32x4 accw[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) accw[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < S - 1; ++s)
+    if (s < nk) issue(s, s);
+  const char* wimg = smem + WOFF;
+  int rslot = 0, islot = S - 1;
+  for (int kt = 0; kt < nk; ++kt) {
+    // K-tile kt's DMA has landed for this wave: the loads issued after it are K-tile kt + 1's and (ADD) the
+    // previous K-tile's add loads; stores are not counted on (a smaller count only waits longer)
+    if (kt + 1 < nk) {
+      if (ADD && kt > 0) wait_vm<GW + NCH>();
+      else wait_vm<GW>();
+    } else {
+      wait_vm<0>();
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // ... for every wave, and every wave is done with slot (kt - 1) % S
+    char* cur = smem + rslot * STAGE;
+    char* xt = cur + (GS + xs) * SUB;
+    const long long p0 = (long long)(kt0 + kt) * 64;
+    // this lane's 16-B chunks e of the wave's dX rows: row row0 + (lane + 64 e) / 8, chunk lane % 8
+    u32x4 av[NCH];
+    if constexpr (ADD) {
+#pragma unroll
+      for (int e = 0; e < NCH; ++e) {
+        const long long p = min(p0 + row0 + (lane >> 3) + 8 * e, (long long)a.P - 1);
+        const uint16_t* src = a.add + (size_t)p * C + xs * 64 + (lane & 7) * 8;
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(av[e]) : "v"(src) : "memory");
+      }
+    }
+    const bool more = kt + S - 1 < nk;
+    if (more) issue(kt + S - 1, islot);  // refills the slot consumed in iteration kt - 1
+    // dW += dY^T X over the K-tile's 64 pixels
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8 af[4], bfr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = sub_frag_tr(cur + nb * SUB, 16 * i, ks, lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bfr[j] = sub_frag_tr(cur + (GS + cb) * SUB, 16 * j, ks, lane);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          accw[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], accw[i][j], 0, 0, 0);
+    }
+    // dX tile = dY tile x W
+    f32x4 accd[DM][4];
+#pragma unroll
+    for (int i = 0; i < DM; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) accd[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (C == 64) {
+#pragma unroll
+      for (int k8 = 0; k8 < 8; ++k8) {
+        const bf16x8 af = sub_frag_k(cur + (k8 >> 1) * SUB, 16 * wave, k8 & 1, lane);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bf16x8 bfr = sub_frag_tr(wimg + (k8 >> 1) * SUB, 16 * j, k8 & 1, lane);
+          accd[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr, af, accd[0][j], 0, 0, 0);
+        }
+      }
+      // every wave reads the whole X tile for dW: all are done before the dX rows go over it
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 af[4], bfr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = sub_frag_k(cur, 16 * i, ks, lane);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bfr[j] = sub_frag_tr(wimg + wave * SUB, 16 * j, ks, lane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            accd[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], accd[i][j], 0, 0, 0);
+      }
+    }
+    // epilogue (conv_epilogue's arithmetic): the mask chunks leave the X tile, the bf16 tile goes over the
+    // wave's own rows of it (lane holds dX[16 i + (lane & 15)][16 j + 4 (lane >> 4) + 0..3]) and comes back
+    // as 16-B row chunks
+    uint4 xm[NCH];
+    if (a.mask) {
+#pragma unroll
+      for (int e = 0; e < NCH; ++e)
+        xm[e] = *reinterpret_cast<const uint4*>(xt + sub_off(row0 + (lane >> 3) + 8 * e, lane & 7));
+    }
+#pragma unroll
+    for (int i = 0; i < DM; ++i) {
+      const int r = row0 + 16 * i + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = 16 * j + 4 * (lane >> 4);
+        uint2 v;
+        v.x = pack2bf(accd[i][j][0], accd[i][j][1]);
+        v.y = pack2bf(accd[i][j][2], accd[i][j][3]);
+        *reinterpret_cast<uint2*>(xt + sub_off(r, col >> 3) + (col & 7) * 2) = v;
+      }
+    }
+    if constexpr (ADD) {  // the add loads have landed: only this iteration's DMA is younger
+      if (!more) wait_vm<0>();
+      if constexpr (NCH == 2) {
+        asm volatile("s_waitcnt vmcnt(%2)" : "+v"(av[0]), "+v"(av[1]) : "n"(GW) : "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(%8)"
+                     : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]), "+v"(av[4]), "+v"(av[5]), "+v"(av[6]),
+                       "+v"(av[7])
+                     : "n"(GW)
+                     : "memory");
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < NCH; ++e) {
+      const int r = row0 + (lane >> 3) + 8 * e;
+      uint4 v = *reinterpret_cast<const uint4*>(xt + sub_off(r, lane & 7));
+      if constexpr (ADD) {
+        float f[8], q[8];
+        unpack8(v, f);
+        unpack8(make_uint4(av[e][0], av[e][1], av[e][2], av[e][3]), q);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) f[t] = (f[t] + q[t]) + 0.f;  // (conv_epilogue adds its zero bias: -0 -> +0)
+        v = pack8(f);
+      }
+      if (a.mask) {  // keep where the mask element is > 0 (bf16: sign clear, not zero)
+        const uint32_t mw[4] = {xm[e].x, xm[e].y, xm[e].z, xm[e].w};
+        uint32_t vw[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t lo = mw[q] & 0xffffu, hi = mw[q] >> 16;
+          const uint32_t keep_lo = ((lo & 0x8000u) || lo == 0) ? 0u : 0xffffu;
+          const uint32_t keep_hi = ((hi & 0x8000u) || hi == 0) ? 0u : 0xffff0000u;
+          vw[q] &= keep_lo | keep_hi;
+        }
+        v = make_uint4(vw[0], vw[1], vw[2], vw[3]);
+      }
+      const long long p = p0 + r;
+      if (p < a.P) *reinterpret_cast<uint4*>(a.dx + (size_t)p * C + xs * 64 + (lane & 7) * 8) = v;
+    }
+    rslot = rslot + 1 == S ? 0 : rslot + 1;
+    islot = islot + 1 == S ? 0 : islot + 1;
+  }
+  // lane holds dW[64 nb + 16 i + (lane & 15)][64 cb + 16 j + 4 (lane >> 4) + 0..3]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float* row = out + (size_t)(64 * nb + 16 * i + (lane & 15)) * C + 64 * cb + 4 * (lane >> 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      *reinterpret_cast<float4*>(row + 16 * j) =
+          make_float4(accw[i][j][0], accw[i][j][1], accw[i][j][2], accw[i][j][3]);
+  }
+}
+
 // (per device; a failure is reported through moe_last_error and the launch
 // that follows fails its check_launch)
 template <auto FN>
@@ -1796,6 +2085,42 @@ extern "C" int rtdetr_conv_wgrad_reduce_batch(int n, const float* const* parts, 
   ProfScope prof(stream, PROF_CONV, bytes);
   MOE_LAUNCH(prof, conv_wgrad_reduce_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b);
   return check_launch("rtdetr_conv_wgrad_reduce_batch");
+}
+
+template <int C, int N, bool ADD>
+static void launch_conv1x1_bwd(const Conv1x1BwdArgs& a, int nsplit, hipStream_t stream, ProfScope& prof) {
+  constexpr size_t lds = kC1Stages * (C + N) * 128 + (size_t)N * C * 2;  // the ring + the resident weight
+  static_assert(lds <= 160 * 1024, "ring + weight exceed the CU's LDS");
+  allow_lds_once<conv1x1_bwd_kernel<C, N, ADD>>(lds);
+  MOE_LAUNCH(prof, (conv1x1_bwd_kernel<C, N, ADD>), dim3(nsplit), dim3(256), lds, stream, a);
+}
+
+extern "C" int rtdetr_conv1x1_bwd(const void* dy, const void* x, const void* w, void* dx, float* part, int nsplit,
+                                  const void* zero, int B, int H, int W, int C, int N, const void* add,
+                                  int mask_input, hipStream_t stream) {
+  const void* ptrs[6] = {dy, x, w, dx, part, zero};
+  if (int rc = conv_check(ptrs, 6, B, H, W, C, N, 1, 1, "rtdetr_conv1x1_bwd")) return rc;
+  if (!((C == 64 && N == 256) || (C == 256 && N == 64)))
+    return fail("rtdetr_conv1x1_bwd: takes {C, N} = {64, 256} (the ResNet stage-1 1x1 layers)");
+  if (!aligned16(add)) return fail("rtdetr_conv1x1_bwd: add must be 16-B aligned");
+  if (nsplit < 1 || nsplit > 256) return fail("rtdetr_conv1x1_bwd: nsplit must be 1..256");
+  Conv1x1BwdArgs a{static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w),
+                   static_cast<uint16_t*>(dx), part, static_cast<const uint16_t*>(add),
+                   static_cast<const uint16_t*>(zero), B * H * W, 0, mask_input ? 1 : 0};
+  const int ktot = (a.P + 63) / 64;
+  a.kt_per = (ktot + nsplit - 1) / nsplit;
+  const double P = a.P, nw = (double)N * C;
+  // dY, X and dX once each (X also serves as the mask), add when given, the weight, the partials
+  ProfScope prof(stream, PROF_CONV, 2.0 * P * (N + 2 * C + (add ? C : 0)) + 2.0 * nw + 4.0 * nsplit * nw, false, 0.0,
+                 4.0 * P * nw);
+  if (C == 64) {
+    if (add) launch_conv1x1_bwd<64, 256, true>(a, nsplit, stream, prof);
+    else launch_conv1x1_bwd<64, 256, false>(a, nsplit, stream, prof);
+  } else {
+    if (add) launch_conv1x1_bwd<256, 64, true>(a, nsplit, stream, prof);
+    else launch_conv1x1_bwd<256, 64, false>(a, nsplit, stream, prof);
+  }
+  return check_launch("rtdetr_conv1x1_bwd");
 }
 
 extern "C" int rtdetr_conv3x3_direct_fwd(const void* x, const float* wf, const float* bias, void* y, int B, int H,

@@ -12,7 +12,10 @@ F.conv2d (MIOpen) for the rest.  Forward: one implicit-GEMM launch (no im2col
 buffer).  Backward: the data gradient is the same kernel over dY with the
 weight flipped and transposed (written to a workspace for large problems,
 read in place for small ones); the weight gradient is split over pixel slices
-with fp32 partials summed in a fixed order (deterministic).
+with fp32 partials summed in a fixed order (deterministic).  The 1x1 layers of
+ResNet stage 1 ({C, N} = {64, 256}) take both gradients from one launch that
+reads g and x once (rtdetr_conv1x1_bwd, bitwise the two; MOE_CONV_BWD_FUSE=0
+keeps the two launches).
 MOE_HIP_CONV=0 keeps every convolution on MIOpen (A/B switch).
 """
 from __future__ import annotations
@@ -215,6 +218,10 @@ class batched_flips:
 
 # MOE_BATCHED_FLIPS=0: every flipping data gradient writes its own W' (A/B switch)
 _BATCHED_FLIPS = os.environ.get("MOE_BATCHED_FLIPS", "1") != "0"
+# MOE_CONV_BWD_FUSE=0: the ResNet stage-1 1x1 layers' backward as the two
+# launches (data gradient, weight-gradient slices) instead of the one
+# rtdetr_conv1x1_bwd launch that reads g and x once (A/B switch; bitwise equal)
+_BWD_FUSE_ON = os.environ.get("MOE_CONV_BWD_FUSE", "1") != "0"
 
 
 def _bwd(x, w, g, need_x, need_w, mask_input, add=None, st=1):
@@ -229,6 +236,22 @@ def _bwd(x, w, g, need_x, need_w, mask_input, add=None, st=1):
     z = _zero(x.device).data_ptr()
     s = L._stream()
     gx = gw = None
+    if (_BWD_FUSE_ON and need_x and need_w and ks == 1 and st == 1 and {C, N} == {64, 256}
+            and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        # one launch for both gradients (rtdetr_conv1x1_bwd: g and x cross HBM once); it reads W in place
+        gx = torch.empty((B, C, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+        ns = L.lib().rtdetr_conv_wgrad_splits(B, H, W, C, N, ks)
+        part = torch.empty(ns * N * C, dtype=torch.float32, device=x.device)
+        gw = torch.empty_like(w, memory_format=torch.channels_last)
+        L._check(L.lib().rtdetr_conv1x1_bwd(g.data_ptr(), x.data_ptr(), w.data_ptr(), gx.data_ptr(), part.data_ptr(),
+                                            ns, z, B, H, W, C, N, None if add is None else _nhwc(add).data_ptr(),
+                                            int(bool(mask_input)), s), "rtdetr_conv1x1_bwd")
+        pend = _WG_PENDING[0]
+        if pend is not None:  # the slice sum runs in the scope's batched reduction (deferred_wgrads)
+            pend.append((part, ns, N * C, gw))
+        else:  # (a batch of one: rtdetr_conv_wgrad's own reduction, bitwise)
+            _reduce_wgrads([(part, ns, N * C, gw)], s)
+        return gx, gw
     if need_x:
         gx = torch.empty((B, C, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
         nb = L.lib().rtdetr_conv_dgrad_workspace(B, H, W, C, N, ks)
@@ -312,11 +335,18 @@ def flush_wgrads():
     pend = _WG_PENDING[0]
     if not pend:
         return
+    from ..moe import _lib as L
+
+    _reduce_wgrads(pend, L._stream())
+    pend.clear()
+
+
+def _reduce_wgrads(pend, s):
+    """The slice sums of the (part, nsplit, numel, gw) entries of pend, _WG_BATCH per launch."""
     import ctypes
 
     from ..moe import _lib as L
 
-    s = L._stream()
     for i in range(0, len(pend), _WG_BATCH):
         chunk = pend[i:i + _WG_BATCH]
         n = len(chunk)
@@ -327,7 +357,6 @@ def flush_wgrads():
         cv = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
         L._check(L.lib().rtdetr_conv_wgrad_reduce_batch(n, cv(parts), cv(nsplit), cv(numel), cv(dws), 1, s),
                  "rtdetr_conv_wgrad_reduce_batch")
-    pend.clear()
 
 
 class GradLink:
