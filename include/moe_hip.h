@@ -781,6 +781,36 @@ int rtdetr_eval_match(const float* boxes, const float* scores, const int32_t* la
                       const int32_t* gt_labels, const int32_t* n_valid, const double* thr, int B, int K, int M,
                       int T, uint8_t* tp, hipStream_t stream);
 
+/* Inference preprocessing (engine.predict, preprocess.py): B decoded frames,
+ * uint8 HWC RGB of any sizes, to the model's input in one launch: resize to
+ * out_h x out_w with the antialiased bilinear filter of PIL / torch
+ * (F.interpolate(mode="bilinear", antialias=True, align_corners=False); stated
+ * by preprocess.resize_reference), / 255, zero padding to pad_h x pad_w with
+ * the content top-left, channels-last.
+ * src: one device buffer holding the frames; desc int64 [B][4] on the device:
+ * byte offset into src, height, width, row stride in bytes (>= 3 width); no
+ * alignment is assumed for offsets or strides, and the frames of a batch may
+ * all differ in size.  dst fp32 [B][pad_h][pad_w][3], the memory of a
+ * channels-last [B, 3, pad_h, pad_w] tensor: every element is written exactly
+ * once, the padding zeros included (no memset, atomics or workspace), so dst
+ * may be a reused buffer or a captured graph's static input.
+ * A slot with height or width <= 0 is empty: its whole image is zeros (how a
+ * last partial batch keeps a captured batch size); so is a slot whose side
+ * exceeds 16384, whose offset is negative or whose stride is below 3 width.
+ * The caller guarantees offset + (height - 1) stride + 3 width <= the size of
+ * src for every other slot (_lib.resize_pad checks its host copy).
+ * Per axis n_in -> n_out: scale = n_in / n_out, support = max(scale, 1),
+ * output i has c = scale (i + 0.5), taps j in [max(int(c - support + 0.5), 0),
+ * min(int(c + support + 0.5), n_in)) with weight max(0, 1 - |(j - c + 0.5) /
+ * support|) over their sum; ranges and weights in fp64, rounded to fp32 once
+ * normalised, both passes accumulated in fp32 with an fp32 intermediate, then
+ * a true division by 255.0f: at n_in == n_out the result is float(x) / 255.0f
+ * bit for bit.  Any upscaling; a reduction up to 8 per axis runs tiled through
+ * LDS, a larger one in a direct (slower) form with the same arithmetic.
+ * B == 0 returns 0 without a launch. */
+int rtdetr_resize_pad_u8(const uint8_t* src, const long long* desc, int B, int out_h, int out_w, int pad_h,
+                         int pad_w, float* dst, hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -1102,7 +1132,7 @@ int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t*
  * 9 Hungarian matching, 10 fp8 grouped GEMM, 11 dense linear weight gradients,
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
  * context-bias gradients, 15 training batch augmentation, 16 validation
- * matching, 17 routing statistics.
+ * matching, 17 routing statistics, 18 inference preprocessing (resize).
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1123,7 +1153,8 @@ enum moe_prof_kind {
   MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
   MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
   MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match) */
-  MOE_PROF_ROUTE_STATS = 17 /* validation: per-context routing statistics (moe_route_stats) */
+  MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
+  MOE_PROF_RESIZE = 18     /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

@@ -9,6 +9,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --augment     the batch-augmentation kernels at C2's batch
   python multimodal-moe_amd/kbench.py --eval-match  the validation matcher against the host loop
   python multimodal-moe_amd/kbench.py --route-stats the routing-statistics kernel against its torch reference
+  python multimodal-moe_amd/kbench.py --resize      the inference resize kernel against the host resize it replaces
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -378,6 +379,81 @@ def route_stats_leg(reps, rounds):
         print(json.dumps(out), flush=True)
 
 
+def resize_leg(reps, rounds):
+    """rtdetr_resize_pad_u8 on a batch of 16 frames: ZOD's 3848 x 2168 ->
+    1248 x 704, and 1280 x 720 at identity scale padded to 736.  kernel_us: the
+    kernel's dispatch-stamped execution time; GBs: (source bytes + 12 pad_h
+    pad_w B) over it, and its share of the HBM peak.  device_path_ms: upload of
+    the packed uint8 batch + the launch, wall clock.  host_path_ms: what it
+    replaces, on this machine's CPU in this process -- PIL resize +
+    _padded_image per frame, the fp32 upload and the channels-last copy, wall
+    clock.  Median, min and max over the rounds, the sides interleaved in each
+    round; the kernel's output is checked against resize_reference first."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe.preprocess import HostCollate, PackCollate, padded_hw, resize_reference
+
+    B = 16
+    rng = np.random.default_rng(0)
+    for name, (sh, sw), imgsz in (("zod", (2168, 3848), (704, 1248)), ("identity", (720, 1280), (720, 1280))):
+        out_hw, pad_hw = padded_hw(imgsz)
+        # smooth content plus noise, one frame per slot
+        frames = []
+        for _ in range(B):
+            base = rng.integers(0, 256, (sh // 8 + 1, sw // 8 + 1, 3)).astype(np.float32)
+            up = np.kron(base, np.ones((8, 8, 1), np.float32))[:sh, :sw]
+            frames.append(np.clip(up + rng.normal(0, 8, (sh, sw, 3)), 0, 255).astype(np.uint8))
+        items = [(f, f"{i}.png", 0) for i, f in enumerate(frames)]
+        packed = PackCollate(out_hw)(items)
+        buf, desc = packed["buf"].pin_memory(), packed["desc"]
+        dbuf = buf.cuda()
+        out = L.resize_pad(dbuf, desc, out_hw, pad_hw)
+        ref = resize_reference(frames[0], *out_hw, *pad_hw)
+        err = float((out[0].cpu().double() - ref).abs().max())
+        if err > 5e-6:
+            raise SystemExit(f"resize_pad differs from resize_reference by {err:.3e}")
+        ddesc = desc.cuda()
+        host = HostCollate(out_hw, pad_hw)
+
+        def kernel():
+            L.resize_pad(dbuf, None, out_hw, pad_hw, out=out, desc_dev=ddesc)
+
+        def device_path():
+            L.resize_pad(buf.cuda(non_blocking=True), desc, out_hw, pad_hw, out=out)
+
+        def host_path():
+            host(items)["images"].cuda(non_blocking=True).contiguous(memory_format=torch.channels_last)
+
+        def wall(fn, n):
+            ts = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            return statistics.median(ts)
+
+        res = {"kernel_us": [], "device_path_ms": [], "host_path_ms": []}
+        for _ in range(rounds):
+            res["kernel_us"].append(timed(kernel, reps))
+            res["device_path_ms"].append(wall(device_path, 5))
+            res["host_path_ms"].append(wall(host_path, 1))
+        byts = int(buf.numel()) + 12 * pad_hw[0] * pad_hw[1] * B
+        line = {"kernel": "rtdetr_resize_pad_u8", "shape": f"{name} B{B} {sh}x{sw} -> {out_hw[0]}x{out_hw[1]} "
+                f"(pad {pad_hw[0]}x{pad_hw[1]})", "max_err_vs_reference": err, "bytes": byts}
+        for k, v in res.items():
+            line[k] = round(statistics.median(v), 3)
+            line[k + "_min"] = round(min(v), 3)
+            line[k + "_max"] = round(max(v), 3)
+        line["GBs"] = round(byts / line["kernel_us"] * 1e-3, 1)
+        line["hbm_peak_share"] = round(line["GBs"] / L.PEAK_HBM_GBS, 3)
+        line["host_over_device_path"] = round(line["host_path_ms"] / line["device_path_ms"], 1)
+        print(json.dumps(line), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -426,6 +502,9 @@ def main():
                     help="time the validation matcher (B 16, K 300, M 20 / 64) against the host loop and exit")
     ap.add_argument("--route-stats", action="store_true",
                     help="time moe_route_stats (C2's eval shapes, batch 16) against its torch reference and exit")
+    ap.add_argument("--resize", action="store_true",
+                    help="time rtdetr_resize_pad_u8 (16 ZOD-sized frames, and identity scale) against the host "
+                         "resize it replaces and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -456,6 +535,9 @@ def main():
         return
     if a.route_stats:
         route_stats_leg(a.reps, a.rounds)
+        return
+    if a.resize:
+        resize_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

@@ -1,0 +1,52 @@
+"""Detect on image files with a trained RT-DETR-MoE checkpoint (or a bare
+architecture spec) and write predictions.json (COCO results format) -- and,
+with --save-img, overlays -- under RUNS_DIR/rtdetr/<run-name>_predict.
+
+Same flag style as scripts/eval_detector.py.  --source is a directory, a glob,
+one image file or a dataset yaml; frames may have any size.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from pathlib import Path
+
+PKG_ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(PKG_ROOT)) if str(PKG_ROOT) not in sys.path else None
+
+from src.paths import RUNS_DIR  # noqa: E402
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(description="Predict with a detector run.")
+    ap.add_argument("--weights", type=str, required=True, help="checkpoint (best.pt / last.pt) or architecture spec")
+    ap.add_argument("--source", type=str, required=True, help="directory, glob, image file or dataset yaml")
+    ap.add_argument("--img-h", type=int, default=704)
+    ap.add_argument("--img-w", type=int, default=1248)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--device", type=str, default="0")
+    ap.add_argument("--conf", type=float, default=0.25)
+    ap.add_argument("--max-det", type=int, default=300)
+    ap.add_argument("--context", type=str, default=None,
+                    help="one solar context label for every frame (default: contexts.json / COCO jsons by the source)")
+    ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--save-img", action="store_true", help="also write the frames with their boxes drawn")
+    ap.add_argument("--run-name", type=str, default="rtdetr")
+    return ap.parse_args(argv)
+
+
+def main(argv=None) -> None:
+    a = parse_args(argv)
+    from src.rtdetr_moe import engine
+
+    res = engine.predict(a.weights, a.source, imgsz=(a.img_h, a.img_w), batch=a.batch, device=a.device, conf=a.conf,
+                         max_det=a.max_det, contexts=a.context, workers=a.workers, project=str(RUNS_DIR / "rtdetr"),
+                         name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img)
+    n_det = sum(len(p.scores) for p in res.predictions)
+    print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
+    print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))
+    print(f"Saved predictions -> {res.save_dir / 'predictions.json'}")
+
+
+if __name__ == "__main__":
+    main()

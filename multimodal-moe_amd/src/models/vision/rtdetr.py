@@ -34,6 +34,7 @@ __all__ = [
     "RtdetrTrainConfig", "train_rtdetr_detector", "eval_rtdetr_detector", "save_rtdetr_metrics_json",
     "save_rtdetr_training_summary", "get_rtdetr_model_size_stats_from_weights",
     "infer_model_variant_from_weights", "save_metrics_table_csv", "save_run_metadata_artifacts",
+    "predict_rtdetr_detector",
 ]
 
 DEFAULT_MODEL = "rtdetr-r50-moe8-top2"
@@ -106,6 +107,26 @@ def eval_rtdetr_detector(
     eng = _engine()
     return eng.validate(_check_model_name(weights_path), data_yaml, split=split, imgsz=_imgsz(imgsz),
                         batch=batch, device=device, project=project, name=name)
+
+
+def predict_rtdetr_detector(
+    weights_path: str,
+    source,
+    imgsz: Union[int, tuple[int, int]] = (704, 1248),
+    batch: int = 16,
+    device: str = "0",
+    conf: float = 0.25,
+    project: str | None = None,
+    name: str | None = None,
+):
+    """Detect on image files (a directory, a glob, a list of paths or a dataset
+    yaml) of any size; returns a results object with ``.predictions`` (per
+    image: path, source size, context id, boxes xyxy in source pixels, scores,
+    labels), ``.speed`` (ms per image), ``.save_dir`` (predictions.json in COCO
+    results format when ``project`` and ``name`` are given) and ``.model``."""
+    eng = _engine()
+    return eng.predict(_check_model_name(weights_path), source, imgsz=_imgsz(imgsz), batch=batch, device=device,
+                       conf=conf, project=project, name=name)
 
 
 def save_rtdetr_metrics_json(metrics, out_path: str | Path) -> Path:

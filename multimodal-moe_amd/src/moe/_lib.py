@@ -116,6 +116,7 @@ SIGNATURES = {
     "moe_router_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rtdetr_hungarian_match": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_eval_match": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "rtdetr_resize_pad_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -208,7 +209,7 @@ def lib() -> ctypes.CDLL:
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
               11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
-              16: "eval_match", 17: "route_stats"}
+              16: "eval_match", 17: "route_stats", 18: "resize"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -838,6 +839,73 @@ def eval_match(boxes, scores, labels, gt_boxes, gt_labels, n_valid, thr):
                                  _ptr(n_valid), _ptr(thr), B, K, M, T, _ptr(tp), _stream())
     _check(rc, "rtdetr_eval_match")
     return tp
+
+
+RESIZE_MAX_SIDE = 16384  # rtdetr_resize_pad_u8's largest source side
+
+
+def check_resize_desc(desc, nbytes: int) -> None:
+    """Validate a host descriptor table (int64 [B, 4]: byte offset, height,
+    width, row stride in bytes) against a source buffer of ``nbytes`` bytes:
+    every non-empty slot (height and width > 0) must lie inside the buffer."""
+    if desc.dim() != 2 or desc.shape[1] != 4 or desc.dtype != torch.int64 or desc.is_cuda:
+        raise MoEKernelError("resize_pad: desc must be a host int64 [B, 4] tensor")
+    for b, (off, h, w, stride) in enumerate(desc.tolist()):
+        if h <= 0 or w <= 0:
+            continue  # an empty slot: never read
+        if h > RESIZE_MAX_SIDE or w > RESIZE_MAX_SIDE:
+            raise MoEKernelError(f"resize_pad: slot {b}: {h} x {w} exceeds the largest side {RESIZE_MAX_SIDE}")
+        if off < 0 or stride < 3 * w or off + (h - 1) * stride + 3 * w > nbytes:
+            raise MoEKernelError(f"resize_pad: slot {b} (offset {off}, {h} x {w}, stride {stride}) lies outside "
+                                 f"the {nbytes}-byte source buffer")
+
+
+def resize_pad(src, desc_host, out_hw, pad_hw, out=None, desc_dev=None):
+    """The model's input from a batch of decoded frames, one launch
+    (rtdetr_resize_pad_u8): src uint8 device buffer with the frames (HWC RGB)
+    back to back; desc_host int64 [B, 4] on the host (byte offset, height,
+    width, row stride; height or width <= 0: an empty slot -> zeros), validated
+    against src here and then uploaded (into ``desc_dev``, a device int64
+    [B, 4], when given: a captured launch keeps reading that tensor; with
+    desc_host None, desc_dev is launched as it stands -- the caller ran
+    check_resize_desc and uploaded it, as a launch under graph capture must).
+    Returns the fp32 channels-last [B, 3, pad_h, pad_w] tensor (``out`` when
+    given), every element written: content resized to out_hw top-left with the
+    antialiased bilinear filter, / 255, zero padding."""
+    if not src.is_cuda:
+        raise MoEKernelError("src must be a GPU tensor (HIP path has no CPU fallback)")
+    if src.dtype != torch.uint8 or src.dim() != 1 or not src.is_contiguous():
+        raise MoEKernelError("resize_pad: src must be a contiguous 1-D uint8 tensor")
+    (oh, ow), (ph, pw) = (int(v) for v in out_hw), (int(v) for v in pad_hw)
+    if oh < 1 or ow < 1 or ph < oh or pw < ow:
+        raise MoEKernelError(f"resize_pad: need out >= 1 and pad >= out, got out {oh} x {ow}, pad {ph} x {pw}")
+    if desc_dev is not None:
+        _need(desc_dev, torch.int64, "desc_dev")
+        if desc_dev.dim() != 2 or desc_dev.shape[1] != 4:
+            raise MoEKernelError("resize_pad: desc_dev must be [B, 4]")
+    if desc_host is None:  # the caller validated and uploaded the table itself (a launch under capture)
+        if desc_dev is None:
+            raise MoEKernelError("resize_pad: desc_host or desc_dev is needed")
+        B = int(desc_dev.shape[0])
+    else:
+        check_resize_desc(desc_host, src.numel())
+        B = int(desc_host.shape[0])
+        if desc_dev is None:
+            desc_dev = desc_host.to(src.device, non_blocking=True)
+        else:
+            if int(desc_dev.shape[0]) != B:
+                raise MoEKernelError("resize_pad: desc_dev must be [B, 4]")
+            desc_dev.copy_(desc_host, non_blocking=True)
+    if out is None:
+        out = torch.empty((B, 3, ph, pw), dtype=torch.float32, device=src.device,
+                          memory_format=torch.channels_last)
+    else:
+        if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, 3, ph, pw) \
+                or not out.permute(0, 2, 3, 1).is_contiguous():
+            raise MoEKernelError(f"resize_pad: out must be a channels-last fp32 GPU tensor [{B}, 3, {ph}, {pw}]")
+    rc = lib().rtdetr_resize_pad_u8(_ptr(src), _ptr(desc_dev), B, oh, ow, ph, pw, _ptr(out), _stream())
+    _check(rc, "rtdetr_resize_pad_u8")
+    return out
 
 
 def grouped_gemm_wgrad(x, y, offsets, G, want_colsum=True, out_dtype=torch.float32):

@@ -770,3 +770,178 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
             (save_dir / "context_report.json").write_text(json.dumps(report, indent=1))
     return DetMetrics(results_dict=_results_dict(box), box=box, speed=speed, model=ModelHandle(model),
                       save_dir=save_dir, moe=_moe_stats(model), context=report)
+
+
+# ---------------------------------------------------------------------------
+# prediction on image files
+# ---------------------------------------------------------------------------
+@dataclass
+class Prediction:
+    """One image's detections: rows with score >= conf, at most max_det, best
+    first; boxes fp32 [n, 4] xyxy in source pixels, clipped to the frame."""
+    path: str
+    size: tuple  # (w, h) of the source frame
+    ctx: int
+    boxes: torch.Tensor
+    scores: torch.Tensor
+    labels: torch.Tensor
+
+
+@dataclass
+class PredictResults:
+    predictions: list
+    speed: dict
+    save_dir: Path | None
+    model: ModelHandle | None
+
+
+def _image_id(path):
+    stem = Path(path).stem
+    return int(stem) if stem.isdigit() else stem
+
+
+def coco_results(predictions) -> list:
+    """COCO results rows as Ultralytics' save_json writes them: image_id (the
+    stem, an int when numeric), file_name, category_id, bbox xywh in source
+    pixels to 3 decimals, score to 5."""
+    rows = []
+    for p in predictions:
+        for box, s, c in zip(p.boxes.tolist(), p.scores.tolist(), p.labels.tolist()):
+            x1, y1, x2, y2 = box
+            rows.append({"image_id": _image_id(p.path), "file_name": Path(p.path).name, "category_id": int(c),
+                         "bbox": [round(x1, 3), round(y1, 3), round(x2 - x1, 3), round(y2 - y1, 3)],
+                         "score": round(s, 5)})
+    return rows
+
+
+def _save_overlay(pred: Prediction, out_path: Path):
+    from PIL import Image, ImageDraw
+
+    im = Image.open(pred.path).convert("RGB")
+    draw = ImageDraw.Draw(im)
+    for (x1, y1, x2, y2), s, c in zip(pred.boxes.tolist(), pred.scores.tolist(), pred.labels.tolist()):
+        draw.rectangle([x1, y1, max(x2, x1), max(y2, y1)], outline=(255, 64, 64), width=max(1, im.width // 640))
+        draw.text((x1 + 2, y1 + 2), f"{int(c)} {s:.2f}", fill=(255, 255, 0))
+    im.save(out_path)
+
+
+def predict_resize_on_gpu(dev: torch.device) -> bool:
+    """Whether predict resizes on the GPU (rtdetr_resize_pad_u8): on a GPU
+    device unless MOE_PREDICT_RESIZE=0 asks for the loader's host path."""
+    return dev.type == "cuda" and os.environ.get("MOE_PREDICT_RESIZE", "1") != "0"
+
+
+@torch.no_grad()
+def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
+            workers=4, project=None, name=None, save_json=True, save_img=False) -> PredictResults:
+    """Detect on image files of any size.  ``source``: a directory, a glob, a
+    list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
+    batch is one upload of the decoded uint8 frames and ONE HIP launch
+    (rtdetr_resize_pad_u8: antialiased bilinear resize to ``imgsz``, / 255,
+    padding to a multiple of 32, channels-last), the graph-replayed EvalForward
+    (a partial last batch is filled with empty slots, so one graph serves the
+    run), postprocess_batched with each image's size mapped to its source
+    frame, and one copy back.  With device="cpu" or MOE_PREDICT_RESIZE=0 the
+    frames take the datasets' host path instead (PIL resize + _padded_image).
+    ``workers`` threads decode (and, on the host path, resize) ahead of the GPU
+    (preprocess.iter_batches); 0 reads in the calling thread.
+    ``.speed``: ms per image, wall clock as ``_evaluate`` takes it (graph
+    capture excluded): "preprocess" from asking the loader for the batch to the
+    model's input standing on the device (decode, upload, the resize launch, or
+    the host resize), "inference" the forward, "postprocess" the boxes back on
+    the host.  Files, under ``project/name`` when both are given:
+    predictions.json (``save_json``; COCO results) and ``save_img`` overlays."""
+    from .preprocess import FrameSource, HostCollate, PackCollate, iter_batches, mapped_sizes, padded_hw
+
+    devices = parse_device(device)
+    dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
+    on_gpu = dev.type == "cuda"
+    if on_gpu:
+        torch.cuda.set_device(dev)
+        from ..moe import _lib
+
+        _lib.lib()
+    batch, max_det = int(batch), int(max_det)
+    if batch < 1 or max_det < 1:
+        raise ValueError(f"batch {batch} and max_det {max_det} must be >= 1")
+    model = load_model(weights, dev)
+    if on_gpu:
+        model = model.to(memory_format=torch.channels_last)
+    was_training = model.training
+    model.eval()
+    out_hw, pad_hw = padded_hw(imgsz)
+    gpu_resize = predict_resize_on_gpu(dev)
+    ds = FrameSource(source, contexts=contexts)
+    collate = PackCollate(out_hw, pin=True) if gpu_resize else HostCollate(out_hw, pad_hw)
+    fwd = EvalForward(model)
+    from ..moe.context import MISSING_ID
+
+    preds = []
+    t_pre = t_inf = t_post = 0.0
+    it = iter_batches(ds, batch, workers, collate)  # decoding threads (no processes forked under a GPU context)
+    while True:
+        t0 = time.perf_counter()
+        try:
+            bt = next(it)
+        except StopIteration:
+            break
+        n = len(bt["paths"])
+        fill = batch - n if on_gpu else 0  # empty slots: the captured batch size serves a partial last batch
+        ctx = bt["ctx"]
+        if fill:
+            ctx = torch.cat([ctx, torch.full((fill,), MISSING_ID, dtype=torch.int32)])
+        ctx = ctx.to(dev)
+        t_cap = 0.0
+        if gpu_resize:
+            desc = bt["desc"]
+            if fill:
+                desc = torch.cat([desc, torch.zeros((fill, 4), dtype=torch.int64)])
+            images = _lib.resize_pad(bt["buf"].to(dev, non_blocking=True), desc, out_hw, pad_hw)
+        else:
+            images = bt["images"]
+            if fill:
+                images = torch.cat([images, images.new_zeros((fill,) + tuple(images.shape[1:]))])
+            images = images.to(dev, non_blocking=True)
+            if on_gpu:
+                images = images.contiguous(memory_format=torch.channels_last)
+        if on_gpu:
+            tc = time.perf_counter()
+            fwd.prepare(images, ctx)  # first batch: graph capture, untimed
+            t_cap = time.perf_counter() - tc
+            torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        out = fwd(images, ctx)
+        if on_gpu:
+            torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        sizes = bt["sizes"]
+        mapped = mapped_sizes(sizes, out_hw, pad_hw) + [(1.0, 1.0)] * fill
+        boxes, scores, labels = model.postprocess_batched(out, mapped, num_top=max_det)
+        lim = torch.tensor([[w, h, w, h] for w, h in sizes] + [[1.0] * 4] * fill, dtype=boxes.dtype,
+                           device=boxes.device)
+        boxes = torch.minimum(boxes.clamp(min=0.0), lim[:, None, :])
+        packed = torch.cat([boxes, scores[..., None], labels[..., None].to(boxes.dtype)], -1).cpu()  # one copy back
+        for i in range(n):
+            row = packed[i]
+            keep = row[:, 4] >= conf  # postprocess_batched's rows are already best first
+            preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
+                                    boxes=row[keep, :4].contiguous(), scores=row[keep, 4].contiguous(),
+                                    labels=row[keep, 5].to(torch.int64)))
+        t3 = time.perf_counter()
+        t_pre += t1 - t0 - t_cap
+        t_inf += t2 - t1
+        t_post += t3 - t2
+    if was_training:
+        model.train()
+    n_img = max(len(preds), 1)
+    speed = {"preprocess": 1e3 * t_pre / n_img, "inference": 1e3 * t_inf / n_img,
+             "postprocess": 1e3 * t_post / n_img}
+    save_dir = Path(project) / name if project and name else None
+    if save_dir is not None:
+        save_dir.mkdir(parents=True, exist_ok=True)
+        if save_json:
+            (save_dir / "predictions.json").write_text(json.dumps(coco_results(preds)))
+        if save_img:
+            for p in preds:
+                _save_overlay(p, save_dir / Path(p.path).name)
+    return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=ModelHandle(model))

@@ -96,6 +96,19 @@ int main() {
   expect_error("route_stats n_ctx=0", moe_route_stats(i32, f32, i32, f32, i32, 0, 6, 12, 8, 2, i64, s));
   expect_error("route_stats ctx=NULL n_ctx=6", moe_route_stats(i32, f32, i32, f32, nullptr, 6, 6, 12, 8, 2, i64, s));
   expect_error("route_stats stats=NULL", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 8, 2, nullptr, s));
+  expect_error("resize_pad src=NULL", rtdetr_resize_pad_u8(nullptr, i64, 1, 32, 32, 32, 32, f32, s));
+  expect_error("resize_pad desc=NULL", rtdetr_resize_pad_u8(u8, nullptr, 1, 32, 32, 32, 32, f32, s));
+  expect_error("resize_pad dst=NULL", rtdetr_resize_pad_u8(u8, i64, 1, 32, 32, 32, 32, nullptr, s));
+  expect_error("resize_pad out_h=0", rtdetr_resize_pad_u8(u8, i64, 1, 0, 32, 32, 32, f32, s));
+  expect_error("resize_pad out_w=-1", rtdetr_resize_pad_u8(u8, i64, 1, 32, -1, 32, 32, f32, s));
+  expect_error("resize_pad pad_h<out_h", rtdetr_resize_pad_u8(u8, i64, 1, 33, 32, 32, 32, f32, s));
+  expect_error("resize_pad pad_w<out_w", rtdetr_resize_pad_u8(u8, i64, 1, 32, 33, 32, 32, f32, s));
+  expect_error("resize_pad B=-1", rtdetr_resize_pad_u8(u8, i64, -1, 32, 32, 32, 32, f32, s));
+  ++g_n;
+  if (rtdetr_resize_pad_u8(nullptr, nullptr, 0, 32, 32, 32, 32, nullptr, s) != 0) {  // B == 0: success, no launch
+    std::printf("FAIL resize_pad B=0 must succeed\n");
+    ++g_fail;
+  }
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

@@ -1,0 +1,90 @@
+"""predict() on synthetic ZOD-sized frames: the GPU resize against the host path.
+
+Writes N (default 64) 3848 x 2168 JPEGs from a seed into a temporary directory,
+then runs engine.predict on them with MOE_PREDICT_RESIZE=1 and =0 alternately
+(default three times each, one process) and prints one JSON line per run with
+``speed`` (ms per image) and a last line with the medians and spreads.
+
+  python tools/predict_bench.py [--model rtdetr-r50-moe8-top2] [--n 64] [--batch 16] [--rounds 3] [--workers 4]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "multimodal-moe_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def write_frames(d: Path, n: int, seed: int = 0, hw=(2168, 3848)):
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    h, w = hw
+    for i in range(n):
+        base = rng.integers(0, 256, (h // 16 + 1, w // 16 + 1, 3), dtype=np.uint8)
+        im = Image.fromarray(base).resize((w, h), Image.BILINEAR)  # smooth content: JPEG sizes like a camera frame's
+        im.save(d / f"{i:06d}.jpg", quality=90)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="rtdetr-r50-moe8-top2")
+    ap.add_argument("--n", type=int, default=64)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--device", default="0")
+    a = ap.parse_args(argv)
+    from src.rtdetr_moe import engine
+
+    with tempfile.TemporaryDirectory(prefix="predict_bench_") as td:
+        d = Path(td)
+        t0 = time.perf_counter()
+        write_frames(d, a.n)
+        print(json.dumps({"frames": a.n, "write_s": round(time.perf_counter() - t0, 2)}), flush=True)
+        from PIL import Image
+
+        from src.rtdetr_moe.preprocess import host_resize
+
+        dec, rsz = [], []
+        for p in sorted(d.glob("*.jpg"))[:8]:  # what one loader worker spends per frame
+            t0 = time.perf_counter()
+            arr = np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8)
+            t1 = time.perf_counter()
+            host_resize(arr, (704, 1248), (704, 1248))
+            dec.append(1e3 * (t1 - t0))
+            rsz.append(1e3 * (time.perf_counter() - t1))
+        print(json.dumps({"jpeg_decode_ms_per_frame_one_core": round(statistics.median(dec), 2),
+                          "host_resize_ms_per_frame_one_core": round(statistics.median(rsz), 2)}), flush=True)
+        runs = {"1": [], "0": []}
+        for r in range(a.rounds):
+            for switch in ("1", "0"):
+                os.environ["MOE_PREDICT_RESIZE"] = switch
+                torch.manual_seed(0)
+                t0 = time.perf_counter()
+                res = engine.predict(a.model, d, batch=a.batch, device=a.device, conf=0.25, workers=a.workers)
+                line = {"round": r, "MOE_PREDICT_RESIZE": switch, "images": len(res.predictions),
+                        "wall_s": round(time.perf_counter() - t0, 2),
+                        **{k: round(v, 3) for k, v in res.speed.items()}}
+                print(json.dumps(line), flush=True)
+                runs[switch].append(res.speed)
+        out = {"model": a.model, "batch": a.batch, "workers": a.workers}
+        for switch, name in (("1", "gpu_resize"), ("0", "host_resize")):
+            for k in ("preprocess", "inference", "postprocess"):
+                v = [s[k] for s in runs[switch]]
+                out[f"{name}/{k}"] = [round(statistics.median(v), 3), round(min(v), 3), round(max(v), 3)]
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
