@@ -811,6 +811,39 @@ int rtdetr_eval_match(const float* boxes, const float* scores, const int32_t* la
 int rtdetr_resize_pad_u8(const uint8_t* src, const long long* desc, int B, int out_h, int out_w, int pad_h,
                          int pad_w, float* dst, hipStream_t stream);
 
+/* Tiled prediction (engine.predict(tiles=...), merge.py): the detections of a
+ * frame's passes -- the full frame and its tiles -- merged by a greedy,
+ * score-ordered suppression, one launch per batch, one workgroup per image
+ * (merge.merge_reference on the host, restated so that the decisions are the
+ * same bit for bit).
+ * boxes fp32 [B][N][4] xyxy (16-byte aligned, finite), scores fp32 [B][N],
+ * labels int32 [B][N]; n_valid int32 [B], clamped to [0, N]; NULL means N.
+ * Candidate i of image b takes part if i < n_valid[b] and scores[i] >= conf (a
+ * NaN score never does).  The candidates are visited in np.argsort(-scores,
+ * kind="stable") order: descending score, equal scores by lower index.  A
+ * visited candidate is suppressed if some already kept j has the same label
+ * (or class_agnostic != 0) and inter > thr * den; otherwise it is kept; the
+ * walk stops after max_det kept.  fp32, every operation rounded on its own, no
+ * division, no FMA contraction:
+ *   area = max(x2 - x1, 0) * max(y2 - y1, 0)
+ *   iw = max(min(x2_i, x2_j) - max(x1_i, x1_j), 0), ih likewise; inter = iw * ih
+ *   den = (area_i + area_j) - inter   metric 0, "iou"
+ *   den = min(area_i, area_j)         metric 1, "ios": intersection over the smaller box
+ * so a zero-area box never suppresses anything and is never suppressed.
+ * Outputs, best first: out_boxes fp32 [B][max_det][4] (16-byte aligned),
+ * out_scores fp32, out_labels int32 and out_src int32 [B][max_det] (the
+ * candidate index of each kept row), count int32 [B] (the kept rows).  Every
+ * output element is written -- rows past count[b] get zeros, and -1 in out_src
+ * -- so the buffers can be reused: no memset, no atomics on global memory, no
+ * workspace.
+ * N <= 4096, max_det in [1, 1024], B <= 1024 (60.2 KiB of LDS at the largest);
+ * conf and thr not NaN.  A bad argument returns non-zero before any launch.
+ * B == 0 returns 0 without a launch; N == 0 writes the empty outputs. */
+int rtdetr_nms_merge(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                     int B, int N, float conf, float thr, int metric, int class_agnostic, int max_det,
+                     float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_src,
+                     int32_t* count, hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -1132,7 +1165,8 @@ int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t*
  * 9 Hungarian matching, 10 fp8 grouped GEMM, 11 dense linear weight gradients,
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
  * context-bias gradients, 15 training batch augmentation, 16 validation
- * matching, 17 routing statistics, 18 inference preprocessing (resize).
+ * matching, 17 routing statistics, 18 inference preprocessing (resize),
+ * 19 tiled prediction's merge.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1154,7 +1188,8 @@ enum moe_prof_kind {
   MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
   MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match) */
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
-  MOE_PROF_RESIZE = 18     /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
+  MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
+  MOE_PROF_MERGE = 19      /* tiled prediction: the passes' detections merged (rtdetr_nms_merge) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

@@ -10,6 +10,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --eval-match  the validation matcher against the host loop
   python multimodal-moe_amd/kbench.py --route-stats the routing-statistics kernel against its torch reference
   python multimodal-moe_amd/kbench.py --resize      the inference resize kernel against the host resize it replaces
+  python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -454,6 +455,103 @@ def resize_leg(reps, rounds):
         print(json.dumps(line), flush=True)
 
 
+def nms_merge_leg(reps, rounds):
+    """rtdetr_nms_merge at tiled prediction's shape (B 16 frames, N 1500
+    candidates: the full frame and a 2 x 2 grid at k 300; max_det 300; "ios" and
+    "iou" at 0.5, conf 0.25) against merge.merge_reference on the host, same
+    process, same candidates (checked equal first).  The candidates are
+    clustered: N // 6 objects per frame, each several times, boxes of
+    pedestrian shape jittered by a few pixels, scores on a 1/64 grid, two
+    labels.  kernel_us: the kernel's dispatch-stamped execution time per launch;
+    device_path_ms: launch + one packed copy back, wall clock; host_merge_ms:
+    the reference loop over the 16 frames on arrays already on the host, wall
+    clock.  forward_replay_us: one EvalForward graph replay at batch 16
+    (rtdetr-r50-moe8-top2, 704 x 1248; event pair around the replay).  Median,
+    min and max over the rounds, the sides interleaved in each round."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import engine
+    from src.rtdetr_moe.merge import merge_reference
+    from src.rtdetr_moe.model import RTDETRMoE
+
+    B, N, max_det, conf, thr = 16, 1500, 300, 0.25, 0.5
+    rng = np.random.default_rng(0)
+    M = N // 6
+    cx, cy = rng.uniform(100, 3748, (B, M)), rng.uniform(120, 2048, (B, M))
+    h = rng.uniform(40, 200, (B, M))
+    which = rng.integers(0, M, (B, N))
+    take = lambda a: np.take_along_axis(a, which, 1)  # noqa: E731
+    jit = rng.normal(0.0, 3.0, (B, N, 4))
+    x1, y1 = take(cx) - 0.2 * take(h) + jit[..., 0], take(cy) - 0.5 * take(h) + jit[..., 1]
+    x2, y2 = take(cx) + 0.2 * take(h) + jit[..., 2], y1 + take(h) * rng.uniform(0.6, 1.0, (B, N)) + jit[..., 3]
+    boxes = np.stack([x1, y1, x2, y2], -1).astype(np.float32)
+    scores = (rng.integers(0, 64, (B, N)) / 64.0).astype(np.float32)
+    labels = rng.integers(0, 2, (B, N)).astype(np.int32)
+    db, ds, dl = (torch.from_numpy(a).cuda() for a in (boxes, scores, labels))
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    def wall(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return statistics.median(ts)
+
+    for metric in ("ios", "iou"):
+        out = tuple(t.cpu() for t in L.nms_merge(db, ds, dl, None, conf, thr, metric, max_det))
+        want = [merge_reference(boxes[b], scores[b], labels[b], None, conf, thr, metric, max_det) for b in range(B)]
+        for b, k in enumerate(want):
+            if int(out[4][b]) != len(k) or out[3][b, :len(k)].tolist() != k.tolist():
+                raise SystemExit(f"nms_merge differs from merge_reference ({metric}, image {b})")
+
+        def device_path():
+            ob, osc, ol, osrc, _ = L.nms_merge(db, ds, dl, None, conf, thr, metric, max_det)
+            torch.cat([ob, osc[..., None], ol[..., None].float(), osrc[..., None].float()], -1).cpu()
+
+        def host_path():
+            for b in range(B):
+                merge_reference(boxes[b], scores[b], labels[b], None, conf, thr, metric, max_det)
+
+        res = {"kernel_us": [], "device_path_ms": [], "host_merge_ms": [], "forward_replay_us": []}
+        for _ in range(rounds):
+            res["kernel_us"].append(timed(lambda: L.nms_merge(db, ds, dl, None, conf, thr, metric, max_det), reps))
+            res["device_path_ms"].append(wall(device_path, max(3, reps // 5)))
+            res["host_merge_ms"].append(wall(host_path, 3))
+            res["forward_replay_us"].append(replay_us())
+        line = {"kernel": "rtdetr_nms_merge", "shape": f"B{B} N{N} max_det{max_det} {metric} thr{thr} conf{conf}",
+                "take_part": int((scores >= conf).sum()), "kept": int(sum(len(k) for k in want))}
+        for k, v in res.items():
+            line[k] = round(statistics.median(v), 3)
+            line[k + "_min"] = round(min(v), 3)
+            line[k + "_max"] = round(max(v), 3)
+        line["host_over_kernel"] = round(1e3 * line["host_merge_ms"] / line["kernel_us"], 1)
+        line["kernel_share_of_forward"] = round(line["kernel_us"] / line["forward_replay_us"], 4)
+        print(json.dumps(line), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -505,6 +603,9 @@ def main():
     ap.add_argument("--resize", action="store_true",
                     help="time rtdetr_resize_pad_u8 (16 ZOD-sized frames, and identity scale) against the host "
                          "resize it replaces and exit")
+    ap.add_argument("--nms-merge", action="store_true",
+                    help="time rtdetr_nms_merge (B 16, N 1500, max_det 300) against merge.merge_reference on the host "
+                         "and one EvalForward replay, and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -538,6 +639,9 @@ def main():
         return
     if a.resize:
         resize_leg(a.reps, a.rounds)
+        return
+    if a.nms_merge:
+        nms_merge_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

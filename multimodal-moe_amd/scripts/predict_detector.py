@@ -3,7 +3,9 @@ architecture spec) and write predictions.json (COCO results format) -- and,
 with --save-img, overlays -- under RUNS_DIR/rtdetr/<run-name>_predict.
 
 Same flag style as scripts/eval_detector.py.  --source is a directory, a glob,
-one image file or a dataset yaml; frames may have any size.
+one image file or a dataset yaml; frames may have any size.  --tiles 2x2 adds
+sliced inference: every frame is also detected on a grid of crops and the passes
+are merged (engine.predict).
 """
 from __future__ import annotations
 
@@ -32,6 +34,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--save-img", action="store_true", help="also write the frames with their boxes drawn")
     ap.add_argument("--run-name", type=str, default="rtdetr")
+    ap.add_argument("--tiles", type=str, default=None,
+                    help="ROWSxCOLS, e.g. 2x2: also detect on an overlapping grid of crops of every frame and merge")
+    ap.add_argument("--tile-overlap", type=float, default=0.2, help="overlap of neighbouring tiles, in [0, 0.5]")
+    ap.add_argument("--merge-iou", type=float, default=0.5, help="the merge's suppression threshold")
+    ap.add_argument("--merge-metric", type=str, default="ios", choices=("ios", "iou"),
+                    help="ios: intersection over the smaller box; iou: over the union")
+    ap.add_argument("--class-agnostic", action="store_true", help="merge across labels")
     return ap.parse_args(argv)
 
 
@@ -41,7 +50,9 @@ def main(argv=None) -> None:
 
     res = engine.predict(a.weights, a.source, imgsz=(a.img_h, a.img_w), batch=a.batch, device=a.device, conf=a.conf,
                          max_det=a.max_det, contexts=a.context, workers=a.workers, project=str(RUNS_DIR / "rtdetr"),
-                         name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img)
+                         name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
+                         tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
+                         class_agnostic=a.class_agnostic)
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
     print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))

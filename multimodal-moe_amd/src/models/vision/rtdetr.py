@@ -118,15 +118,24 @@ def predict_rtdetr_detector(
     conf: float = 0.25,
     project: str | None = None,
     name: str | None = None,
+    tiles=None,
+    tile_overlap: float = 0.2,
+    merge_iou: float = 0.5,
+    merge_metric: str = "ios",
+    class_agnostic: bool = False,
 ):
     """Detect on image files (a directory, a glob, a list of paths or a dataset
     yaml) of any size; returns a results object with ``.predictions`` (per
     image: path, source size, context id, boxes xyxy in source pixels, scores,
     labels), ``.speed`` (ms per image), ``.save_dir`` (predictions.json in COCO
-    results format when ``project`` and ``name`` are given) and ``.model``."""
+    results format when ``project`` and ``name`` are given) and ``.model``.
+    ``tiles=(rows, cols)`` (or "RxC") adds sliced inference: every frame is
+    also detected on an overlapping grid of crops and the passes are merged
+    (engine.predict); ``.predictions[i].source`` then names each row's pass."""
     eng = _engine()
     return eng.predict(_check_model_name(weights_path), source, imgsz=_imgsz(imgsz), batch=batch, device=device,
-                       conf=conf, project=project, name=name)
+                       conf=conf, project=project, name=name, tiles=tiles, tile_overlap=tile_overlap,
+                       merge_iou=merge_iou, merge_metric=merge_metric, class_agnostic=class_agnostic)
 
 
 def save_rtdetr_metrics_json(metrics, out_path: str | Path) -> Path:

@@ -117,6 +117,7 @@ SIGNATURES = {
     "rtdetr_hungarian_match": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_eval_match": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "rtdetr_resize_pad_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "rtdetr_nms_merge": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -209,7 +210,7 @@ def lib() -> ctypes.CDLL:
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
               11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
-              16: "eval_match", 17: "route_stats", 18: "resize"}
+              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -905,6 +906,55 @@ def resize_pad(src, desc_host, out_hw, pad_hw, out=None, desc_dev=None):
             raise MoEKernelError(f"resize_pad: out must be a channels-last fp32 GPU tensor [{B}, 3, {ph}, {pw}]")
     rc = lib().rtdetr_resize_pad_u8(_ptr(src), _ptr(desc_dev), B, oh, ow, ph, pw, _ptr(out), _stream())
     _check(rc, "rtdetr_resize_pad_u8")
+    return out
+
+
+NMS_MERGE_MAX_N, NMS_MERGE_MAX_DET, NMS_MERGE_MAX_B = 4096, 1024, 1024  # rtdetr_nms_merge's limits
+NMS_METRICS = {"iou": 0, "ios": 1}
+
+
+def nms_merge(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=300, class_agnostic=False, out=None):
+    """The merge of tiled prediction, one launch for the batch (rtdetr_nms_merge:
+    merge.merge_reference per image, bit for bit).  boxes fp32 [B, N, 4] xyxy,
+    scores fp32 [B, N], labels int32 [B, N], n_valid int32 [B] or None (= N).
+    -> (out_boxes fp32 [B, max_det, 4], out_scores fp32, out_labels int32,
+    out_src int32 [B, max_det], count int32 [B]), best first, every element
+    written (rows past count: zeros, -1 in out_src).  ``out``: that tuple of
+    tensors to write into instead of new ones."""
+    _need(boxes, torch.float32, "boxes")
+    _need(scores, torch.float32, "scores")
+    _need(labels, torch.int32, "labels")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4:
+        raise MoEKernelError("nms_merge: boxes must be [B, N, 4]")
+    B, N, _ = (int(v) for v in boxes.shape)
+    if tuple(scores.shape) != (B, N) or tuple(labels.shape) != (B, N):
+        raise MoEKernelError("nms_merge: scores / labels must be [B, N]")
+    if n_valid is not None:
+        _need(n_valid, torch.int32, "n_valid")
+        if tuple(n_valid.shape) != (B,):
+            raise MoEKernelError("nms_merge: n_valid must be [B]")
+    if metric not in NMS_METRICS:
+        raise MoEKernelError(f"nms_merge: metric must be one of {sorted(NMS_METRICS)}, got {metric!r}")
+    max_det = int(max_det)
+    dev = boxes.device
+    shapes = ((B, max(max_det, 0), 4), (B, max(max_det, 0)), (B, max(max_det, 0)), (B, max(max_det, 0)), (B,))
+    dtypes = (torch.float32, torch.float32, torch.int32, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        if len(out) != 5:
+            raise MoEKernelError("nms_merge: out must be (boxes, scores, labels, src, count)")
+        for t, s, d, name in zip(out, shapes, dtypes, ("out_boxes", "out_scores", "out_labels", "out_src", "count")):
+            _need(t, d, name)
+            if tuple(t.shape) != s:
+                raise MoEKernelError(f"nms_merge: {name} must be {s}, got {tuple(t.shape)}")
+    tensors = [boxes, scores, labels, *out] + ([n_valid] if n_valid is not None else [])
+    if any(t.device != dev for t in tensors):
+        raise MoEKernelError("nms_merge: all tensors must be on one device")
+    rc = lib().rtdetr_nms_merge(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), B, N, float(conf), float(thr),
+                                NMS_METRICS[metric], int(bool(class_agnostic)), max_det, *(_ptr(t) for t in out),
+                                _stream())
+    _check(rc, "rtdetr_nms_merge")
     return out
 
 

@@ -785,6 +785,8 @@ class Prediction:
     boxes: torch.Tensor
     scores: torch.Tensor
     labels: torch.Tensor
+    # tiled prediction: the pass each row came from, int64 [n]: 0 the full frame, 1 + t tile t; None without tiles
+    source: torch.Tensor | None = None
 
 
 @dataclass
@@ -831,9 +833,17 @@ def predict_resize_on_gpu(dev: torch.device) -> bool:
     return dev.type == "cuda" and os.environ.get("MOE_PREDICT_RESIZE", "1") != "0"
 
 
+def predict_merge_on_gpu(dev: torch.device) -> bool:
+    """Whether tiled prediction merges its passes on the GPU (rtdetr_nms_merge):
+    on a GPU device unless MOE_PREDICT_MERGE=0 asks for merge.merge_reference
+    on the copied-back candidates."""
+    return dev.type == "cuda" and os.environ.get("MOE_PREDICT_MERGE", "1") != "0"
+
+
 @torch.no_grad()
 def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
-            workers=4, project=None, name=None, save_json=True, save_img=False) -> PredictResults:
+            workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
+            merge_iou=0.5, merge_metric="ios", class_agnostic=False) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -850,9 +860,36 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     model's input standing on the device (decode, upload, the resize launch, or
     the host resize), "inference" the forward, "postprocess" the boxes back on
     the host.  Files, under ``project/name`` when both are given:
-    predictions.json (``save_json``; COCO results) and ``save_img`` overlays."""
-    from .preprocess import FrameSource, HostCollate, PackCollate, iter_batches, mapped_sizes, padded_hw
+    predictions.json (``save_json``; COCO results) and ``save_img`` overlays.
+    ``tiles=(rows, cols)``: sliced inference.  Each frame is also detected on
+    an overlapping grid of crops (merge.tile_windows at ``tile_overlap``), which
+    reach the model at up to rows x cols times the full frame's resolution, and
+    the passes are merged (merge.merge_reference's rule with ``conf``,
+    ``merge_iou``, ``merge_metric`` "ios" / "iou", ``class_agnostic`` and
+    ``max_det``).  On a GPU the tiles are further rows of the resize kernel's
+    descriptor table into the buffer already uploaded -- cut into chunks of
+    ``batch`` slots, each one resize launch, one replay of the same captured
+    graph and one postprocess_batched, boxes shifted by the window's origin and
+    clipped to the window -- and the merge of a batch's [B, (1 + rows cols) k,
+    4] candidates (the full frame first, then the tiles row-major; k =
+    min(max_det, queries x classes), at most 4096 in all) is ONE HIP launch
+    (rtdetr_nms_merge; MOE_PREDICT_MERGE=0: merge_reference on the host) and
+    one packed copy back.  On the CPU, or with MOE_PREDICT_RESIZE=0, the tiles
+    are cropped and resized on the host.  ``Prediction.source`` then holds the
+    pass of every row and ``.speed`` gains "passes" (1 + rows cols; the three
+    timings include every pass, the merge under "postprocess").  Without
+    ``tiles`` nothing of this runs."""
+    from .merge import MERGE_MAX_DET, MERGE_MAX_N, METRICS, merge_reference, parse_tiles, tile_windows
+    from .preprocess import (FrameSource, HostCollate, PackCollate, TileHostCollate, TilePackCollate, iter_batches,
+                             mapped_sizes, padded_hw)
 
+    tiles = parse_tiles(tiles)
+    if tiles is not None:
+        tile_windows(2 * tiles[1], 2 * tiles[0], tiles, tile_overlap)  # the overlap's ValueError, before any work
+        if merge_metric not in METRICS:
+            raise ValueError(f"merge_metric must be one of {sorted(METRICS)}, got {merge_metric!r}")
+        if not 0.0 <= float(merge_iou) <= 1.0:
+            raise ValueError(f"merge_iou must be in [0, 1], got {merge_iou}")
     devices = parse_device(device)
     dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
     on_gpu = dev.type == "cuda"
@@ -871,8 +908,20 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     model.eval()
     out_hw, pad_hw = padded_hw(imgsz)
     gpu_resize = predict_resize_on_gpu(dev)
+    n_tiles = 0
+    if tiles is not None:
+        n_tiles = tiles[0] * tiles[1]
+        n_cand = (1 + n_tiles) * min(max_det, model.decoder.num_queries * model.num_classes)
+        if n_cand > MERGE_MAX_N or max_det > MERGE_MAX_DET:
+            raise ValueError(f"tiles {tiles[0]}x{tiles[1]} with max_det {max_det} is {n_cand} candidates per frame: "
+                             f"the merge takes at most {MERGE_MAX_N} candidates and max_det {MERGE_MAX_DET}")
+    gpu_merge = predict_merge_on_gpu(dev)
     ds = FrameSource(source, contexts=contexts)
-    collate = PackCollate(out_hw, pin=True) if gpu_resize else HostCollate(out_hw, pad_hw)
+    if tiles is None:
+        collate = PackCollate(out_hw, pin=True) if gpu_resize else HostCollate(out_hw, pad_hw)
+    else:
+        collate = TilePackCollate(out_hw, tiles, tile_overlap, pin=True) if gpu_resize \
+            else TileHostCollate(out_hw, pad_hw, tiles, tile_overlap)
     fwd = EvalForward(model)
     from ..moe.context import MISSING_ID
 
@@ -896,7 +945,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
             desc = bt["desc"]
             if fill:
                 desc = torch.cat([desc, torch.zeros((fill, 4), dtype=torch.int64)])
-            images = _lib.resize_pad(bt["buf"].to(dev, non_blocking=True), desc, out_hw, pad_hw)
+            src = bt["buf"].to(dev, non_blocking=True)  # the one upload; the tile passes read it again
+            images = _lib.resize_pad(src, desc, out_hw, pad_hw)
         else:
             images = bt["images"]
             if fill:
@@ -920,13 +970,84 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         lim = torch.tensor([[w, h, w, h] for w, h in sizes] + [[1.0] * 4] * fill, dtype=boxes.dtype,
                            device=boxes.device)
         boxes = torch.minimum(boxes.clamp(min=0.0), lim[:, None, :])
-        packed = torch.cat([boxes, scores[..., None], labels[..., None].to(boxes.dtype)], -1).cpu()  # one copy back
-        for i in range(n):
-            row = packed[i]
-            keep = row[:, 4] >= conf  # postprocess_batched's rows are already best first
-            preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
-                                    boxes=row[keep, :4].contiguous(), scores=row[keep, 4].contiguous(),
-                                    labels=row[keep, 5].to(torch.int64)))
+        if tiles is not None:
+            # the tile passes: n n_tiles slots, frame-major, in chunks of ``batch`` on the captured graph
+            wins = [w for frame_wins in bt["windows"] for w in frame_wins]
+            slot_ctx = bt["ctx"].repeat_interleave(n_tiles)
+            tb, ts, tl = [], [], []
+            t_tile = [0.0, 0.0]  # preprocess, inference of the tile passes
+            for s in range(0, len(wins), batch):
+                ta = time.perf_counter()
+                w = wins[s:s + batch]
+                cfill = batch - len(w) if on_gpu else 0
+                cctx = slot_ctx[s:s + batch]
+                if cfill:
+                    cctx = torch.cat([cctx, torch.full((cfill,), MISSING_ID, dtype=torch.int32)])
+                cctx = cctx.to(dev)
+                if gpu_resize:
+                    tdesc = bt["tile_desc"][s:s + batch]
+                    if cfill:
+                        tdesc = torch.cat([tdesc, torch.zeros((cfill, 4), dtype=torch.int64)])
+                    timg = _lib.resize_pad(src, tdesc, out_hw, pad_hw)
+                else:
+                    timg = bt["tile_images"][s:s + batch]
+                    if cfill:
+                        timg = torch.cat([timg, timg.new_zeros((cfill,) + tuple(timg.shape[1:]))])
+                    timg = timg.to(dev, non_blocking=True)
+                    if on_gpu:
+                        timg = timg.contiguous(memory_format=torch.channels_last)
+                if on_gpu:
+                    torch.cuda.synchronize()
+                tb0 = time.perf_counter()
+                tout = fwd(timg, cctx)
+                if on_gpu:
+                    torch.cuda.synchronize()
+                t_tile[0] += tb0 - ta
+                t_tile[1] += time.perf_counter() - tb0
+                tmapped = mapped_sizes([(tw, th) for _, _, tw, th in w], out_hw, pad_hw) + [(1.0, 1.0)] * cfill
+                b_, s_, l_ = model.postprocess_batched(tout, tmapped, num_top=max_det)
+                lo = torch.tensor([[x0, y0, x0, y0] for x0, y0, _, _ in w] + [[0.0] * 4] * cfill, dtype=b_.dtype,
+                                  device=b_.device)
+                hi = torch.tensor([[x0 + tw, y0 + th, x0 + tw, y0 + th] for x0, y0, tw, th in w]
+                                  + [[1.0] * 4] * cfill, dtype=b_.dtype, device=b_.device)
+                # shifted by the window's origin, clipped to the window
+                b_ = torch.minimum(torch.maximum(b_ + lo[:, None, :], lo[:, None, :]), hi[:, None, :])
+                tb.append(b_[:len(w)])
+                ts.append(s_[:len(w)])
+                tl.append(l_[:len(w)])
+            k = boxes.shape[1]
+            # candidates per frame: the full frame's k rows, then each tile's, row-major
+            cb = torch.cat([boxes[:n], torch.cat(tb).reshape(n, n_tiles * k, 4)], 1)
+            cs = torch.cat([scores[:n], torch.cat(ts).reshape(n, n_tiles * k)], 1)
+            cl = torch.cat([labels[:n], torch.cat(tl).reshape(n, n_tiles * k)], 1)
+            if gpu_merge:
+                ob, osc, ol, osrc, _ = _lib.nms_merge(cb, cs, cl.to(torch.int32), None, conf, merge_iou, merge_metric,
+                                                      max_det, class_agnostic)
+                packed = torch.cat([ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype)],
+                                   -1).cpu()  # one copy back; src < 0 marks the rows past the kept ones
+                rows = [packed[i][packed[i][:, 6] >= 0] for i in range(n)]
+            else:
+                packed = torch.cat([cb, cs[..., None], cl[..., None].to(cb.dtype)], -1).cpu()
+                rows = []
+                for i in range(n):
+                    keep = torch.from_numpy(merge_reference(packed[i][:, :4], packed[i][:, 4], packed[i][:, 5], None,
+                                                            conf, merge_iou, merge_metric, max_det, class_agnostic))
+                    rows.append(torch.cat([packed[i][keep], keep[:, None].to(packed.dtype)], -1))
+            for i, row in enumerate(rows):
+                preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
+                                        boxes=row[:, :4].contiguous(), scores=row[:, 4].contiguous(),
+                                        labels=row[:, 5].to(torch.int64), source=row[:, 6].to(torch.int64) // k))
+            t_pre += t_tile[0]
+            t_inf += t_tile[1]
+            t_post -= t_tile[0] + t_tile[1]  # what is left of t3 - t2 is postprocessing: every pass's and the merge
+        else:
+            packed = torch.cat([boxes, scores[..., None], labels[..., None].to(boxes.dtype)], -1).cpu()  # one copy back
+            for i in range(n):
+                row = packed[i]
+                keep = row[:, 4] >= conf  # postprocess_batched's rows are already best first
+                preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
+                                        boxes=row[keep, :4].contiguous(), scores=row[keep, 4].contiguous(),
+                                        labels=row[keep, 5].to(torch.int64)))
         t3 = time.perf_counter()
         t_pre += t1 - t0 - t_cap
         t_inf += t2 - t1
@@ -936,6 +1057,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     n_img = max(len(preds), 1)
     speed = {"preprocess": 1e3 * t_pre / n_img, "inference": 1e3 * t_inf / n_img,
              "postprocess": 1e3 * t_post / n_img}
+    if tiles is not None:
+        speed["passes"] = 1 + n_tiles
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
         save_dir.mkdir(parents=True, exist_ok=True)

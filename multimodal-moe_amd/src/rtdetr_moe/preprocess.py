@@ -19,6 +19,9 @@
 * ``HostCollate``: the loader's host path (PIL resize + data._padded_image,
   exactly as YoloDataset / CocoDataset do it): the CPU device, and the baseline
   the kernel is measured against (MOE_PREDICT_RESIZE=0).
+* ``TilePackCollate`` / ``TileHostCollate``: the same batches with the tiles of
+  every frame (engine.predict(tiles=...)): further descriptor rows into the
+  buffer that is uploaded anyway, or crops resized on the host.
 """
 from __future__ import annotations
 
@@ -235,6 +238,64 @@ class HostCollate:
                 "paths": [b[1] for b in batch],
                 "sizes": [(int(b[0].shape[1]), int(b[0].shape[0])) for b in batch],
                 "ctx": torch.tensor([b[2] for b in batch], dtype=torch.int32)}
+
+
+# ---------------------------------------------------------------------------
+# tiled prediction (engine.predict(tiles=...)): the same batches plus their tiles
+# ---------------------------------------------------------------------------
+class TilePackCollate(PackCollate):
+    """PackCollate plus the tiles of every frame as further rows of the same
+    descriptor table -- a crop of an uploaded frame is [off + y0 stride + 3 x0,
+    th, tw, stride], so the tiles cost no second upload: "tile_desc" int64
+    [B T, 4], frame-major, tiles row-major (merge.tile_windows on each PACKED
+    frame, from its own descriptor row), and "windows": per frame its T windows
+    (x0, y0, tw, th) in SOURCE pixels -- the packed window times src / packed
+    per axis where pack_frames reduced the frame on the host (floats then)."""
+
+    def __init__(self, out_hw, tiles, overlap, pin=False):
+        super().__init__(out_hw, pin)
+        self.tiles, self.overlap = (int(tiles[0]), int(tiles[1])), float(overlap)
+
+    def __call__(self, batch):
+        from .merge import tile_windows
+
+        bt = super().__call__(batch)
+        rows, windows = [], []
+        for (off, h, w, stride), (sw, sh) in zip(bt["desc"].tolist(), bt["sizes"]):
+            wins = tile_windows(w, h, self.tiles, self.overlap)
+            rows += [[off + y0 * stride + 3 * x0, th, tw, stride] for x0, y0, tw, th in wins]
+            if (sw, sh) != (w, h):
+                sx, sy = sw / w, sh / h
+                wins = [(x0 * sx, y0 * sy, tw * sx, th * sy) for x0, y0, tw, th in wins]
+            windows.append(wins)
+        bt["tile_desc"] = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+        bt["windows"] = windows
+        return bt
+
+
+class TileHostCollate(HostCollate):
+    """HostCollate plus the tiles of every frame, cropped on the host (numpy
+    slices of the decoded frame) and resized with host_resize: "tile_images"
+    fp32 [B T, 3, pad_h, pad_w], frame-major, tiles row-major, and "windows":
+    per frame its T windows (x0, y0, tw, th) in source pixels."""
+
+    def __init__(self, out_hw, pad_hw, tiles, overlap):
+        super().__init__(out_hw, pad_hw)
+        self.tiles, self.overlap = (int(tiles[0]), int(tiles[1])), float(overlap)
+
+    def __call__(self, batch):
+        from .merge import tile_windows
+
+        bt = super().__call__(batch)
+        imgs, windows = [], []
+        for frame, _, _ in batch:
+            wins = tile_windows(int(frame.shape[1]), int(frame.shape[0]), self.tiles, self.overlap)
+            imgs += [host_resize(np.ascontiguousarray(frame[y0:y0 + th, x0:x0 + tw]), self.out_hw, self.pad_hw)
+                     for x0, y0, tw, th in wins]
+            windows.append(wins)
+        bt["tile_images"] = torch.stack(imgs)
+        bt["windows"] = windows
+        return bt
 
 
 def iter_batches(ds, batch: int, workers: int, collate, ahead: int = 2):

@@ -109,6 +109,30 @@ int main() {
     std::printf("FAIL resize_pad B=0 must succeed\n");
     ++g_fail;
   }
+  expect_error("nms_merge N=4097", rtdetr_nms_merge(f32, f32, i32, nullptr, 1, 4097, 0.25f, 0.5f, 1, 0, 300, f32, f32,
+                                                    i32, i32, i32, s));
+  expect_error("nms_merge max_det=0", rtdetr_nms_merge(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 0, f32, f32,
+                                                       i32, i32, i32, s));
+  expect_error("nms_merge max_det=1025", rtdetr_nms_merge(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 1025, f32,
+                                                          f32, i32, i32, i32, s));
+  expect_error("nms_merge B=1025", rtdetr_nms_merge(f32, f32, i32, nullptr, 1025, 64, 0.25f, 0.5f, 1, 0, 300, f32, f32,
+                                                    i32, i32, i32, s));
+  expect_error("nms_merge metric=2", rtdetr_nms_merge(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 2, 0, 300, f32, f32,
+                                                      i32, i32, i32, s));
+  expect_error("nms_merge thr=NaN", rtdetr_nms_merge(f32, f32, i32, nullptr, 1, 64, 0.25f, __builtin_nanf(""), 1, 0,
+                                                     300, f32, f32, i32, i32, i32, s));
+  expect_error("nms_merge boxes=NULL", rtdetr_nms_merge(nullptr, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, f32,
+                                                        f32, i32, i32, i32, s));
+  expect_error("nms_merge count=NULL", rtdetr_nms_merge(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, f32,
+                                                        f32, i32, i32, nullptr, s));
+  expect_error("nms_merge boxes misaligned", rtdetr_nms_merge(f32 + 1, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0,
+                                                              300, f32, f32, i32, i32, i32, s));
+  ++g_n;
+  if (rtdetr_nms_merge(nullptr, nullptr, nullptr, nullptr, 0, 64, 0.25f, 0.5f, 1, 0, 300, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, s) != 0) {  // B == 0: success, no launch
+    std::printf("FAIL nms_merge B=0 must succeed\n");
+    ++g_fail;
+  }
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

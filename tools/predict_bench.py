@@ -4,8 +4,12 @@ Writes N (default 64) 3848 x 2168 JPEGs from a seed into a temporary directory,
 then runs engine.predict on them with MOE_PREDICT_RESIZE=1 and =0 alternately
 (default three times each, one process) and prints one JSON line per run with
 ``speed`` (ms per image) and a last line with the medians and spreads.
+With --tiles RxC it runs, on the same files and alternately, prediction without
+tiles, with tiles merged on the GPU (MOE_PREDICT_MERGE=1) and with tiles merged
+on the host (MOE_PREDICT_MERGE=0), all with the GPU resize.
 
   python tools/predict_bench.py [--model rtdetr-r50-moe8-top2] [--n 64] [--batch 16] [--rounds 3] [--workers 4]
+  python tools/predict_bench.py --tiles 2x2 [--conf 0.25]
 """
 from __future__ import annotations
 
@@ -36,6 +40,32 @@ def write_frames(d: Path, n: int, seed: int = 0, hw=(2168, 3848)):
         im.save(d / f"{i:06d}.jpg", quality=90)
 
 
+def tiles_leg(a, d: Path, engine):
+    """Untiled, tiled with the merge kernel and tiled with the host merge, alternated per round."""
+    legs = (("untiled", None, "1"), ("tiles_gpu_merge", a.tiles, "1"), ("tiles_host_merge", a.tiles, "0"))
+    os.environ["MOE_PREDICT_RESIZE"] = "1"
+    runs = {name: [] for name, _, _ in legs}
+    for r in range(a.rounds):
+        for name, tiles, merge in legs:
+            os.environ["MOE_PREDICT_MERGE"] = merge
+            torch.manual_seed(0)
+            t0 = time.perf_counter()
+            res = engine.predict(a.model, d, batch=a.batch, device=a.device, conf=a.conf, workers=a.workers,
+                                 tiles=tiles)
+            line = {"round": r, "leg": name, "images": len(res.predictions),
+                    "detections": sum(len(p.scores) for p in res.predictions),
+                    "wall_s": round(time.perf_counter() - t0, 2), **{k: round(v, 3) for k, v in res.speed.items()}}
+            print(json.dumps(line), flush=True)
+            runs[name].append(res.speed)
+    os.environ.pop("MOE_PREDICT_MERGE", None)
+    out = {"model": a.model, "batch": a.batch, "workers": a.workers, "tiles": a.tiles, "conf": a.conf}
+    for name, _, _ in legs:
+        for k in ("preprocess", "inference", "postprocess"):
+            v = [s[k] for s in runs[name]]
+            out[f"{name}/{k}"] = [round(statistics.median(v), 3), round(min(v), 3), round(max(v), 3)]
+    print(json.dumps(out), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="rtdetr-r50-moe8-top2")
@@ -44,6 +74,8 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--device", default="0")
+    ap.add_argument("--tiles", default=None, help="ROWSxCOLS: time tiled prediction against the untiled run")
+    ap.add_argument("--conf", type=float, default=0.25)
     a = ap.parse_args(argv)
     from src.rtdetr_moe import engine
 
@@ -66,6 +98,9 @@ def main(argv=None):
             rsz.append(1e3 * (time.perf_counter() - t1))
         print(json.dumps({"jpeg_decode_ms_per_frame_one_core": round(statistics.median(dec), 2),
                           "host_resize_ms_per_frame_one_core": round(statistics.median(rsz), 2)}), flush=True)
+        if a.tiles:
+            tiles_leg(a, d, engine)
+            return
         runs = {"1": [], "0": []}
         for r in range(a.rounds):
             for switch in ("1", "0"):
