@@ -138,7 +138,10 @@ __device__ void lsap_solve(const CostFn& cost_qm, int n, int Q, int M, int32_t* 
         const int index = last_un >= 0 ? last_un : first_eq;
         const int j = remaining[index];
         s_minval = L;
-        if (row4col[j] == -1) s_sink = j;
+        if (L == INFINITY) {
+          // no remaining column is reachable at a finite cost: infeasible, as scipy
+          // decides BEFORE it looks at the column (its path entry was never written)
+        } else if (row4col[j] == -1) s_sink = j;
         else s_i = row4col[j];
         SC[j] = 1;
         remaining[index] = remaining[nrem - 1];
