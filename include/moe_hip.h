@@ -781,6 +781,30 @@ int rtdetr_eval_match(const float* boxes, const float* scores, const int32_t* la
                       const int32_t* gt_labels, const int32_t* n_valid, const double* thr, int B, int K, int M,
                       int T, uint8_t* tp, hipStream_t stream);
 
+/* Validation, size-stratified (the size report; metrics.match_predictions_banded
+ * on the host, restated so that code is the same bit for bit): the matching of
+ * rtdetr_eval_match once per height band, with the truths outside the band as
+ * ignore regions.  The first seven operands, K, M and T are those of
+ * rtdetr_eval_match.  scale fp64 [B]: source-frame pixels per evaluated pixel
+ * of each image.  bands fp64 [R][2]: (lo, hi) box heights in source pixels, lo
+ * inclusive, hi exclusive, hi may be +inf; bands may overlap.  A box is in band
+ * r when lo <= height * scale[b] < hi, the truth height y2 - y1 in fp64, the
+ * prediction height y2 - y1 in fp32 and then widened, the product in fp64 (no
+ * FMA contraction); a NaN or negative height is in no band.
+ * code uint8 [B][R][K][T], every entry written, in the INPUT prediction order:
+ * per band and threshold, with a taken set of its own and the visit order of
+ * rtdetr_eval_match, a prediction takes among the untaken truths of its label
+ * with iou >= thr[t] the in-band one with the largest IoU (lowest j among
+ * equals) -> 1 true positive; when none is in-band, the out-of-band one by the
+ * same rule, which is taken as well -> 2 ignored; with no candidate, 0 (false
+ * positive) if its own height is in the band, else 2.
+ * One workgroup per (image, band), one wave per threshold; K <= 1024,
+ * M <= 1024, T <= 16, R <= 8.  Counted and profiled as MOE_PROF_EVAL. */
+int rtdetr_eval_match_bands(const float* boxes, const float* scores, const int32_t* labels, const double* gt_boxes,
+                            const int32_t* gt_labels, const int32_t* n_valid, const double* thr,
+                            const double* scale, const double* bands, int B, int K, int M, int T, int R,
+                            uint8_t* code, hipStream_t stream);
+
 /* Inference preprocessing (engine.predict, preprocess.py): B decoded frames,
  * uint8 HWC RGB of any sizes, to the model's input in one launch: resize to
  * out_h x out_w with the antialiased bilinear filter of PIL / torch

@@ -22,6 +22,14 @@
 // union = (area_a + area_b) - inter; iou = inter / max(union, 1e-9).  No FMA
 // contraction anywhere (pragma below): a fused (area_a + area_b) - w h flips
 // bits.  The fp64 division is the correctly rounded one.
+//
+// rtdetr_eval_match_bands is the size-stratified form (the size report of
+// validation, metrics.match_predictions_banded): the same workgroup per (image,
+// height band), the truths outside the band as ignore regions.  Each lane
+// keeps an in-band and an out-of-band best; the in-band set is reduced first
+// and the out-of-band one only when the wave found no in-band candidate.  Both
+// kernels are one template (eval_match_image), so the staging, the ranks, the
+// IoU and the selection are shared.
 #include "moe_common.h"
 #include "prof.h"
 
@@ -29,7 +37,7 @@
 
 namespace moe {
 
-constexpr int kEvalMaxK = 1024, kEvalMaxM = 1024, kEvalMaxT = 16;
+constexpr int kEvalMaxK = 1024, kEvalMaxM = 1024, kEvalMaxT = 16, kEvalMaxR = 8;
 
 __host__ __device__ constexpr size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
@@ -83,10 +91,25 @@ __device__ __forceinline__ int take_best(double best, int best_j, int lane, uint
   return 1;
 }
 
-__global__ __launch_bounds__(1024) void eval_match_kernel(
+// lo <= h < hi: membership of a box height in a band (a NaN height is in none)
+__device__ __forceinline__ bool in_band(double h, double lo, double hi) { return h >= lo && h < hi; }
+
+// One image of either matcher (blockIdx.x = the image; out = its [K][T] slab).
+// kBands = false: metrics.match_predictions, out <- tp (0 / 1).
+// kBands = true: metrics.match_predictions_banded for the band [lo, hi) of box
+// heights in source pixels (evaluated pixels times scale), out <- 0 false
+// positive, 1 true positive, 2 ignored.  Truths outside the band are ignore
+// regions: a prediction takes the best in-band candidate (1); only when it has
+// none, the best out-of-band candidate (2, and that truth is taken too); with
+// no candidate at all it is 0 if its own height is in the band, else 2.  Truth
+// heights are fp64, the prediction height is the fp32 difference widened, as
+// the reference takes them; each is multiplied by scale in fp64.
+template <bool kBands>
+__device__ __forceinline__ void eval_match_image(
     const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
     const double* __restrict__ gt_boxes, const int32_t* __restrict__ gt_labels, const int32_t* __restrict__ n_valid,
-    const double* __restrict__ thr, int K, int M, int T, uint8_t* __restrict__ tp) {
+    const double* __restrict__ thr, int K, int M, int T, uint8_t* __restrict__ out, double scale, double lo,
+    double hi) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const EvalLds o(K, M);
   const int Ms = (int)(up16((size_t)M * 8) / 8);
@@ -131,7 +154,7 @@ __global__ __launch_bounds__(1024) void eval_match_kernel(
   const int t = tid >> 6, lane = tid & 63;  // wave t: threshold t
   const double th = thr[t];
   uint32_t taken = 0;  // bit jj: truth lane + 64 jj is taken (M <= 1024: 16 bits)
-  uint8_t* tpb = tp + (size_t)b * K * T + t;
+  uint8_t* tpb = out + t;
   if (n <= 64) {
     // One truth per lane, kept in registers.  The IoU of a pair does not depend
     // on the chain's state (only the selection does), so the IoUs of four
@@ -142,9 +165,10 @@ __global__ __launch_bounds__(1024) void eval_match_kernel(
     const int jl = real ? lane : 0;  // in bounds; the value is unused when !real
     const double bx1 = g[jl], by1 = g[Ms + jl], bx2 = g[2 * Ms + jl], by2 = g[3 * Ms + jl];
     const int gl = glabel[jl];
+    const bool g_in = kBands ? in_band((by2 - by1) * scale, lo, hi) : true;
     for (int r0 = 0; r0 < K; r0 += U) {
       int pi[U];
-      bool cand[U];
+      bool cand[U], p_in[U];
       double iou[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -152,29 +176,68 @@ __global__ __launch_bounds__(1024) void eval_match_kernel(
         const float4 p = *reinterpret_cast<const float4*>(pbox + 4 * pi[u]);
         iou[u] = pair_iou(p, bx1, by1, bx2, by2);
         cand[u] = real && plabel[pi[u]] == gl && iou[u] >= th;
+        p_in[u] = kBands ? in_band((double)(p.w - p.y) * scale, lo, hi) : true;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (r0 + u >= K) break;
-        const int hit = take_best(iou[u], cand[u] && !(taken & 1u) ? lane : -1, lane, taken);
+        const bool c = cand[u] && !(taken & 1u);
+        int hit = take_best(iou[u], c && g_in ? lane : -1, lane, taken);
+        if constexpr (kBands) {
+          if (!hit) hit = 2 * take_best(iou[u], c && !g_in ? lane : -1, lane, taken);
+          if (!hit) hit = p_in[u] ? 0 : 2;
+        }
         if (lane == 0) tpb[(size_t)pi[u] * T] = (uint8_t)hit;
       }
     }
     return;
   }
+  uint32_t inb = 0;  // bit jj: truth lane + 64 jj is in the band
+  if constexpr (kBands) {
+    for (int j = lane, jj = 0; j < n; j += 64, ++jj)
+      if (in_band((g[3 * Ms + j] - g[Ms + j]) * scale, lo, hi)) inb |= 1u << jj;
+  }
   for (int r = 0; r < K; ++r) {
     const int i = order[r];
     const float4 p = *reinterpret_cast<const float4*>(pbox + 4 * i);
     const int pl = plabel[i];
-    double best = 0.0;
-    int best_j = -1;
+    double best = 0.0, obest = 0.0;  // the lane's best in-band and out-of-band candidates
+    int best_j = -1, obest_j = -1;
     for (int j = lane, jj = 0; j < n; j += 64, ++jj) {
       const double iou = pair_iou(p, g[j], g[Ms + j], g[2 * Ms + j], g[3 * Ms + j]);
-      if (glabel[j] == pl && !((taken >> jj) & 1u) && iou >= th) better(best, best_j, iou, j);
+      if (glabel[j] == pl && !((taken >> jj) & 1u) && iou >= th) {
+        if (!kBands || ((inb >> jj) & 1u))
+          better(best, best_j, iou, j);
+        else
+          better(obest, obest_j, iou, j);
+      }
     }
-    const int hit = take_best(best, best_j, lane, taken);
+    int hit = take_best(best, best_j, lane, taken);
+    if constexpr (kBands) {
+      if (!hit) hit = 2 * take_best(obest, obest_j, lane, taken);
+      if (!hit) hit = in_band((double)(p.w - p.y) * scale, lo, hi) ? 0 : 2;
+    }
     if (lane == 0) tpb[(size_t)i * T] = (uint8_t)hit;
   }
+}
+
+__global__ __launch_bounds__(1024) void eval_match_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const double* __restrict__ gt_boxes, const int32_t* __restrict__ gt_labels, const int32_t* __restrict__ n_valid,
+    const double* __restrict__ thr, int K, int M, int T, uint8_t* __restrict__ tp) {
+  eval_match_image<false>(boxes, scores, labels, gt_boxes, gt_labels, n_valid, thr, K, M, T,
+                          tp + (size_t)blockIdx.x * K * T, 1.0, 0.0, 0.0);
+}
+
+// grid (B, R): workgroup (b, r) matches image b for band r; code uint8 [B][R][K][T]
+__global__ __launch_bounds__(1024) void eval_match_bands_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const double* __restrict__ gt_boxes, const int32_t* __restrict__ gt_labels, const int32_t* __restrict__ n_valid,
+    const double* __restrict__ thr, const double* __restrict__ scale, const double* __restrict__ bands, int K, int M,
+    int T, uint8_t* __restrict__ code) {
+  const int b = blockIdx.x, r = blockIdx.y;
+  eval_match_image<true>(boxes, scores, labels, gt_boxes, gt_labels, n_valid, thr, K, M, T,
+                         code + ((size_t)b * gridDim.y + r) * K * T, scale[b], bands[2 * r], bands[2 * r + 1]);
 }
 
 }  // namespace moe
@@ -194,4 +257,22 @@ extern "C" int rtdetr_eval_match(const float* boxes, const float* scores, const 
   MOE_LAUNCH(prof, eval_match_kernel, dim3(B), dim3(64 * T), shmem, stream, boxes, scores, labels, gt_boxes,
              gt_labels, n_valid, thr, K, M, T, tp);
   return check_launch("rtdetr_eval_match");
+}
+
+extern "C" int rtdetr_eval_match_bands(const float* boxes, const float* scores, const int32_t* labels,
+                                       const double* gt_boxes, const int32_t* gt_labels, const int32_t* n_valid,
+                                       const double* thr, const double* scale, const double* bands, int B, int K,
+                                       int M, int T, int R, uint8_t* code, hipStream_t stream) {
+  if (B < 1 || K < 1 || M < 1 || T < 1 || R < 1 || K > kEvalMaxK || M > kEvalMaxM || T > kEvalMaxT || R > kEvalMaxR)
+    return fail(
+        "rtdetr_eval_match_bands: need B >= 1, 1 <= K <= 1024, 1 <= M <= 1024, 1 <= T <= 16, 1 <= R <= 8");
+  if (!boxes || !scores || !labels || !gt_boxes || !gt_labels || !n_valid || !thr || !scale || !bands || !code)
+    return fail("rtdetr_eval_match_bands: NULL pointer");
+  const size_t shmem = EvalLds(K, M).total;
+  if (shmem > 64 * 1024) return fail("rtdetr_eval_match_bands: K/M too large for LDS");
+  ProfScope prof(stream, PROF_EVAL,
+                 (double)B * R * (K * 24.0 + M * 36.0 + 12.0 + (double)K * T) + 8.0 * T + 16.0 * R);
+  MOE_LAUNCH(prof, eval_match_bands_kernel, dim3(B, R), dim3(64 * T), shmem, stream, boxes, scores, labels, gt_boxes,
+             gt_labels, n_valid, thr, scale, bands, K, M, T, code);
+  return check_launch("rtdetr_eval_match_bands");
 }

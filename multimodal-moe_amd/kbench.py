@@ -8,6 +8,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py [--reps 50] [--rounds 5] [--variants 1,2] [--stages 3,4]
   python multimodal-moe_amd/kbench.py --augment     the batch-augmentation kernels at C2's batch
   python multimodal-moe_amd/kbench.py --eval-match  the validation matcher against the host loop
+  python multimodal-moe_amd/kbench.py --eval-match-bands  the size-stratified matcher, the plain one and the host loop
   python multimodal-moe_amd/kbench.py --route-stats the routing-statistics kernel against its torch reference
   python multimodal-moe_amd/kbench.py --resize      the inference resize kernel against the host resize it replaces
   python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
@@ -247,6 +248,78 @@ def augment_leg(reps, rounds):
                           "GBs": round(byts / med * 1e-3, 1), "bytes": byts}), flush=True)
 
 
+def _eval_match_inputs(rng, B, K, M):
+    """One batch of the eval-match legs: M truths per image, K predictions of
+    which half are jittered truths and half noise, one class.  Returns the host
+    arrays (boxes, scores, labels, gt, gl) and rtdetr_eval_match's device operands."""
+    import numpy as np
+
+    from src.rtdetr_moe import metrics as MT
+
+    xy = rng.uniform(0, 1100, (B, M, 2))
+    gt = np.concatenate([xy, xy + rng.uniform(15, 120, (B, M, 2))], 2)
+    src = rng.integers(0, M, (B, K))
+    boxes = np.take_along_axis(gt, src[..., None], 1) + rng.uniform(-6, 6, (B, K, 4))
+    noise = rng.random((B, K)) < 0.5
+    p = rng.uniform(0, 1100, (int(noise.sum()), 2))
+    boxes[noise] = np.concatenate([p, p + rng.uniform(5, 120, p.shape)], 1)  # half the predictions: noise
+    boxes = boxes.astype(np.float32)
+    scores = rng.random((B, K)).astype(np.float32)
+    labels = np.zeros((B, K), np.int64)
+    gl = np.zeros((B, M), np.int64)
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    d = (cu(boxes), cu(scores), cu(labels.astype(np.int32)), cu(gt), cu(gl.astype(np.int32)),
+         torch.full((B,), M, dtype=torch.int32, device="cuda"), cu(np.asarray(MT.IOU_THRESHOLDS, np.float64)))
+    return boxes, scores, labels, gt, gl, d
+
+
+def eval_match_bands_leg(reps, rounds):
+    """The size-stratified matcher at the eval-match leg's shapes (B 16, K 300,
+    M 20 or 64, one class) with the three default bands, every other image at
+    the scale of a 3848 x 2168 frame evaluated at 1248 x 704: us per batch of
+    rtdetr_eval_match_bands and of rtdetr_eval_match on the same inputs
+    (dispatch-stamped kernel time), next to ms per batch of the host's
+    metrics.match_predictions_banded (wall clock, 16 images).  Refuses to time
+    unless the codes equal the reference.  Median, min and max over the rounds,
+    the sides interleaved in each round."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import metrics as MT
+
+    B, K = 16, 300
+    names, bands = MT.named_bands()
+    scale = np.where(np.arange(B) % 2 == 0, 1.0, 2168 / 704)
+    rng = np.random.default_rng(0)
+    for M in (20, 64):
+        boxes, scores, labels, gt, gl, d = _eval_match_inputs(rng, B, K, M)
+        db = (*d, torch.from_numpy(scale).cuda(), torch.from_numpy(bands).cuda())
+
+        def host_path():
+            return np.stack([MT.match_predictions_banded(boxes[b], scores[b], labels[b], gt[b], gl[b], bands, scale[b])
+                             for b in range(B)])
+
+        want = host_path()
+        if not np.array_equal(L.eval_match_bands(*db).cpu().numpy(), want):
+            raise SystemExit("eval_match_bands differs from match_predictions_banded")
+        res = {"bands_kernel_us": [], "eval_match_kernel_us": [], "host_match_ms": []}
+        for _ in range(rounds):
+            res["bands_kernel_us"].append(timed(lambda: L.eval_match_bands(*db), reps))
+            res["eval_match_kernel_us"].append(timed(lambda: L.eval_match(*d), reps))
+            t0 = time.perf_counter()
+            host_path()
+            res["host_match_ms"].append(1e3 * (time.perf_counter() - t0))
+        out = {"kernel": "rtdetr_eval_match_bands",
+               "shape": f"B{B} K{K} M{M} T{len(MT.IOU_THRESHOLDS)} R{len(bands)}", "bands": names,
+               "codes_at_0.5": {n: [int((want[:, r, :, 0] == c).sum()) for c in (0, 1, 2)] for r, n in enumerate(names)}}
+        for k, v in res.items():
+            out[k] = round(statistics.median(v), 3)
+            out[k + "_min"] = round(min(v), 3)
+            out[k + "_max"] = round(max(v), 3)
+        print(json.dumps(out), flush=True)
+
+
 def eval_match_leg(reps, rounds):
     """The validation matcher at the eval leg's shape (B 16, K 300 predictions,
     M 20 or 64 truths per image, one class): us per batch of rtdetr_eval_match
@@ -264,20 +337,8 @@ def eval_match_leg(reps, rounds):
     B, K = 16, 300
     rng = np.random.default_rng(0)
     for M in (20, 64):
-        xy = rng.uniform(0, 1100, (B, M, 2))
-        gt = np.concatenate([xy, xy + rng.uniform(15, 120, (B, M, 2))], 2)
-        src = rng.integers(0, M, (B, K))
-        boxes = np.take_along_axis(gt, src[..., None], 1) + rng.uniform(-6, 6, (B, K, 4))
-        noise = rng.random((B, K)) < 0.5
-        p = rng.uniform(0, 1100, (int(noise.sum()), 2))
-        boxes[noise] = np.concatenate([p, p + rng.uniform(5, 120, p.shape)], 1)  # half the predictions: noise
-        boxes = boxes.astype(np.float32)
-        scores = rng.random((B, K)).astype(np.float32)
-        labels = np.zeros((B, K), np.int64)
-        gl = np.zeros((B, M), np.int64)
+        boxes, scores, labels, gt, gl, d = _eval_match_inputs(rng, B, K, M)
         cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
-        d = (cu(boxes), cu(scores), cu(labels.astype(np.int32)), cu(gt), cu(gl.astype(np.int32)),
-             torch.full((B,), M, dtype=torch.int32, device="cuda"), cu(np.asarray(MT.IOU_THRESHOLDS, np.float64)))
         tp = L.eval_match(*d).cpu().numpy().astype(bool)
         want = np.stack([MT.match_predictions(boxes[b], scores[b], labels[b], gt[b], gl[b]) for b in range(B)])
         if not np.array_equal(tp, want):
@@ -598,6 +659,9 @@ def main():
     ap.add_argument("--augment", action="store_true", help="time the batch-augmentation kernels (C2's batch) and exit")
     ap.add_argument("--eval-match", action="store_true",
                     help="time the validation matcher (B 16, K 300, M 20 / 64) against the host loop and exit")
+    ap.add_argument("--eval-match-bands", action="store_true",
+                    help="time the size-stratified matcher (B 16, K 300, M 20 / 64, R 3) against the plain matcher "
+                         "and the host loop and exit")
     ap.add_argument("--route-stats", action="store_true",
                     help="time moe_route_stats (C2's eval shapes, batch 16) against its torch reference and exit")
     ap.add_argument("--resize", action="store_true",
@@ -633,6 +697,9 @@ def main():
         return
     if a.eval_match:
         eval_match_leg(a.reps, a.rounds)
+        return
+    if a.eval_match_bands:
+        eval_match_bands_leg(a.reps, a.rounds)
         return
     if a.route_stats:
         route_stats_leg(a.reps, a.rounds)

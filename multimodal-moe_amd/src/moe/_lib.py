@@ -116,6 +116,7 @@ SIGNATURES = {
     "moe_router_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rtdetr_hungarian_match": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_eval_match": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "rtdetr_eval_match_bands": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_resize_pad_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_nms_merge": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
@@ -290,13 +291,20 @@ def profile_records(clear=True):
 
 def launch_counts(reset=False) -> dict:
     """{kind name: launches} the library has issued since the last reset
-    (host-side counts, graph capture included: moe_launch_counts)."""
+    (host-side counts, graph capture included: moe_launch_counts).
+    "eval_match_bands" -- the launches of eval_match_bands(), which the library
+    counts with eval_match's -- is reported apart and taken out of "eval_match"."""
+    global _eval_match_bands_launches
     n = max(PROF_KINDS) + 1
     buf = (ctypes.c_longlong * n)()
     _check(lib().moe_launch_counts(ctypes.cast(buf, ctypes.c_void_p), n), "moe_launch_counts")
+    out = {PROF_KINDS[i]: int(buf[i]) for i in range(n)}
+    out["eval_match_bands"] = min(_eval_match_bands_launches, out["eval_match"])
+    out["eval_match"] -= out["eval_match_bands"]
     if reset:
         lib().moe_launch_counts_reset()
-    return {PROF_KINDS[i]: int(buf[i]) for i in range(n) if buf[i]}
+        _eval_match_bands_launches = 0
+    return {k: v for k, v in out.items() if v}
 
 
 def _ptr(t: torch.Tensor | None) -> int | None:
@@ -840,6 +848,46 @@ def eval_match(boxes, scores, labels, gt_boxes, gt_labels, n_valid, thr):
                                  _ptr(n_valid), _ptr(thr), B, K, M, T, _ptr(tp), _stream())
     _check(rc, "rtdetr_eval_match")
     return tp
+
+
+EVAL_MATCH_MAX_R = 8  # rtdetr_eval_match_bands' most bands
+# rtdetr_eval_match_bands shares the library's eval_match launch counter (and profiler kind);
+# launch_counts() reports its launches, counted here, under their own name
+_eval_match_bands_launches = 0
+
+
+def eval_match_bands(boxes, scores, labels, gt_boxes, gt_labels, n_valid, thr, scale, bands):
+    """Size-stratified validation matching of a batch
+    (metrics.match_predictions_banded per image, bit for bit).  The operands of
+    ``eval_match`` plus scale fp64 [B] (source pixels per evaluated pixel) and
+    bands fp64 [R, 2] (lo, hi box heights in source pixels) -> code uint8
+    [B, R, K, T]: 0 false positive, 1 true positive, 2 ignored, in the input
+    prediction order."""
+    global _eval_match_bands_launches
+    _need(boxes, torch.float32, "boxes")
+    _need(scores, torch.float32, "scores")
+    _need(labels, torch.int32, "labels")
+    _need(gt_boxes, torch.float64, "gt_boxes")
+    _need(gt_labels, torch.int32, "gt_labels")
+    _need(n_valid, torch.int32, "n_valid")
+    _need(thr, torch.float64, "thr")
+    _need(scale, torch.float64, "scale")
+    _need(bands, torch.float64, "bands")
+    if (boxes.dim() != 3 or boxes.shape[-1] != 4 or gt_boxes.dim() != 3 or gt_boxes.shape[-1] != 4 or thr.dim() != 1
+            or bands.dim() != 2 or bands.shape[-1] != 2):
+        raise MoEKernelError("eval_match_bands: boxes [B, K, 4], gt_boxes [B, M, 4], thr [T], bands [R, 2]")
+    B, K, _ = boxes.shape
+    M, T, R = int(gt_boxes.shape[1]), int(thr.shape[0]), int(bands.shape[0])
+    if (tuple(scores.shape) != (B, K) or tuple(labels.shape) != (B, K) or int(gt_boxes.shape[0]) != B
+            or tuple(gt_labels.shape) != (B, M) or tuple(n_valid.shape) != (B,) or tuple(scale.shape) != (B,)):
+        raise MoEKernelError("eval_match_bands: scores / labels [B, K], gt_labels [B, M], n_valid / scale [B] expected")
+    code = torch.empty((B, R, K, T), dtype=torch.uint8, device=boxes.device)
+    rc = lib().rtdetr_eval_match_bands(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(gt_boxes), _ptr(gt_labels),
+                                       _ptr(n_valid), _ptr(thr), _ptr(scale), _ptr(bands), B, K, M, T, R, _ptr(code),
+                                       _stream())
+    _check(rc, "rtdetr_eval_match_bands")
+    _eval_match_bands_launches += 1
+    return code
 
 
 RESIZE_MAX_SIDE = 16384  # rtdetr_resize_pad_u8's largest source side

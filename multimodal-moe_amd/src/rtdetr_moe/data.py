@@ -194,7 +194,9 @@ class YoloDataset(torch.utils.data.Dataset):
         from PIL import Image
 
         p = self.images[i]
-        im = Image.open(p).convert("RGB").resize((self.w, self.h), Image.BILINEAR)
+        im = Image.open(p).convert("RGB")
+        src_size = (im.width, im.height)  # the file's size, before the resize
+        im = im.resize((self.w, self.h), Image.BILINEAR)
         img = _padded_image(np.asarray(im, dtype=np.uint8), self.pad_h, self.pad_w, self.as_uint8)
         boxes, labels = [], []
         lp = self._label_path(p)
@@ -209,7 +211,8 @@ class YoloDataset(torch.utils.data.Dataset):
                               h * self.h / self.pad_h])
                 labels.append(c)
         t = {"boxes": torch.tensor(boxes, dtype=torch.float32).reshape(-1, 4),
-             "labels": torch.tensor(labels, dtype=torch.int64), "orig_size": (self.pad_w, self.pad_h)}
+             "labels": torch.tensor(labels, dtype=torch.int64), "orig_size": (self.pad_w, self.pad_h),
+             "src_size": src_size}
         return img, t, self.contexts.get(p.stem, MISSING_ID)
 
 
@@ -257,7 +260,8 @@ class CocoDataset(torch.utils.data.Dataset):
                           (x1 - x0) / ow * self.w / self.pad_w, (y1 - y0) / oh * self.h / self.pad_h])
             labels.append(self.cat_to_label[int(a["category_id"])])
         t = {"boxes": torch.tensor(boxes, dtype=torch.float32).reshape(-1, 4),
-             "labels": torch.tensor(labels, dtype=torch.int64), "orig_size": (self.pad_w, self.pad_h)}
+             "labels": torch.tensor(labels, dtype=torch.int64), "orig_size": (self.pad_w, self.pad_h),
+             "src_size": (ow, oh)}
         ctx = im.get("solar_context_bin")
         return img, t, MISSING_ID if ctx is None else context_id_from_label(ctx)
 

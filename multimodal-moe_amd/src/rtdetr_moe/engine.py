@@ -32,7 +32,7 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 from ..moe.config import parse_moe_spec
 from .criterion import SetCriterion
 from .data import CocoDataset, SyntheticZOD, YoloDataset, collate
-from .metrics import BoxMetrics, DetectionEvaluator, DeviceDetectionEvaluator, gt_xyxy_pixels
+from .metrics import BoxMetrics, DetectionEvaluator, DeviceDetectionEvaluator, gt_xyxy_pixels, named_bands
 from .model import RTDETRMoE
 from .schedule import accumulate_count, schedule_at, warmup_iters
 
@@ -102,6 +102,7 @@ class DetMetrics:
     save_dir: Path | None = None
     moe: dict = field(default_factory=dict)
     context: dict | None = None  # the per-context report (validate(context_report=True)), else None
+    size: dict | None = None  # the size report (validate(size_report=True)), else None
 
 
 def _results_dict(box: BoxMetrics) -> dict:
@@ -517,6 +518,11 @@ def _context_report_on(flag: bool | None) -> bool:
     return os.environ.get("MOE_CONTEXT_REPORT") == "1" if flag is None else bool(flag)
 
 
+def _size_report_on(flag: bool | None) -> bool:
+    """The size-report switch: an explicit argument, else MOE_SIZE_REPORT=1."""
+    return os.environ.get("MOE_SIZE_REPORT") == "1" if flag is None else bool(flag)
+
+
 def _context_columns(report: dict) -> dict:
     """results.csv columns of one epoch's context report: mAP50-95 per solar
     bin (an empty cell for a bin without targets) and, per MoE layer, the mutual
@@ -657,12 +663,23 @@ class EvalForward:
 
 @torch.no_grad()
 def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed, speed: dict | None = None,
-              ev_out: list | None = None, report: dict | None = None):
+              ev_out: list | None = None, report: dict | None = None, size_report: dict | None = None,
+              size_bands=None):
     """report: a dict to fill with the per-context report (``_fill_report``):
     detection metrics per solar bin and each MoE layer's routing table, summed
     over the split by one more HIP launch per layer forward.  None: the pass
-    launches and returns exactly what it does without the feature."""
+    launches and returns exactly what it does without the feature.
+
+    size_report: a dict to fill with the size report (``_fill_size_report``):
+    AP, recall and log-average miss rate per pedestrian-height band of
+    size_bands (``metrics.named_bands``; heights in source-frame pixels, an
+    image's scale its target's ``src_size`` height over the content height, 1.0
+    without one), matched by one more HIP launch per batch.  None: as above."""
     model.eval()
+    names = bands = None
+    if size_report is not None:
+        names, bands = named_bands(size_bands)
+    content_h = _hw(imgsz)[0]
     on_gpu = device.type == "cuda"
     fwd = EvalForward(model)
     stats = None
@@ -680,6 +697,9 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
         for images, targets, ctx in _batches(data, split, imgsz, batch, workers, seed, 0, 1, 0):
             t0 = time.perf_counter()
             ids = [int(c) for c in ctx.tolist()] if report is not None else None  # on the host, before the upload
+            scales = None
+            if bands is not None:
+                scales = [t["src_size"][1] / content_h if "src_size" in t else 1.0 for t in targets]
             images = images.to(device, non_blocking=True)
             ctx = ctx.to(device)
             t_cap = 0.0
@@ -697,7 +717,7 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
             H, W = images.shape[-2:]
             if on_gpu:
                 ev.update_batch(*model.postprocess_batched(out, [(W, H)] * images.shape[0]), targets, size=(W, H),
-                                ctx=ids)
+                                ctx=ids, bands=bands, scales=scales)
                 torch.cuda.synchronize()
             else:
                 dets = model.postprocess(out, [(W, H)] * images.shape[0])
@@ -705,7 +725,8 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
                     gt_xyxy = gt_xyxy_pixels(t["boxes"].numpy().astype(np.float64), W, H)
                     ev.update(det["boxes"].float().cpu().numpy(), det["scores"].float().cpu().numpy(),
                               det["labels"].cpu().numpy(), gt_xyxy, t["labels"].numpy(),
-                              ctx=ids[i] if ids is not None else None)
+                              ctx=ids[i] if ids is not None else None, bands=bands,
+                              scale=1.0 if scales is None else scales[i])
             t3 = time.perf_counter()
             t_pre += t1 - t0 - t_cap
             t_inf += t2 - t1
@@ -717,7 +738,23 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
                       "loss": 0.0, "postprocess": 1e3 * t_post / n_img})
     if report is not None:
         _fill_report(report, model, ev, stats)
+    if size_report is not None:
+        _fill_size_report(size_report, ev, names, bands, n_img)
     return ev.compute()
+
+
+def _fill_size_report(report: dict, ev: DetectionEvaluator, names, bands, images: int) -> None:
+    """The size report of one validation pass (size_report.json): {"unit":
+    "source px", "bands": [{"name", "lo", "hi"}] (hi null for an open band),
+    "images", "detection": {band name or "all": targets, AP50, AP50-95, recall,
+    LAMR}} (``DetectionEvaluator.compute_by_size``; null metrics for a band
+    without in-band truths)."""
+    report["unit"] = "source px"
+    report["bands"] = [{"name": n, "lo": float(lo), "hi": float(hi) if np.isfinite(hi) else None}
+                       for n, (lo, hi) in zip(names, bands)]
+    report["images"] = int(images)
+    empty = {"targets": 0, "AP50": None, "AP50-95": None, "recall": None, "LAMR": None}
+    report["detection"] = ev.compute_by_size(names) if images else {n: dict(empty) for n in [*names, "all"]}
 
 
 def _fill_report(report: dict, model: RTDETRMoE, ev: DetectionEvaluator, stats) -> None:
@@ -746,10 +783,20 @@ def _fill_report(report: dict, model: RTDETRMoE, ev: DetectionEvaluator, stats) 
 
 
 def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0", project=None, name=None,
-             workers=4, seed=0, context_report: bool | None = None) -> DetMetrics:
+             workers=4, seed=0, context_report: bool | None = None, size_report: bool | None = None,
+             size_bands=None) -> DetMetrics:
     """context_report: also build the per-context report (``DetMetrics.context``
     and, with a save directory, context_report.json there); None reads
-    MOE_CONTEXT_REPORT=1.  Off by default."""
+    MOE_CONTEXT_REPORT=1.  Off by default.
+
+    size_report: also build the size report (``DetMetrics.size`` and, with a
+    save directory, size_report.json there): AP, recall and log-average miss
+    rate per pedestrian-height band; None reads MOE_SIZE_REPORT=1.  Off by
+    default.  size_bands: (name, lo, hi) triples in source-frame pixels, lo
+    inclusive, hi exclusive, hi None for an open band (default far [0, 40),
+    medium [40, 100), near [100, inf))."""
+    if size_bands is not None:
+        named_bands(size_bands)  # a bad table fails before the model loads
     devices = parse_device(device)
     dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
     if dev.type == "cuda":
@@ -762,14 +809,18 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
         model = model.to(memory_format=torch.channels_last)
     speed = {}
     report = {} if _context_report_on(context_report) else None
-    box = _evaluate(model, data, split, imgsz, batch, dev, workers, seed, speed, report=report)
+    sizes = {} if _size_report_on(size_report) else None
+    box = _evaluate(model, data, split, imgsz, batch, dev, workers, seed, speed, report=report, size_report=sizes,
+                    size_bands=size_bands)
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
         save_dir.mkdir(parents=True, exist_ok=True)
         if report is not None:
             (save_dir / "context_report.json").write_text(json.dumps(report, indent=1))
+        if sizes is not None:
+            (save_dir / "size_report.json").write_text(json.dumps(sizes, indent=1))
     return DetMetrics(results_dict=_results_dict(box), box=box, speed=speed, model=ModelHandle(model),
-                      save_dir=save_dir, moe=_moe_stats(model), context=report)
+                      save_dir=save_dir, moe=_moe_stats(model), context=report, size=sizes)
 
 
 # ---------------------------------------------------------------------------

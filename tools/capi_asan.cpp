@@ -88,6 +88,16 @@ int main() {
   expect_error("eval_match T=17", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 4, 17, u8, s));
   expect_error("eval_match M=0", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 0, 10, u8, s));
   expect_error("eval_match tp=NULL", rtdetr_eval_match(f32, f32, i32, f64, i32, i32, f64, 1, 300, 4, 10, nullptr, s));
+  expect_error("eval_match_bands R=9",
+               rtdetr_eval_match_bands(f32, f32, i32, f64, i32, i32, f64, f64, f64, 1, 300, 4, 10, 9, u8, s));
+  expect_error("eval_match_bands R=0",
+               rtdetr_eval_match_bands(f32, f32, i32, f64, i32, i32, f64, f64, f64, 1, 300, 4, 10, 0, u8, s));
+  expect_error("eval_match_bands K=1025",
+               rtdetr_eval_match_bands(f32, f32, i32, f64, i32, i32, f64, f64, f64, 1, 1025, 4, 10, 3, u8, s));
+  expect_error("eval_match_bands bands=NULL",
+               rtdetr_eval_match_bands(f32, f32, i32, f64, i32, i32, f64, f64, nullptr, 1, 300, 4, 10, 3, u8, s));
+  expect_error("eval_match_bands code=NULL",
+               rtdetr_eval_match_bands(f32, f32, i32, f64, i32, i32, f64, f64, f64, 1, 300, 4, 10, 3, nullptr, s));
   auto* i64 = reinterpret_cast<long long*>(buf);
   expect_error("route_stats T%tpi", moe_route_stats(i32, f32, i32, f32, i32, 6, 5, 12, 8, 2, i64, s));
   expect_error("route_stats E=65", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 65, 2, i64, s));
