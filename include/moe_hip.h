@@ -1022,6 +1022,21 @@ int rtdetr_conv_wgrad_reduce_batch(int n, const float* const* parts, const int* 
 int rtdetr_conv1x1_bwd(const void* dy, const void* x, const void* w, void* dx, float* part, int nsplit,
                        const void* zero, int B, int H, int W, int C, int N, const void* add, int mask_input,
                        hipStream_t stream);
+/* A ResNet stage-1 bottleneck's output, and optionally the next block's
+ * branch2a from it, in ONE launch (1x1 stride 1, 64 -> 256):
+ *   y = relu((conv(h2, w2c) + r) + bias)      bf16 [B H W][256]
+ *   h = relu(conv(y, wn) + bias_n)            bf16 [B H W][next], next = 64 / 128
+ * r is the tensor resid [B H W][256], or -- resid NULL, xs [B H W][64] and ws
+ * [256][64] given -- the bf16 output of conv(xs, ws) computed in the kernel
+ * (the first block's shortcut convolution).  next = 0: y only (wn, bias_n, h
+ * unused).  h is computed from the bf16 y tile while it is on chip, so y is
+ * not read back.  Every output is bitwise what rtdetr_conv_fwd writes in
+ * separate launches (conv(xs, ws) bias-free; y with resid / bias / relu; h with
+ * bias_n / relu).  nwg: workgroups (0 = automatic), each a run of consecutive
+ * 64-pixel tiles. */
+int rtdetr_conv1x1_block_out(const void* h2, const void* w2c, const void* resid, const void* xs, const void* ws,
+                             const float* bias, void* y, const void* wn, const float* bias_n, void* h, int next,
+                             const void* zero, int B, int H, int W, int nwg, hipStream_t stream);
 /* Measurement / A-B knobs (0, or -1 for conv_dgrad_flip, = automatic):
  * "conv_bm" forward pixel-tile rows 64 / 128 / 256; "conv_wg_stages"
  * weight-gradient LDS ring depth 2..4; "conv_wg_splits" weight-gradient pixel

@@ -32,6 +32,9 @@
 //   conv1x1_bwd_kernel both of the above for the 1x1 stride-1 layers of ResNet
 //                      stage 1 ({C, N} = {64, 256}) in one launch that reads dY
 //                      and X once (HBM-bound layers); bitwise the two launches.
+//   stage1_out_kernel  a stage-1 block output (branch2c + residual + bias +
+//                      ReLU), block 1's shortcut convolution and the next
+//                      block's branch2a from the output tile, in one launch.
 // Tiles 128 x 128 x 64, 4 waves (2 x 2), an S-deep LDS-DMA ring (one
 // global_load_lds_dwordx4 per lane per 1 KiB, counted vmcnt waits, raw
 // s_barrier), K-contiguous operand images (fwd) or MN-contiguous ones read by
@@ -1572,6 +1575,284 @@ __global__ __launch_bounds__(256) void conv1x1_bwd_kernel(Conv1x1BwdArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// ResNet stage-1 block output (+ the next block's branch2a) in one launch
+// ---------------------------------------------------------------------------
+// stage1_out_kernel<RC, NEXT>, per 64-pixel tile:
+//   y = relu((bf16(h2 W2c^T) + resid) + bias)          bf16 [P][256]
+//       resid: a tensor [P][256] (RC = false), or bf16(xs Ws^T) computed here
+//       from xs [P][64] (RC = true: block 1's shortcut convolution, whose
+//       output then never crosses HBM)
+//   h = relu(bf16(y Wn^T) + bias_n)                     bf16 [P][NEXT], NEXT > 0
+//       from the bf16 y tile while it is in LDS (the next block's branch2a,
+//       which otherwise reads y straight back)
+// -- bitwise what rtdetr_conv_fwd writes in two (three) launches: the MFMA
+// operand roles and fragment k mapping of conv_fwd_kernel's 32-deep tiles,
+// ascending 32-deep steps from a zero accumulator, conv_epilogue's arithmetic
+// and order of adds (element-wise, so it runs in the accumulator layout here).
+// Wave w owns output channels 64 w .. 64 w + 63 of y (all 64 pixels) and
+// channels NEXT / 4 w .. of h.  The weights are loop-invariant MFMA operands:
+// each wave keeps its rows' fragments in registers (W2c 32, Ws 32, Wn NEXT / 2
+// VGPRs), loaded once from global memory, so LDS holds only the stream: h2 and
+// resid / xs through an S-deep LDS-DMA ring of [64][64] sub-images (sub_swz)
+// that stays in flight across the workgroup's pixel tiles (hand-counted waits,
+// dma16_uncounted).  The y tile is written in place over the resid tile (RC: a
+// separate 32 KiB tile), leaves as 128-B row segments and is the A operand of
+// the second GEMM; h is staged in its own tile and leaves as whole rows.
+// Tail pixels read the zero page and are not stored.  No atomics.
+struct BlockOutArgs {
+  const uint16_t* h2;      // [P][64]
+  const uint16_t* w2c;     // [256][64]
+  const uint16_t* res;     // RC: xs [P][64]; else resid [P][256]
+  const uint16_t* ws;      // RC: [256][64]
+  const float* bias;       // [256]
+  uint16_t* y;             // [P][256]
+  const uint16_t* wn;      // [NEXT][256]
+  const float* bias_n;     // [NEXT]
+  uint16_t* h;             // [P][NEXT]
+  const uint16_t* zero;
+  int P, kt_per;
+};
+
+template <bool RC>
+struct BlockOutCfg {
+  static constexpr int RS = RC ? 1 : 4;            // sub-images of the resid / xs tile
+  static constexpr int S = RC ? 6 : 3;             // ring depth
+  static constexpr int SUB = 64 * 128;
+  static constexpr int STAGE = (1 + RS) * SUB;     // RC 16 KiB, else 40 KiB
+  static constexpr int GW = 2 * (1 + RS);          // DMA instructions per wave per stage
+  static constexpr int YOFF = S * STAGE;           // RC: the y tile behind the ring
+  static constexpr int HOFF = YOFF + (RC ? 4 * SUB : 0);
+  static constexpr size_t lds(int next) { return HOFF + (size_t)(next / 64) * SUB; }
+};
+
+// two packed bf16 -> floats (unpack8's halves)
+__device__ __forceinline__ void unpack2(uint32_t w, float& lo, float& hi) {
+  lo = __uint_as_float(w << 16);
+  hi = __uint_as_float(w & 0xffff0000u);
+}
+
+template <bool RC, int NEXT>
+__global__ __launch_bounds__(256) void stage1_out_kernel(BlockOutArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert(NEXT == 0 || NEXT == 64 || NEXT == 128, "next branch2a: none, 64 or 128 channels");
+  using Cfg = BlockOutCfg<RC>;
+  constexpr int RS = Cfg::RS, S = Cfg::S, SUB = Cfg::SUB, STAGE = Cfg::STAGE, GW = Cfg::GW;
+  static_assert((S - 2) * GW <= 63, "vmcnt range");
+  constexpr int TN2 = NEXT / 64;  // 16-column blocks of h per wave (1 where NEXT = 0: unused)
+  constexpr int T2 = TN2 > 0 ? TN2 : 1;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ktot = (a.P + 63) / 64;
+  const int kt0 = blockIdx.x * a.kt_per;
+  const int nk = max(0, min(a.kt_per, ktot - kt0));
+  if (nk == 0) return;
+  // this wave's weight fragments (conv_fwd_kernel's rd32: row = output channel, 16-B chunk lane >> 4 of the
+  // 32-deep k-step) and this lane's bias values (accumulator layout: columns 16 j + 4 (lane >> 4) + 0..3)
+  const int frow = lane & 15, fk = 8 * (lane >> 4);
+  bf16x8 wc[4][2], wsf[RC ? 4 : 1][2], wnf[T2][8];
+  float bi[4][4], bn[T2][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int n = 64 * wave + 16 * j;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      wc[j][ks] = *reinterpret_cast<const bf16x8*>(a.w2c + (size_t)(n + frow) * 64 + 32 * ks + fk);
+      if constexpr (RC) wsf[j][ks] = *reinterpret_cast<const bf16x8*>(a.ws + (size_t)(n + frow) * 64 + 32 * ks + fk);
+    }
+    const float4 b = *reinterpret_cast<const float4*>(a.bias + n + 4 * (lane >> 4));
+    bi[j][0] = b.x; bi[j][1] = b.y; bi[j][2] = b.z; bi[j][3] = b.w;
+  }
+  if constexpr (NEXT > 0) {
+#pragma unroll
+    for (int j = 0; j < TN2; ++j) {
+      const int n = (NEXT / 4) * wave + 16 * j;
+#pragma unroll
+      for (int k8 = 0; k8 < 8; ++k8)
+        wnf[j][k8] = *reinterpret_cast<const bf16x8*>(a.wn + (size_t)(n + frow) * 256 + 32 * k8 + fk);
+      const float4 b = *reinterpret_cast<const float4*>(a.bias_n + n + 4 * (lane >> 4));
+      bn[j][0] = b.x; bn[j][1] = b.y; bn[j][2] = b.z; bn[j][3] = b.w;
+    }
+  }
+  // the loads above have landed before the first DMA is issued: from here on only the ring and the stores are
+  // in flight, and the hand-counted waits below see every load
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      asm volatile("" : "+v"(wc[j][ks]));
+      if constexpr (RC) asm volatile("" : "+v"(wsf[j][ks]));
+    }
+  if constexpr (NEXT > 0) {
+#pragma unroll
+    for (int j = 0; j < TN2; ++j)
+#pragma unroll
+      for (int k8 = 0; k8 < 8; ++k8) asm volatile("" : "+v"(wnf[j][k8]));
+  }
+  wait_vm<0>();
+  // DMA instruction t = wave + 4 (j & 1) of sub-image j / 2 covers its rows 8 t .. 8 t + 7 (conv1x1_bwd_kernel)
+  const int rowA = 8 * wave + (lane >> 3);
+  const int c8 = ((lane & 7) ^ sub_swz(rowA)) * 8;
+  auto issue = [&](int kt, int slot) {
+    char* buf = smem + slot * STAGE;
+    const long long p0 = (long long)(kt0 + kt) * 64 + rowA;
+#pragma unroll
+    for (int j = 0; j < GW; ++j) {
+      const int sub = j >> 1;
+      const long long p = p0 + 32 * (j & 1);
+      const uint16_t* src = sub == 0 ? a.h2 + (size_t)p * 64 + c8
+                                     : a.res + (size_t)p * (64 * RS) + (sub - 1) * 64 + c8;
+      dma16_uncounted(p < a.P ? src : a.zero + c8, buf + sub * SUB + (wave + 4 * (j & 1)) * 1024);
+    }
+  };
+#pragma unroll
+  for (int s = 0; s < S - 1; ++s)
+    if (s < nk) issue(s, s);
+  char* const hst = smem + Cfg::HOFF;
+  int rslot = 0, islot = S - 1;
+  for (int kt = 0; kt < nk; ++kt) {
+    // tile kt's DMA has landed for this wave: the loads issued after it are those of the min(S - 2,
+    // nk - 1 - kt) tiles behind it (loads return in order; stores are not counted on)
+    {
+      const int newer = min(S - 2, nk - 1 - kt);
+      if (newer >= 4) wait_vm<(S >= 6 ? 4 : 0) * GW>();
+      else if (newer == 3) wait_vm<(S >= 5 ? 3 : 0) * GW>();
+      else if (newer == 2) wait_vm<(S >= 4 ? 2 : 0) * GW>();
+      else if (newer == 1) wait_vm<(S >= 3 ? 1 : 0) * GW>();
+      else wait_vm<0>();
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // ... for every wave; every wave is done with tile kt - 1 (its slot, y, h tiles)
+    char* cur = smem + rslot * STAGE;
+    char* yimg = RC ? smem + Cfg::YOFF : cur + SUB;  // [4 sub-images]: sub-image w = channels 64 w ..
+    const long long p0 = (long long)(kt0 + kt) * 64;
+    if (kt + S - 1 < nk) issue(kt + S - 1, islot);  // refills the slot consumed in iteration kt - 1
+    f32x4 acc[4][4], accs[RC ? 4 : 1][RC ? 4 : 1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (RC) accs[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8 af[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = sub_frag_k(cur, 16 * i, ks, lane);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[j][ks], af[i], acc[i][j], 0, 0, 0);
+      if constexpr (RC) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = sub_frag_k(cur + SUB, 16 * i, ks, lane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            accs[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wsf[j][ks], af[i], accs[i][j], 0, 0, 0);
+      }
+    }
+    // epilogue (conv_epilogue's arithmetic): lane holds y[16 i + (lane & 15)][64 w + 16 j + 4 (lane >> 4) + 0..3];
+    // the resid values leave the wave's sub-image at exactly the bytes the y values go to
+    char* ysub = yimg + wave * SUB;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 16 * i + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = 16 * j + 4 * (lane >> 4);
+        uint2* at = reinterpret_cast<uint2*>(ysub + sub_off(r, col >> 3) + (col & 7) * 2);
+        uint2 q;
+        if constexpr (RC) {
+          q.x = pack2bf(accs[i][j][0], accs[i][j][1]);
+          q.y = pack2bf(accs[i][j][2], accs[i][j][3]);
+        } else {
+          q = *at;
+        }
+        float f[4], g[4];
+        unpack2(pack2bf(acc[i][j][0], acc[i][j][1]), f[0], f[1]);
+        unpack2(pack2bf(acc[i][j][2], acc[i][j][3]), f[2], f[3]);
+        unpack2(q.x, g[0], g[1]);
+        unpack2(q.y, g[2], g[3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          f[e] += g[e];
+          f[e] += bi[j][e];
+          f[e] = fmaxf(f[e], 0.f);
+        }
+        uint2 v;
+        v.x = pack2bf(f[0], f[1]);
+        v.y = pack2bf(f[2], f[3]);
+        *at = v;
+      }
+    }
+    // the wave's sub-image back as 16-B row chunks: row (lane >> 3) + 8 e, chunk lane & 7
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int r = (lane >> 3) + 8 * e;
+      const uint4 v = *reinterpret_cast<const uint4*>(ysub + sub_off(r, lane & 7));
+      const long long p = p0 + r;
+      if (p < a.P) *reinterpret_cast<uint4*>(a.y + (size_t)p * 256 + 64 * wave + (lane & 7) * 8) = v;
+    }
+    if constexpr (NEXT > 0) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // the whole y tile is in LDS
+      f32x4 acc2[4][T2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < TN2; ++j) acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k8 = 0; k8 < 8; ++k8) {
+        bf16x8 af[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = sub_frag_k(yimg + (k8 >> 1) * SUB, 16 * i, k8 & 1, lane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < TN2; ++j)
+            acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wnf[j][k8], af[i], acc2[i][j], 0, 0, 0);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = 16 * i + (lane & 15);
+#pragma unroll
+        for (int j = 0; j < TN2; ++j) {
+          const int col = (NEXT / 4) * wave + 16 * j + 4 * (lane >> 4);
+          float f[4];
+          unpack2(pack2bf(acc2[i][j][0], acc2[i][j][1]), f[0], f[1]);
+          unpack2(pack2bf(acc2[i][j][2], acc2[i][j][3]), f[2], f[3]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            f[e] += bn[j][e];
+            f[e] = fmaxf(f[e], 0.f);
+          }
+          uint2 v;
+          v.x = pack2bf(f[0], f[1]);
+          v.y = pack2bf(f[2], f[3]);
+          *reinterpret_cast<uint2*>(hst + (col >> 6) * SUB + sub_off(r, (col & 63) >> 3) + (col & 7) * 2) = v;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // the whole h tile is in LDS: out as whole rows
+      constexpr int CPRN = NEXT / 8;
+#pragma unroll
+      for (int e = 0; e < NEXT / 32; ++e) {
+        const int idx = tid + 256 * e;
+        const int r = idx / CPRN, c = idx % CPRN;
+        const uint4 v = *reinterpret_cast<const uint4*>(hst + (c >> 3) * SUB + sub_off(r, c & 7));
+        const long long p = p0 + r;
+        if (p < a.P) *reinterpret_cast<uint4*>(a.h + (size_t)p * NEXT + c * 8) = v;
+      }
+    }
+    rslot = rslot + 1 == S ? 0 : rslot + 1;
+    islot = islot + 1 == S ? 0 : islot + 1;
+  }
+}
+
 // (per device; a failure is reported through moe_last_error and the launch
 // that follows fails its check_launch)
 template <auto FN>
@@ -2121,6 +2402,57 @@ extern "C" int rtdetr_conv1x1_bwd(const void* dy, const void* x, const void* w, 
     else launch_conv1x1_bwd<256, 64, false>(a, nsplit, stream, prof);
   }
   return check_launch("rtdetr_conv1x1_bwd");
+}
+
+template <bool RC, int NEXT>
+static void launch_block_out(const BlockOutArgs& a, int grid, hipStream_t stream, ProfScope& prof) {
+  constexpr size_t lds = BlockOutCfg<RC>::lds(NEXT);
+  static_assert(lds <= 160 * 1024, "ring + tiles exceed the CU's LDS");
+  allow_lds_once<stage1_out_kernel<RC, NEXT>>(lds);
+  MOE_LAUNCH(prof, (stage1_out_kernel<RC, NEXT>), dim3(grid), dim3(256), lds, stream, a);
+}
+
+extern "C" int rtdetr_conv1x1_block_out(const void* h2, const void* w2c, const void* resid, const void* xs,
+                                        const void* ws, const float* bias, void* y, const void* wn,
+                                        const float* bias_n, void* h, int next, const void* zero, int B, int H, int W,
+                                        int nwg, hipStream_t stream) {
+  const char* what = "rtdetr_conv1x1_block_out";
+  const void* ptrs[5] = {h2, w2c, bias, y, zero};
+  if (int rc = conv_check(ptrs, 5, B, H, W, 64, 256, 1, 1, what)) return rc;
+  if ((resid != nullptr) == (xs != nullptr)) return fail(std::string(what) + ": give resid or (xs, ws), not both");
+  if (xs != nullptr && ws == nullptr) return fail(std::string(what) + ": xs without ws");
+  if (next != 0 && next != 64 && next != 128) return fail(std::string(what) + ": next must be 0, 64 or 128");
+  if (next != 0 && (wn == nullptr || bias_n == nullptr || h == nullptr))
+    return fail(std::string(what) + ": next without wn / bias_n / h");
+  if (!aligned16(resid) || !aligned16(xs) || !aligned16(ws) || !aligned16(wn) || !aligned16(bias_n) || !aligned16(h))
+    return fail(std::string(what) + ": operands must be 16-B aligned");
+  if (nwg < 0) return fail(std::string(what) + ": nwg must be >= 0 (0 = automatic)");
+  if (B == 0) return 0;
+  const bool rc_ = xs != nullptr;
+  BlockOutArgs a{static_cast<const uint16_t*>(h2), static_cast<const uint16_t*>(w2c),
+                 static_cast<const uint16_t*>(rc_ ? xs : resid), static_cast<const uint16_t*>(ws), bias,
+                 static_cast<uint16_t*>(y), static_cast<const uint16_t*>(wn), bias_n, static_cast<uint16_t*>(h),
+                 static_cast<const uint16_t*>(zero), B * H * W, 0};
+  // one workgroup per CU, each a run of consecutive 64-pixel tiles
+  const int ktot = (a.P + 63) / 64;
+  const int want = std::min(ktot, nwg > 0 ? nwg : 256);
+  a.kt_per = (ktot + want - 1) / want;
+  const int grid = (ktot + a.kt_per - 1) / a.kt_per;
+  const double P = a.P;
+  // h2, resid / xs in; y, h out; the weights
+  ProfScope prof(stream, PROF_CONV,
+                 2.0 * P * (64 + (rc_ ? 64 : 256) + 256 + next) + 2.0 * 64 * 256 * (rc_ ? 2 : 1) + 2.0 * next * 256,
+                 false, 0.0, 2.0 * P * 256 * (64.0 * (rc_ ? 2 : 1) + next));
+  if (rc_) {
+    if (next == 0) launch_block_out<true, 0>(a, grid, stream, prof);
+    else if (next == 64) launch_block_out<true, 64>(a, grid, stream, prof);
+    else launch_block_out<true, 128>(a, grid, stream, prof);
+  } else {
+    if (next == 0) launch_block_out<false, 0>(a, grid, stream, prof);
+    else if (next == 64) launch_block_out<false, 64>(a, grid, stream, prof);
+    else launch_block_out<false, 128>(a, grid, stream, prof);
+  }
+  return check_launch(what);
 }
 
 extern "C" int rtdetr_conv3x3_direct_fwd(const void* x, const float* wf, const float* bias, void* y, int B, int H,

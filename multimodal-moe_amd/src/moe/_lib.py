@@ -148,6 +148,7 @@ SIGNATURES = {
     "rtdetr_conv_wgrad_part": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rtdetr_conv_wgrad_reduce_batch": (_I, [_I, _P, _P, _P, _P, _I, _P]),
     "rtdetr_conv1x1_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "rtdetr_conv1x1_block_out": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "train_grad_pack": (_I, [_P, _P, _I, _P, _P]),
     "train_grad_accum": (_I, [_P, _P, _I, _P, _I, _P]),
     "train_grad_sqnorm": (_I, [_P, _P, _I, _P, _P]),

@@ -17,7 +17,8 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
-from .conv import conv2d, conv2d_add_bias_relu_fork, conv2d_bias_relu, conv_module, conv_module_stats, hip_conv_ok_for
+from .conv import (chain_short_ok, conv2d, conv2d_add_bias_relu_fork, conv2d_bias_relu,
+                   conv2d_short_add_bias_relu_fork, conv_module, conv_module_stats, hip_conv_ok_for, take_parked)
 from .fused import AddBiasReLU, AddBiasReLUFork, BiasReLU, bn_act, bn_act_eval, bn_act_ok, bn_eval_ok
 
 _FUSED_BN = os.environ.get("MOE_FUSED_BN", "1") != "0"  # A/B switch: training BN + SiLU in HIP
@@ -231,6 +232,16 @@ class ConvNormLayer(nn.Module):
             w = _FoldScale.apply(self.conv.weight, scale)
         return w, shift
 
+    def peek_folded(self):
+        """(W * scale, shift) of this step as folded() will return them, without
+        consuming the folded weight: for the previous block, whose output launch
+        also computes this layer (conv.conv2d_add_bias_relu_fork, nxt).  None
+        when no folded weight was made ahead (folded() would make a new one)."""
+        w = getattr(self, "_w_folded", None)
+        if w is None or not self.fold:
+            return None
+        return w, self.norm.scale_shift()[1]
+
     def conv_shift(self, x, folded=None):
         """Frozen BN: (conv(x, W * scale), shift) -- the BN output minus its shift."""
         w, shift = folded if folded is not None else self.folded()
@@ -244,10 +255,13 @@ class ConvNormLayer(nn.Module):
 
     def bias_relu(self, x, folded, mask_input=False, grad_premasked=False, link=None):
         """relu(BN(conv(x))) with the frozen BN folded: one HIP launch when
-        fused (hip_ok), else conv + the BiasReLU kernel."""
+        fused (hip_ok), else conv + the BiasReLU kernel.  When x's producer
+        already computed this very layer in its own launch (take_parked), the
+        HIP path takes that output and launches nothing."""
         w, shift = folded
         if mask_input or grad_premasked or self.hip_ok(x, x.shape[1], w):
-            return conv2d_bias_relu(x, w, shift, mask_input, grad_premasked, link, self.conv.stride)
+            out = take_parked(x, folded) if self.conv.kernel_size == (1, 1) else None
+            return conv2d_bias_relu(x, w, shift, mask_input, grad_premasked, link, self.conv.stride, out)
         y, _ = self.conv_shift(x, folded)
         return BiasReLU.apply(y, shift)
 
@@ -435,19 +449,27 @@ def _fork_ok(short):
     return not _NO_FORK and (short is None or short.conv.fold)
 
 
-def _block_out(last, short, h, x, folded_last=None, mask_input=False, link_in=None, short_link=None):
+def _block_out(last, short, h, x, folded_last=None, mask_input=False, link_in=None, short_link=None, next_a=None):
     """relu(last(h) + shortcut(x)) as a (main, shortcut) pair of handles on the
     same activation (see fused.AddBiasReLUFork).  With frozen BNs the two BN
     shifts join the residual add and the ReLU in one fused kernel -- the
     epilogue of last's HIP convolution when it has one (folded_last given and
-    hip_ok; mask_input: h is a ReLU output only last consumes)."""
+    hip_ok; mask_input: h is a ReLU output only last consumes).  next_a: the
+    next block's branch2a layer, which the same launch computes as well at the
+    ResNet stage-1 shapes -- as it does a stride-1 shortcut convolution there
+    (conv.MOE_CONV_CHAIN)."""
     if last.fold and _fork_ok(short) and folded_last is not None:
         wl, sl = folded_last
         if mask_input or last.hip_ok(h, h.shape[1], wl):
+            nxt = next_a.peek_folded() if next_a is not None and next_a.act_name == "relu" else None
+            if short is not None and not short.down and short.conv.fold and short.conv.conv.stride == (1, 1):
+                if chain_short_ok(h, wl, x, short.conv.conv.weight):
+                    ws, ss = short.conv.folded()
+                    return conv2d_short_add_bias_relu_fork(h, wl, x, ws, sl + ss, mask_input, nxt)
             b, bias = (x, sl) if short is None else short.conv_shift(x, short_link)
             if short is not None:
                 bias = sl + bias
-            return conv2d_add_bias_relu_fork(h, wl, b, bias, mask_input, link_in if short is None else None)
+            return conv2d_add_bias_relu_fork(h, wl, b, bias, mask_input, link_in if short is None else None, nxt)
     if mask_input:  # the producer skipped its ReLU backward for the fork path's dgrad mask
         raise RuntimeError("_block_out: mask_input set but the fused fork path does not run")
     if last.fold and (short is None or short.conv.fold):
@@ -491,9 +513,10 @@ class BasicBlock(nn.Module):
         self.branch2a = ConvNormLayer(cin, cout, 3, stride, "relu", frozen)
         self.branch2b = ConvNormLayer(cout, cout, 3, 1, None, frozen)
 
-    def forward(self, x, x_short=None):
+    def forward(self, x, x_short=None, next_a=None):
         """x feeds branch2a, x_short (default x) the shortcut; returns the
-        (main, shortcut) handles of the output."""
+        (main, shortcut) handles of the output.  (next_a: see BottleNeck;
+        unused here.)"""
         xs = x if x_short is None else x_short
         a, b = self.branch2a, self.branch2b
         if _FUSED_EPI and a.fold and b.fold and a.act_name == "relu" and x.is_cuda:
@@ -518,13 +541,15 @@ class BottleNeck(nn.Module):
         self.branch2c = ConvNormLayer(width, cout * 4, 1, 1, None, frozen)
         self.short = None if shortcut else _Shortcut(cin, cout * 4, stride, frozen)
 
-    def forward(self, x, x_short=None):
+    def forward(self, x, x_short=None, next_a=None):
         """x feeds branch2a, x_short (default x) the shortcut; returns the
         (main, shortcut) handles of the output.  Fused (frozen BNs, HIP
         convolutions): each branch's shift + ReLU is its convolution's
         epilogue, the block output's residual add + ReLU is branch2c's, and
         branch2a's / branch2b's ReLU backwards run in the dgrad epilogue of the
-        next convolution (their only consumer) where that one is HIP too."""
+        next convolution (their only consumer) where that one is HIP too.
+        next_a: the branch2a layer of the block that consumes this output
+        (PResNet.forward), for _block_out."""
         xs = x if x_short is None else x_short
         a, b, c = self.branch2a, self.branch2b, self.branch2c
         if _FUSED_EPI and a.fold and b.fold and c.fold and x.is_cuda:
@@ -537,7 +562,7 @@ class BottleNeck(nn.Module):
             h1 = a.bias_relu(x, fa, grad_premasked=pre_ab, link=link)
             h2 = b.bias_relu(h1, fb, mask_input=pre_ab, grad_premasked=pre_bc)
             return _block_out(c, self.short, h2, xs, fc, mask_input=pre_bc, link_in=link,
-                              short_link=link if self.short is not None else None)
+                              short_link=link if self.short is not None else None, next_a=next_a)
         return _block_out(self.branch2c, self.short, self.branch2b(self.branch2a(x)), xs)
 
 
@@ -643,9 +668,13 @@ class PResNet(nn.Module):
         x = stem_max_pool(self._stem(x), self.pool)
         xs = None
         outs = []
+        # each block is told the branch2a layer that consumes its output (the next
+        # block's, across stage boundaries too): see _block_out
+        blocks = [blk for stage in self.stages for blk in stage]
+        nexts = iter([getattr(b, "branch2a", None) for b in blocks[1:]] + [None])
         for i, stage in enumerate(self.stages):
             for blk in stage:
-                x, xs = blk(x, xs)
+                x, xs = blk(x, xs, next(nexts))
             if i in self.return_idx:
                 outs.append(x)
         # returned outputs whose gradient the next stage finishes through a

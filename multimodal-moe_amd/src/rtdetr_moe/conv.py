@@ -15,7 +15,11 @@ read in place for small ones); the weight gradient is split over pixel slices
 with fp32 partials summed in a fixed order (deterministic).  The 1x1 layers of
 ResNet stage 1 ({C, N} = {64, 256}) take both gradients from one launch that
 reads g and x once (rtdetr_conv1x1_bwd, bitwise the two; MOE_CONV_BWD_FUSE=0
-keeps the two launches).
+keeps the two launches).  The forward of a stage-1 block output (branch2c +
+residual + shift + ReLU) also computes the next block's branch2a from the
+output tile, and the first block's shortcut convolution, in the same launch
+(rtdetr_conv1x1_block_out, bitwise the separate launches; MOE_CONV_CHAIN=0
+keeps those).
 MOE_HIP_CONV=0 keeps every convolution on MIOpen (A/B switch).
 """
 from __future__ import annotations
@@ -82,6 +86,78 @@ def _fwd(x, w, bias=None, resid=None, relu=False, st=1):
                                      None if resid is None else resid.data_ptr(), int(relu), L._stream()),
              "rtdetr_conv_fwd")
     return y
+
+
+# MOE_CONV_CHAIN=0: a ResNet stage-1 block output, the first block's shortcut
+# convolution and the next block's branch2a as separate launches instead of
+# the one rtdetr_conv1x1_block_out launch (A/B switch; bitwise equal)
+_CHAIN_ON = os.environ.get("MOE_CONV_CHAIN", "1") != "0"
+
+
+def _chain_ok(x, w, bias) -> bool:
+    """Whether a block output y = relu((conv(x, w) + resid) + bias) is at the
+    shape of rtdetr_conv1x1_block_out (1x1, 64 -> 256, bf16 on the GPU)."""
+    return (_CHAIN_ON and bias is not None and x.is_cuda and x.dim() == 4 and x.shape[0] > 0 and x.shape[1] == 64
+            and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and tuple(w.shape) == (256, 64, 1, 1))
+
+
+def _chain_next_ok(nxt) -> bool:
+    """nxt = (folded weight, shift) of the next block's branch2a: a bf16 1x1
+    256 -> 64 / 128 weight the kernel has an instance for."""
+    if nxt is None:
+        return False
+    wn = nxt[0]
+    return (wn.is_cuda and wn.dtype == torch.bfloat16 and wn.dim() == 4 and tuple(wn.shape[1:]) == (256, 1, 1)
+            and wn.shape[0] in (64, 128) and wn.data_ptr() % 16 == 0)
+
+
+def _fwd_block_out(x, w, bias, resid=None, xs=None, ws=None, nxt=None):
+    """(y, h) of one rtdetr_conv1x1_block_out launch: y = relu((conv(x, w) +
+    r) + bias) with r = resid or the bf16 conv(xs, ws); h = relu(conv(y, wn) +
+    bias_n) for nxt = (wn, bias_n fp32), else None."""
+    from ..moe import _lib as L
+
+    B, _, H, W = x.shape
+    y = torch.empty((B, 256, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    h = wn = bn = None
+    if nxt is not None:
+        wn, bn = nxt
+        h = torch.empty((B, wn.shape[0], H, W), dtype=torch.bfloat16, device=x.device,
+                        memory_format=torch.channels_last)
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    L._check(L.lib().rtdetr_conv1x1_block_out(x.data_ptr(), w.data_ptr(), p(resid), p(xs), p(ws), bias.data_ptr(),
+                                              y.data_ptr(), p(wn), p(bn), p(h), 0 if wn is None else wn.shape[0],
+                                              _zero(x.device).data_ptr(), B, H, W, 0, L._stream()),
+             "rtdetr_conv1x1_block_out")
+    return y, h
+
+
+def _park_next(link, h, nxt):
+    """Park the next block's branch2a output on the block output's GradLink,
+    with what identifies the weight and shift it was computed from."""
+    if h is not None:
+        wn, shift = nxt
+        link.h_next = (h, wn, wn._version, shift, shift._version)
+
+
+def take_parked(x, folded):
+    """The branch2a output a producing block parked on x (a block output made
+    by rtdetr_conv1x1_block_out) for the folded pair (w, shift) -- only when w
+    and shift are the very tensors the producer computed it from, unchanged
+    since; else None (the convolution launches as usual)."""
+    link = getattr(x, "grad_link", None)
+    p = getattr(link, "h_next", None) if link is not None else None
+    if p is None:
+        return None
+    link.h_next = None
+    h, wn, vw, sn, vs = p
+    w, shift = folded
+    same_w = w is wn or (w.data_ptr() == wn.data_ptr() and w.shape == wn.shape and w.dtype == wn.dtype
+                         and w.stride() == wn.stride())
+    if same_w and w._version == vw and shift is sn and shift._version == vs and h.shape[0] == x.shape[0] \
+            and h.shape[2:] == x.shape[2:]:
+        return h
+    return None
 
 
 def conv_act_eval(x, w, bias, act, resid=None, st=1, out=None, out_row=0):
@@ -369,9 +445,12 @@ class GradLink:
     it, adds g_s and applies the mask in its dgrad epilogue and marks the
     result final; y's fork then takes it as is (no rtdetr_relu_grad2 pass)."""
 
-    __slots__ = ("g_short", "final", "g_ext", "ext_used")
+    __slots__ = ("g_short", "final", "g_ext", "ext_used", "h_next")
 
     def __init__(self):
+        # forward only: the next block's branch2a output, computed with this
+        # block output by rtdetr_conv1x1_block_out (_park_next / take_parked)
+        self.h_next = None
         self.g_short = None
         self.final = False
         # a returned stage output's gradient from its external consumer (the
@@ -393,10 +472,11 @@ class _ConvHIP(torch.autograd.Function):
     gradient is already masked (no threshold pass here)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias=None, relu=False, mask_input=False, grad_premasked=False, link=None, st=1):
+    def forward(ctx, x, w, bias=None, relu=False, mask_input=False, grad_premasked=False, link=None, st=1, out=None):
         x = _nhwc(x)
         w = _nhwc(w)
-        y = _fwd(x, w, bias, None, relu, st)
+        # out: this very output, already computed by x's producer (take_parked)
+        y = out if out is not None else _fwd(x, w, bias, None, relu, st)
         ctx.st = st
         ctx.flags = (bool(relu) and not grad_premasked, bool(mask_input))
         ctx.link = link  # x is a block output (GradLink): finish its gradient here when the hand-off is there
@@ -413,7 +493,7 @@ class _ConvHIP(torch.autograd.Function):
             add, mask_input = link.g_short, True
             link.g_short, link.final = None, True
         gx, gw = _bwd(x, w, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1], mask_input, add, ctx.st)
-        return gx, gw, None, None, None, None, None, None
+        return gx, gw, None, None, None, None, None, None, None
 
 
 class _ConvHIPFork(torch.autograd.Function):
@@ -424,10 +504,14 @@ class _ConvHIPFork(torch.autograd.Function):
     the gradient of both the convolution output and resid."""
 
     @staticmethod
-    def forward(ctx, x, w, resid, bias, mask_input=False, link_in=None, link_out=None):
+    def forward(ctx, x, w, resid, bias, mask_input=False, link_in=None, link_out=None, nxt=None):
         x = _nhwc(x)
         w = _nhwc(w)
-        y = _fwd(x, w, bias, _nhwc(resid), True)
+        if nxt is not None:  # (checked by the caller) with the next block's branch2a, parked on link_out
+            y, h = _fwd_block_out(x, w, bias, resid=_nhwc(resid), nxt=(nxt[0], nxt[1].float().contiguous()))
+            _park_next(link_out, h, nxt)
+        else:
+            y = _fwd(x, w, bias, _nhwc(resid), True)
         ctx.set_materialize_grads(False)  # an unused handle: no zero-filled gradient
         ctx.mask_input = bool(mask_input)
         ctx.links = (link_in, link_out)  # link_in: resid is the previous block's output (identity shortcut)
@@ -456,14 +540,64 @@ class _ConvHIPFork(torch.autograd.Function):
             if ext is not None:
                 dy1 = ext if dy1 is None else dy1 + ext
             if dy1 is None and dy2 is None:
-                return None, None, None, None, None, None, None
+                return None, None, None, None, None, None, None, None
             if dy1 is None:
                 dy1, dy2 = dy2, None
             g = L.relu_grad2_nhwc(_nhwc(dy1), None if dy2 is None else _nhwc(dy2), y)
         if link_in is not None:
             link_in.g_short = g
         gx, gw = _bwd(x, w, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.mask_input)
-        return gx, gw, g if ctx.needs_input_grad[2] else None, None, None, None, None
+        return gx, gw, g if ctx.needs_input_grad[2] else None, None, None, None, None, None
+
+
+class _ConvHIPForkShort(torch.autograd.Function):
+    """_ConvHIPFork for a block whose shortcut is a 1x1 stride-1 convolution of
+    xs (ResNet stage 1, block 1): resid = conv(xs, ws) is computed inside the
+    rtdetr_conv1x1_block_out launch and never written.  Backward: the fork's,
+    plus the shortcut convolution's own (_bwd(xs, ws, g): what its separate
+    _ConvHIP node ran, on the same g)."""
+
+    @staticmethod
+    def forward(ctx, x, w, xs, ws, bias, mask_input=False, link_out=None, nxt=None):
+        x, xs = _nhwc(x), _nhwc(xs)
+        w, ws = _nhwc(w), _nhwc(ws)
+        y, h = _fwd_block_out(x, w, bias, xs=xs, ws=ws,
+                              nxt=None if nxt is None else (nxt[0], nxt[1].float().contiguous()))
+        _park_next(link_out, h, nxt)
+        ctx.set_materialize_grads(False)
+        ctx.mask_input = bool(mask_input)
+        ctx.link_out = link_out
+        ctx.save_for_backward(x, w, xs, ws, y)
+        return y, y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, dy1, dy2):
+        from ..moe import _lib as L
+
+        x, w, xs, ws, y = ctx.saved_tensors
+        link_out = ctx.link_out
+        ext = None
+        if link_out.g_ext is not None and not link_out.ext_used:
+            ext = link_out.g_ext
+        link_out.g_ext, link_out.ext_used = None, False
+        if link_out.final:
+            g = dy1  # the next block's branch2a dgrad already added dy2 and masked (GradLink)
+            link_out.final = False
+            if ext is not None:
+                g = g + torch.where(y > 0, ext, torch.zeros_like(ext))
+        else:
+            link_out.g_short = None
+            if ext is not None:
+                dy1 = ext if dy1 is None else dy1 + ext
+            if dy1 is None and dy2 is None:
+                return None, None, None, None, None, None, None, None
+            if dy1 is None:
+                dy1, dy2 = dy2, None
+            g = L.relu_grad2_nhwc(_nhwc(dy1), None if dy2 is None else _nhwc(dy2), y)
+        need = ctx.needs_input_grad
+        gx, gw = _bwd(x, w, g, need[0], need[1], ctx.mask_input)
+        gxs, gws = _bwd(xs, ws, g, need[2], need[3], False)
+        return gx, gw, gxs, gws, None, None, None, None
 
 
 class GradSlot:
@@ -642,23 +776,47 @@ def conv2d(x, weight, stride=1, padding=0):
     return F.conv2d(x, weight, None, stride, padding)
 
 
-def conv2d_bias_relu(x, weight, bias, mask_input=False, grad_premasked=False, link=None, stride=1):
+def conv2d_bias_relu(x, weight, bias, mask_input=False, grad_premasked=False, link=None, stride=1, out=None):
     """relu(conv2d(x, weight) + bias[c]) in one HIP launch (padding (k-1)/2;
     the caller checked hip_conv_ok).  bias: fp32 [Cout], no gradient.
     See _ConvHIP for mask_input / grad_premasked, GradLink for link (x a
-    block output whose other consumer is the identity shortcut)."""
+    block output whose other consumer is the identity shortcut).  out: the
+    result, already computed with x by its producer (take_parked): no launch."""
     return _ConvHIP.apply(x, weight, bias.float().contiguous(), True, mask_input, grad_premasked, link,
-                          _stride(stride))
+                          _stride(stride), out)
 
 
-def conv2d_add_bias_relu_fork(x, weight, resid, bias, mask_input=False, link_in=None):
+def conv2d_add_bias_relu_fork(x, weight, resid, bias, mask_input=False, link_in=None, nxt=None):
     """(y, y) with y = relu((conv2d(x, weight) + resid) + bias[c]) in one HIP
     launch -- see _ConvHIPFork.  link_in: resid is the previous block's output
     through an identity shortcut (GradLink).  y carries the GradLink for the
-    next block as y.grad_link."""
+    next block as y.grad_link.  nxt: the next block's folded branch2a pair
+    (weight, shift); at the ResNet stage-1 shapes (MOE_CONV_CHAIN) the same
+    launch computes that layer's output too and parks it on the link."""
     link_out = GradLink()
-    y, y2 = _ConvHIPFork.apply(x, weight, resid, None if bias is None else bias.float().contiguous(), mask_input,
-                               link_in, link_out)
+    bias = None if bias is None else bias.float().contiguous()
+    if not (_chain_ok(x, weight, bias) and _chain_next_ok(nxt) and resid.dtype == torch.bfloat16
+            and tuple(resid.shape) == (x.shape[0], 256) + tuple(x.shape[2:])):
+        nxt = None
+    y, y2 = _ConvHIPFork.apply(x, weight, resid, bias, mask_input, link_in, link_out, nxt)
+    y.grad_link = link_out
+    return y, y2
+
+
+def chain_short_ok(x, weight, xs, ws) -> bool:
+    """Whether conv2d_short_add_bias_relu_fork takes this block (MOE_CONV_CHAIN,
+    the ResNet stage-1 shapes: both convolutions 1x1, 64 -> 256, bf16)."""
+    return (_chain_ok(x, weight, True) and xs.is_cuda and xs.dtype == torch.bfloat16 and ws.dtype == torch.bfloat16
+            and tuple(ws.shape) == (256, 64, 1, 1) and tuple(xs.shape) == tuple(x.shape)
+            and not (torch.is_autocast_enabled("cuda") and xs.dtype != torch.get_autocast_dtype("cuda")))
+
+
+def conv2d_short_add_bias_relu_fork(x, weight, xs, ws, bias, mask_input=False, nxt=None):
+    """conv2d_add_bias_relu_fork with resid = conv2d(xs, ws) computed in the
+    same launch (_ConvHIPForkShort; the caller checked chain_short_ok)."""
+    link_out = GradLink()
+    y, y2 = _ConvHIPForkShort.apply(x, weight, xs, ws, bias.float().contiguous(), mask_input, link_out,
+                                    nxt if _chain_next_ok(nxt) else None)
     y.grad_link = link_out
     return y, y2
 
