@@ -868,6 +868,41 @@ int rtdetr_nms_merge(const float* boxes, const float* scores, const int32_t* lab
                      float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* out_src,
                      int32_t* count, hipStream_t stream);
 
+/* Box fusion of tiled prediction (engine.predict(..., merge="fuse")): the walk
+ * of rtdetr_nms_merge, after which every kept box (a leader) is averaged with
+ * the copies it suppressed that agree with it (merge.fuse_reference on the
+ * host, bit for bit).  One launch per batch, one workgroup per image, LDS only.
+ * The arguments of rtdetr_nms_merge, and: fuse_thr; windows fp32 [B][P][4]
+ * (x0, y0, x1, y1; 16-byte aligned; row 0 the frame, rows 1..P-1 the tile
+ * windows, in the boxes' pixel units) or NULL with P == 0; with P > 0, N = P k
+ * and candidate i belongs to pass i / k.
+ *   1. A visited, suppressed candidate joins the first leader in kept order
+ *      that suppresses it; candidates past the max_det-th kept one are not
+ *      visited and join nothing.
+ *   2. It fuses if, both boxes clamped coordinate by coordinate into the
+ *      intersection V of the two passes' windows (no clamp with P == 0),
+ *      inter > fuse_thr * ((area_i + area_j) - inter).  The leader always fuses.
+ *   3. Side s of a candidate of pass p > 0 is cut if it lies on an edge of W_p
+ *      that is not an edge of W_0 (x1: x1 <= W_p.x0 and W_p.x0 > W_0.x0, ...).
+ *   4. Per leader and side, over the fusing candidates in visit order, leader
+ *      first: one contributes if the side is not cut and its score is finite
+ *      and > 0; num += score * coord, den += score (fp32, each operation
+ *      rounded on its own); the side is num / den (correctly rounded) if den >
+ *      0, else the leader's; with P > 0 it is clamped into W_0; an axis that
+ *      comes out unordered keeps both of the leader's coordinates.
+ * out_src, count, out_scores and out_labels are rtdetr_nms_merge's on the same
+ * inputs; out_boxes holds the fused boxes; out_members int32 [B][max_det] the
+ * fusing candidates of each row, leader included (0 on the rows past count).
+ * Every output element is written.  Limits: those of rtdetr_nms_merge, P <= 64
+ * (63.2 KiB of LDS at the largest); fuse_thr not NaN.  A bad argument returns
+ * non-zero before any launch; B == 0 returns 0 without a launch; N == 0 writes
+ * the empty outputs. */
+int rtdetr_box_fuse(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                    int B, int N, float conf, float thr, int metric, int class_agnostic, int max_det,
+                    float fuse_thr, const float* windows, int P, float* out_boxes, float* out_scores,
+                    int32_t* out_labels, int32_t* out_src, int32_t* count, int32_t* out_members,
+                    hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -1228,7 +1263,7 @@ enum moe_prof_kind {
   MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match) */
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
-  MOE_PROF_MERGE = 19      /* tiled prediction: the passes' detections merged (rtdetr_nms_merge) */
+  MOE_PROF_MERGE = 19      /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

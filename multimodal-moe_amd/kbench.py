@@ -12,6 +12,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --route-stats the routing-statistics kernel against its torch reference
   python multimodal-moe_amd/kbench.py --resize      the inference resize kernel against the host resize it replaces
   python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
+  python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -613,6 +614,87 @@ def nms_merge_leg(reps, rounds):
         print(json.dumps(line), flush=True)
 
 
+def box_fuse_leg(reps, rounds):
+    """rtdetr_box_fuse on the candidates of --nms-merge (B 16, N 1500, max_det
+    300, "ios" 0.5, conf 0.25), laid out as 5 passes of k 300 with the 2 x 2
+    windows of a 3848 x 2168 frame, fuse_thr 0.55: checked equal to
+    merge.fuse_reference first, then fuse_kernel_us and nms_kernel_us
+    (rtdetr_nms_merge on the same inputs; dispatch-stamped kernel time per
+    launch) and forward_replay_us (one EvalForward graph replay at batch 16,
+    rtdetr-r50-moe8-top2, 704 x 1248), alternated in each round; median, min
+    and max over the rounds."""
+    import numpy as np
+
+    from src.rtdetr_moe import engine
+    from src.rtdetr_moe.merge import fuse_reference, tile_windows
+    from src.rtdetr_moe.model import RTDETRMoE
+
+    B, N, max_det, conf, thr, metric, fuse_thr = 16, 1500, 300, 0.25, 0.5, "ios", 0.55
+    rng = np.random.default_rng(0)  # nms_merge_leg's draw
+    M = N // 6
+    cx, cy = rng.uniform(100, 3748, (B, M)), rng.uniform(120, 2048, (B, M))
+    h = rng.uniform(40, 200, (B, M))
+    which = rng.integers(0, M, (B, N))
+    take = lambda a: np.take_along_axis(a, which, 1)  # noqa: E731
+    jit = rng.normal(0.0, 3.0, (B, N, 4))
+    x1, y1 = take(cx) - 0.2 * take(h) + jit[..., 0], take(cy) - 0.5 * take(h) + jit[..., 1]
+    x2, y2 = take(cx) + 0.2 * take(h) + jit[..., 2], y1 + take(h) * rng.uniform(0.6, 1.0, (B, N)) + jit[..., 3]
+    boxes = np.stack([x1, y1, x2, y2], -1).astype(np.float32)
+    scores = (rng.integers(0, 64, (B, N)) / 64.0).astype(np.float32)
+    labels = rng.integers(0, 2, (B, N)).astype(np.int32)
+    win = np.asarray([(0, 0, 3848, 2168)] + [(x0, y0, x0 + tw, y0 + th)
+                                             for x0, y0, tw, th in tile_windows(3848, 2168, (2, 2), 0.2)], np.float32)
+    windows = np.broadcast_to(win, (B, 5, 4)).copy()
+    db, ds, dl, dw = (torch.from_numpy(a).cuda() for a in (boxes, scores, labels, windows))
+
+    out = tuple(t.cpu() for t in L.box_fuse(db, ds, dl, None, conf, thr, metric, max_det, False, fuse_thr, dw))
+    members = 0
+    for b in range(B):
+        kept, fused, mem = fuse_reference(boxes[b], scores[b], labels[b], None, conf, thr, metric, max_det, False,
+                                          fuse_thr, win)
+        n = len(kept)
+        if (int(out[4][b]) != n or out[3][b, :n].tolist() != kept.tolist()
+                or not np.array_equal(out[0][b, :n].numpy().view(np.int32), fused.view(np.int32))
+                or out[5][b, :n].tolist() != mem.tolist()):
+            raise SystemExit(f"box_fuse differs from fuse_reference (image {b})")
+        members += int(mem.sum())
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    res = {"fuse_kernel_us": [], "nms_kernel_us": [], "forward_replay_us": []}
+    for _ in range(rounds):
+        res["fuse_kernel_us"].append(timed(
+            lambda: L.box_fuse(db, ds, dl, None, conf, thr, metric, max_det, False, fuse_thr, dw), reps))
+        res["nms_kernel_us"].append(timed(lambda: L.nms_merge(db, ds, dl, None, conf, thr, metric, max_det), reps))
+        res["forward_replay_us"].append(replay_us())
+    line = {"kernel": "rtdetr_box_fuse",
+            "shape": f"B{B} N{N} P5 max_det{max_det} {metric} thr{thr} fuse_thr{fuse_thr} conf{conf}",
+            "take_part": int((scores >= conf).sum()), "kept": int(out[4].sum()), "members": members}
+    for k, v in res.items():
+        line[k] = round(statistics.median(v), 3)
+        line[k + "_min"] = round(min(v), 3)
+        line[k + "_max"] = round(max(v), 3)
+    line["fuse_over_nms"] = round(line["fuse_kernel_us"] / line["nms_kernel_us"], 2)
+    line["fuse_share_of_forward"] = round(line["fuse_kernel_us"] / line["forward_replay_us"], 4)
+    print(json.dumps(line), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -670,6 +752,9 @@ def main():
     ap.add_argument("--nms-merge", action="store_true",
                     help="time rtdetr_nms_merge (B 16, N 1500, max_det 300) against merge.merge_reference on the host "
                          "and one EvalForward replay, and exit")
+    ap.add_argument("--box-fuse", action="store_true",
+                    help="time rtdetr_box_fuse (B 16, 5 passes of 300, max_det 300) against rtdetr_nms_merge on the "
+                         "same inputs and one EvalForward replay, after checking it against merge.fuse_reference")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -709,6 +794,9 @@ def main():
         return
     if a.nms_merge:
         nms_merge_leg(a.reps, a.rounds)
+        return
+    if a.box_fuse:
+        box_fuse_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

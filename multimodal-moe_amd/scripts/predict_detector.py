@@ -41,6 +41,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--merge-metric", type=str, default="ios", choices=("ios", "iou"),
                     help="ios: intersection over the smaller box; iou: over the union")
     ap.add_argument("--class-agnostic", action="store_true", help="merge across labels")
+    ap.add_argument("--merge", type=str, default="nms", choices=("nms", "fuse"),
+                    help="nms: keep the best copy of every object; fuse (with --tiles): average it with its other copies")
+    ap.add_argument("--fuse-iou", type=float, default=0.55,
+                    help="--merge fuse: how well a copy must agree with the kept box to be averaged in")
     return ap.parse_args(argv)
 
 
@@ -52,7 +56,7 @@ def main(argv=None) -> None:
                          max_det=a.max_det, contexts=a.context, workers=a.workers, project=str(RUNS_DIR / "rtdetr"),
                          name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
                          tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
-                         class_agnostic=a.class_agnostic)
+                         class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou)
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
     print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))

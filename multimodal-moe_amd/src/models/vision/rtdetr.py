@@ -123,6 +123,8 @@ def predict_rtdetr_detector(
     merge_iou: float = 0.5,
     merge_metric: str = "ios",
     class_agnostic: bool = False,
+    merge: str = "nms",
+    fuse_iou: float = 0.55,
 ):
     """Detect on image files (a directory, a glob, a list of paths or a dataset
     yaml) of any size; returns a results object with ``.predictions`` (per
@@ -131,11 +133,15 @@ def predict_rtdetr_detector(
     results format when ``project`` and ``name`` are given) and ``.model``.
     ``tiles=(rows, cols)`` (or "RxC") adds sliced inference: every frame is
     also detected on an overlapping grid of crops and the passes are merged
-    (engine.predict); ``.predictions[i].source`` then names each row's pass."""
+    (engine.predict); ``.predictions[i].source`` then names each row's pass.
+    ``merge="fuse"`` (with tiles) keeps the same rows and averages each box with
+    the copies of its object at ``fuse_iou``; ``.predictions[i].members`` then
+    counts the boxes averaged into each row."""
     eng = _engine()
     return eng.predict(_check_model_name(weights_path), source, imgsz=_imgsz(imgsz), batch=batch, device=device,
                        conf=conf, project=project, name=name, tiles=tiles, tile_overlap=tile_overlap,
-                       merge_iou=merge_iou, merge_metric=merge_metric, class_agnostic=class_agnostic)
+                       merge_iou=merge_iou, merge_metric=merge_metric, class_agnostic=class_agnostic, merge=merge,
+                       fuse_iou=fuse_iou)
 
 
 def save_rtdetr_metrics_json(metrics, out_path: str | Path) -> Path:

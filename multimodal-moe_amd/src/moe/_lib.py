@@ -119,6 +119,7 @@ SIGNATURES = {
     "rtdetr_eval_match_bands": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_resize_pad_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_nms_merge": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "rtdetr_box_fuse": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -294,17 +295,21 @@ def launch_counts(reset=False) -> dict:
     """{kind name: launches} the library has issued since the last reset
     (host-side counts, graph capture included: moe_launch_counts).
     "eval_match_bands" -- the launches of eval_match_bands(), which the library
-    counts with eval_match's -- is reported apart and taken out of "eval_match"."""
-    global _eval_match_bands_launches
+    counts with eval_match's -- is reported apart and taken out of "eval_match";
+    likewise "box_fuse" (box_fuse()), which the library counts under "merge"."""
+    global _eval_match_bands_launches, _box_fuse_launches
     n = max(PROF_KINDS) + 1
     buf = (ctypes.c_longlong * n)()
     _check(lib().moe_launch_counts(ctypes.cast(buf, ctypes.c_void_p), n), "moe_launch_counts")
     out = {PROF_KINDS[i]: int(buf[i]) for i in range(n)}
     out["eval_match_bands"] = min(_eval_match_bands_launches, out["eval_match"])
     out["eval_match"] -= out["eval_match_bands"]
+    out["box_fuse"] = min(_box_fuse_launches, out["merge"])
+    out["merge"] -= out["box_fuse"]
     if reset:
         lib().moe_launch_counts_reset()
         _eval_match_bands_launches = 0
+        _box_fuse_launches = 0
     return {k: v for k, v in out.items() if v}
 
 
@@ -1004,6 +1009,70 @@ def nms_merge(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=3
                                 NMS_METRICS[metric], int(bool(class_agnostic)), max_det, *(_ptr(t) for t in out),
                                 _stream())
     _check(rc, "rtdetr_nms_merge")
+    return out
+
+
+BOX_FUSE_MAX_N, BOX_FUSE_MAX_DET, BOX_FUSE_MAX_B, BOX_FUSE_MAX_P = 4096, 1024, 1024, 64  # rtdetr_box_fuse's limits
+# rtdetr_box_fuse shares the library's merge launch counter (and profiler kind); launch_counts() reports its
+# launches, counted here, under their own name
+_box_fuse_launches = 0
+
+
+def box_fuse(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=300, class_agnostic=False,
+             fuse_thr=0.55, windows=None, out=None):
+    """Box fusion of tiled prediction, one launch for the batch (rtdetr_box_fuse:
+    merge.fuse_reference per image, bit for bit).  The operands of ``nms_merge``
+    plus fuse_thr and windows fp32 [B, P, 4] (x0, y0, x1, y1: the frame, then
+    the tile windows; N = P k) or None.  -> (out_boxes fp32 [B, max_det, 4] the
+    fused boxes, out_scores, out_labels, out_src, count as nms_merge's, members
+    int32 [B, max_det]: the fused candidates of each row, leader included),
+    every element written (rows past count: zeros, -1 in out_src).  ``out``:
+    that tuple of tensors to write into instead of new ones."""
+    global _box_fuse_launches
+    _need(boxes, torch.float32, "boxes")
+    _need(scores, torch.float32, "scores")
+    _need(labels, torch.int32, "labels")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4:
+        raise MoEKernelError("box_fuse: boxes must be [B, N, 4]")
+    B, N, _ = (int(v) for v in boxes.shape)
+    if tuple(scores.shape) != (B, N) or tuple(labels.shape) != (B, N):
+        raise MoEKernelError("box_fuse: scores / labels must be [B, N]")
+    if n_valid is not None:
+        _need(n_valid, torch.int32, "n_valid")
+        if tuple(n_valid.shape) != (B,):
+            raise MoEKernelError("box_fuse: n_valid must be [B]")
+    P = 0
+    if windows is not None:
+        _need(windows, torch.float32, "windows")
+        if windows.dim() != 3 or int(windows.shape[0]) != B or windows.shape[-1] != 4 or int(windows.shape[1]) < 1:
+            raise MoEKernelError("box_fuse: windows must be [B, P, 4] with P >= 1")
+        P = int(windows.shape[1])
+    if metric not in NMS_METRICS:
+        raise MoEKernelError(f"box_fuse: metric must be one of {sorted(NMS_METRICS)}, got {metric!r}")
+    max_det = int(max_det)
+    dev = boxes.device
+    md = max(max_det, 0)
+    shapes = ((B, md, 4), (B, md), (B, md), (B, md), (B,), (B, md))
+    dtypes = (torch.float32, torch.float32, torch.int32, torch.int32, torch.int32, torch.int32)
+    names = ("out_boxes", "out_scores", "out_labels", "out_src", "count", "members")
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        if len(out) != 6:
+            raise MoEKernelError("box_fuse: out must be (boxes, scores, labels, src, count, members)")
+        for t, s, d, name in zip(out, shapes, dtypes, names):
+            _need(t, d, name)
+            if tuple(t.shape) != s:
+                raise MoEKernelError(f"box_fuse: {name} must be {s}, got {tuple(t.shape)}")
+    tensors = [boxes, scores, labels, *out] + [t for t in (n_valid, windows) if t is not None]
+    if any(t.device != dev for t in tensors):
+        raise MoEKernelError("box_fuse: all tensors must be on one device")
+    rc = lib().rtdetr_box_fuse(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), B, N, float(conf), float(thr),
+                               NMS_METRICS[metric], int(bool(class_agnostic)), max_det, float(fuse_thr),
+                               _ptr(windows), P, *(_ptr(t) for t in out), _stream())
+    _check(rc, "rtdetr_box_fuse")
+    if B > 0:
+        _box_fuse_launches += 1
     return out
 
 

@@ -838,6 +838,8 @@ class Prediction:
     labels: torch.Tensor
     # tiled prediction: the pass each row came from, int64 [n]: 0 the full frame, 1 + t tile t; None without tiles
     source: torch.Tensor | None = None
+    # merge="fuse": the candidates averaged into each row's box, its own included, int64 [n] (>= 1); None otherwise
+    members: torch.Tensor | None = None
 
 
 @dataclass
@@ -885,16 +887,17 @@ def predict_resize_on_gpu(dev: torch.device) -> bool:
 
 
 def predict_merge_on_gpu(dev: torch.device) -> bool:
-    """Whether tiled prediction merges its passes on the GPU (rtdetr_nms_merge):
-    on a GPU device unless MOE_PREDICT_MERGE=0 asks for merge.merge_reference
-    on the copied-back candidates."""
+    """Whether tiled prediction merges its passes on the GPU (rtdetr_nms_merge;
+    merge="fuse": rtdetr_box_fuse): on a GPU device unless MOE_PREDICT_MERGE=0
+    asks for merge.merge_reference (fuse_reference) on the copied-back
+    candidates."""
     return dev.type == "cuda" and os.environ.get("MOE_PREDICT_MERGE", "1") != "0"
 
 
 @torch.no_grad()
 def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
             workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
-            merge_iou=0.5, merge_metric="ios", class_agnostic=False) -> PredictResults:
+            merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -929,12 +932,33 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     are cropped and resized on the host.  ``Prediction.source`` then holds the
     pass of every row and ``.speed`` gains "passes" (1 + rows cols; the three
     timings include every pass, the merge under "postprocess").  Without
-    ``tiles`` nothing of this runs."""
-    from .merge import MERGE_MAX_DET, MERGE_MAX_N, METRICS, merge_reference, parse_tiles, tile_windows
+    ``tiles`` nothing of this runs.
+    ``merge``: "nms" (the default) keeps the best copy of every object as it
+    stands.  "fuse" (tiles only) keeps the same rows -- same scores, labels,
+    order and ``source`` -- and replaces each box by the score-weighted average
+    of the copies of its object: the candidates it suppressed whose box agrees
+    with it where both passes could see (IoU > ``fuse_iou`` after clamping both
+    into the two windows' intersection; 0.55 is the usual weighted-box-fusion
+    default, not tuned here), a side cut by a tile's edge left out of the
+    average (merge.fuse_reference).  The windows -- the frame, then the tiles'
+    clipping bounds -- go up with the batch's other small tensors; on a GPU the
+    fusion is ONE HIP launch in place of the merge's (rtdetr_box_fuse;
+    MOE_PREDICT_MERGE=0 or the CPU: fuse_reference) and ``Prediction.members``
+    (the candidates averaged into each row) joins the one packed copy back."""
+    from .merge import (FUSE_MAX_DET, FUSE_MAX_N, FUSE_MAX_P, MERGE_MAX_DET, MERGE_MAX_N, METRICS, fuse_reference,
+                        merge_reference, parse_tiles, tile_windows)
     from .preprocess import (FrameSource, HostCollate, PackCollate, TileHostCollate, TilePackCollate, iter_batches,
                              mapped_sizes, padded_hw)
 
     tiles = parse_tiles(tiles)
+    if merge not in ("nms", "fuse"):
+        raise ValueError(f"merge must be 'nms' or 'fuse', got {merge!r}")
+    fuse = merge == "fuse"
+    if fuse:
+        if tiles is None:
+            raise ValueError("merge='fuse' fuses the passes of tiled prediction: give tiles=(rows, cols)")
+        if not 0.0 <= float(fuse_iou) <= 1.0:
+            raise ValueError(f"fuse_iou must be in [0, 1], got {fuse_iou}")
     if tiles is not None:
         tile_windows(2 * tiles[1], 2 * tiles[0], tiles, tile_overlap)  # the overlap's ValueError, before any work
         if merge_metric not in METRICS:
@@ -966,6 +990,10 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         if n_cand > MERGE_MAX_N or max_det > MERGE_MAX_DET:
             raise ValueError(f"tiles {tiles[0]}x{tiles[1]} with max_det {max_det} is {n_cand} candidates per frame: "
                              f"the merge takes at most {MERGE_MAX_N} candidates and max_det {MERGE_MAX_DET}")
+        if fuse and (n_cand > FUSE_MAX_N or max_det > FUSE_MAX_DET or 1 + n_tiles > FUSE_MAX_P):
+            raise ValueError(f"tiles {tiles[0]}x{tiles[1]} with max_det {max_det} is {1 + n_tiles} passes and "
+                             f"{n_cand} candidates per frame: the fusion takes at most {FUSE_MAX_P} passes, "
+                             f"{FUSE_MAX_N} candidates and max_det {FUSE_MAX_DET}")
     gpu_merge = predict_merge_on_gpu(dev)
     ds = FrameSource(source, contexts=contexts)
     if tiles is None:
@@ -1071,7 +1099,33 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
             cb = torch.cat([boxes[:n], torch.cat(tb).reshape(n, n_tiles * k, 4)], 1)
             cs = torch.cat([scores[:n], torch.cat(ts).reshape(n, n_tiles * k)], 1)
             cl = torch.cat([labels[:n], torch.cat(tl).reshape(n, n_tiles * k)], 1)
-            if gpu_merge:
+            members = None
+            if fuse:
+                # the passes' windows per frame: the frame, then the bounds each tile's boxes were clipped with
+                win = torch.tensor([[[0.0, 0.0, float(fw), float(fh)]]
+                                    + [[float(x0), float(y0), float(x0 + tw), float(y0 + th)]
+                                       for x0, y0, tw, th in wins[i * n_tiles:(i + 1) * n_tiles]]
+                                    for i, (fw, fh) in enumerate(sizes[:n])], dtype=torch.float32)
+            if fuse and gpu_merge:
+                ob, osc, ol, osrc, _, om = _lib.box_fuse(cb, cs, cl.to(torch.int32), None, conf, merge_iou,
+                                                         merge_metric, max_det, class_agnostic, fuse_iou,
+                                                         win.to(cb.device))
+                packed = torch.cat([ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype),
+                                    om[..., None].to(ob.dtype)], -1).cpu()  # one copy back, members with it
+                rows = [packed[i][packed[i][:, 6] >= 0] for i in range(n)]
+                members = [row[:, 7].to(torch.int64) for row in rows]
+            elif fuse:
+                packed = torch.cat([cb, cs[..., None], cl[..., None].to(cb.dtype)], -1).cpu()
+                rows, members = [], []
+                for i in range(n):
+                    keep, fb, mem = fuse_reference(packed[i][:, :4], packed[i][:, 4], packed[i][:, 5], None, conf,
+                                                   merge_iou, merge_metric, max_det, class_agnostic, fuse_iou,
+                                                   win[i])
+                    keep = torch.from_numpy(keep)
+                    rows.append(torch.cat([torch.from_numpy(fb).reshape(-1, 4), packed[i][keep][:, 4:],
+                                           keep[:, None].to(packed.dtype)], -1))
+                    members.append(torch.from_numpy(mem).to(torch.int64))
+            elif gpu_merge:
                 ob, osc, ol, osrc, _ = _lib.nms_merge(cb, cs, cl.to(torch.int32), None, conf, merge_iou, merge_metric,
                                                       max_det, class_agnostic)
                 packed = torch.cat([ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype)],
@@ -1087,7 +1141,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
             for i, row in enumerate(rows):
                 preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
                                         boxes=row[:, :4].contiguous(), scores=row[:, 4].contiguous(),
-                                        labels=row[:, 5].to(torch.int64), source=row[:, 6].to(torch.int64) // k))
+                                        labels=row[:, 5].to(torch.int64), source=row[:, 6].to(torch.int64) // k,
+                                        members=None if members is None else members[i]))
             t_pre += t_tile[0]
             t_inf += t_tile[1]
             t_post -= t_tile[0] + t_tile[1]  # what is left of t3 - t2 is postprocessing: every pass's and the merge

@@ -6,6 +6,9 @@
   rtdetr_nms_merge (_lib.nms_merge) takes the same decisions bit for bit and is
   tested against this function; it is also the merge of the CPU device and of
   MOE_PREDICT_MERGE=0.
+* ``fuse_reference``: the same walk, after which every kept box is averaged
+  with the copies it suppressed that agree with it (predict(merge="fuse"));
+  the HIP kernel rtdetr_box_fuse (_lib.box_fuse) is tested against it.
 
 The rule.  Candidate i takes part if i < n_valid and scores[i] >= conf (a NaN
 score never does).  The candidates are visited in argsort(-scores, stable)
@@ -27,6 +30,7 @@ import numpy as np
 
 METRICS = {"iou": 0, "ios": 1}  # the kernel's metric argument
 MERGE_MAX_N, MERGE_MAX_DET, MERGE_MAX_B = 4096, 1024, 1024  # rtdetr_nms_merge's limits
+FUSE_MAX_N, FUSE_MAX_DET, FUSE_MAX_B, FUSE_MAX_P = 4096, 1024, 1024, 64  # rtdetr_box_fuse's limits
 
 
 def _axis_windows(L: int, n: int, o: float):
@@ -107,3 +111,142 @@ def merge_reference(boxes, scores, labels, n_valid, conf, thr, metric="ios", max
             kept[nk] = i
             nk += 1
     return kept[:nk].copy()
+
+
+def fuse_reference(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=300, class_agnostic=False,
+                   fuse_thr=0.55, windows=None, return_clusters=False):
+    """One image: merge_reference's walk, then every kept box (a leader) fused
+    with the copies of its object -> (kept int64 [n_kept], identical to
+    merge_reference's; fused boxes fp32 [n_kept, 4]; members int32 [n_kept]).
+    ``windows`` fp32 [P, 4] (x0, y0, x1, y1) or None: row 0 the frame, rows
+    1..P-1 the tile windows; N must be P k, candidate i belongs to pass i // k.
+
+    1. A candidate that was visited and suppressed joins the first leader, in
+       kept order, that suppresses it.  Candidates past the max_det-th kept one
+       are not visited and join nothing.
+    2. It fuses if the two boxes agree on what both passes could see: both
+       clamped, coordinate by coordinate, into V, the intersection of the two
+       passes' windows (no clamp without ``windows``), then inter > fuse_thr *
+       ((area_i + area_j) - inter), always the "iou" form.  The truncated and
+       the full copy of one person pass; a child's box inside an adult's, which
+       "ios" suppresses, does not: it stays suppressed and is not averaged in.
+       The leader always fuses.
+    3. Side s of candidate i of pass p > 0 is cut if it lies on an edge of W_p
+       that is not an edge of the frame W_0: x1 if x1_i <= W_p.x0 and W_p.x0 >
+       W_0.x0, x2 if x2_i >= W_p.x1 and W_p.x1 < W_0.x1, y likewise.
+    4. Per leader and side, over the fusing candidates in visit order (leader
+       first): one contributes if that side is not cut and its score is finite
+       and > 0; num = num + (score * coord), den = den + score in fp32; the
+       fused coordinate is num / den if den > 0, else the leader's own; with
+       ``windows`` it is clamped into W_0; an axis that comes out unordered
+       keeps both of the leader's coordinates.
+    Score and label stay the leader's.  fp32, every operation rounded on its
+    own, no FMA; the only division is the last one.
+    ``return_clusters``: also return rank int64 [N] (the kept rank whose average
+    candidate i went into, a leader its own; -1 for every other candidate) and
+    the number of visited, suppressed candidates."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {sorted(METRICS)}, got {metric!r}")
+    f32 = np.float32
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=f32)).reshape(-1, 4)
+    s = np.asarray(scores, dtype=f32).reshape(-1)
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    N = s.shape[0]
+    W, k = None, 0
+    if windows is not None:
+        W = np.ascontiguousarray(np.asarray(windows, dtype=f32)).reshape(-1, 4)
+        P = W.shape[0]
+        if P < 1 or P > FUSE_MAX_P or N % P != 0:
+            raise ValueError(f"windows must be [P, 4] with 1 <= P <= {FUSE_MAX_P} and N = P k, got P {P}, N {N}")
+        k = max(N // P, 1)
+    n = N if n_valid is None else min(max(int(n_valid), 0), N)
+    conf32, thr32, fthr32, zero = f32(conf), f32(thr), f32(fuse_thr), f32(0)
+    with np.errstate(invalid="ignore"):
+        part = (np.arange(N) < n) & (s >= conf32)
+    order = np.argsort(-s, kind="stable")
+    order = order[part[order]]
+    x1, y1, x2, y2 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    area = np.maximum(x2 - x1, zero) * np.maximum(y2 - y1, zero)
+    max_det = int(max_det)
+    kept = np.empty(min(max_det, len(order)), dtype=np.int64)
+    nk = 0
+    joined = []  # (candidate, kept rank of its leader), in visit order
+    for i in order:
+        if nk >= max_det:
+            break
+        kk = kept[:nk]
+        iw = np.maximum(np.minimum(x2[i], x2[kk]) - np.maximum(x1[i], x1[kk]), zero)
+        ih = np.maximum(np.minimum(y2[i], y2[kk]) - np.maximum(y1[i], y1[kk]), zero)
+        inter = iw * ih
+        den = (area[i] + area[kk]) - inter if metric == "iou" else np.minimum(area[i], area[kk])
+        hit = inter > thr32 * den
+        if not class_agnostic:
+            hit &= lab[kk] == lab[i]
+        if hit.any():
+            joined.append((int(i), int(np.argmax(hit))))
+        else:
+            kept[nk] = i
+            nk += 1
+    kept = kept[:nk].copy()
+
+    def fuses(i, j):
+        bi, bj = b[i], b[j]
+        if W is not None:
+            wi, wj = W[i // k], W[j // k]
+            lo = np.maximum(wi[[0, 1, 0, 1]], wj[[0, 1, 0, 1]])
+            hi = np.minimum(wi[[2, 3, 2, 3]], wj[[2, 3, 2, 3]])
+            bi = np.minimum(np.maximum(bi, lo), hi)
+            bj = np.minimum(np.maximum(bj, lo), hi)
+        ai = np.maximum(bi[2] - bi[0], zero) * np.maximum(bi[3] - bi[1], zero)
+        aj = np.maximum(bj[2] - bj[0], zero) * np.maximum(bj[3] - bj[1], zero)
+        iw = np.maximum(np.minimum(bi[2], bj[2]) - np.maximum(bi[0], bj[0]), zero)
+        ih = np.maximum(np.minimum(bi[3], bj[3]) - np.maximum(bi[1], bj[1]), zero)
+        inter = iw * ih
+        return bool(inter > fthr32 * ((ai + aj) - inter))
+
+    def uncut(i):
+        """Which of the four sides of candidate i may be averaged."""
+        if W is None or i // k == 0:
+            return (True, True, True, True)
+        w, w0 = W[i // k], W[0]
+        return (not (b[i, 0] <= w[0] and w[0] > w0[0]), not (b[i, 1] <= w[1] and w[1] > w0[1]),
+                not (b[i, 2] >= w[2] and w[2] < w0[2]), not (b[i, 3] >= w[3] and w[3] < w0[3]))
+
+    num = np.zeros((nk, 4), dtype=f32)
+    den = np.zeros((nk, 4), dtype=f32)
+    members = np.ones(nk, dtype=np.int32)
+
+    def add(i, q):
+        if np.isfinite(s[i]) and s[i] > zero:
+            for side, ok in enumerate(uncut(i)):
+                if ok:
+                    num[q, side] = num[q, side] + (s[i] * b[i, side])
+                    den[q, side] = den[q, side] + s[i]
+
+    # visit order with the leader first: a leader precedes every candidate it suppresses
+    for q in range(nk):
+        add(int(kept[q]), q)
+    rank = np.full(N, -1, dtype=np.int64)
+    rank[kept] = np.arange(nk)
+    for i, q in joined:
+        if fuses(i, int(kept[q])):
+            members[q] += 1
+            rank[i] = q
+            add(i, q)
+    fused = b[kept].copy() if nk else np.zeros((0, 4), dtype=f32)
+    for q in range(nk):
+        lead = b[kept[q]]
+        out = lead.copy()
+        for side in range(4):
+            if den[q, side] > zero:
+                out[side] = num[q, side] / den[q, side]
+        if W is not None:
+            out = np.minimum(np.maximum(out, W[0][[0, 1, 0, 1]]), W[0][[2, 3, 2, 3]])
+        if out[0] > out[2]:
+            out[0], out[2] = lead[0], lead[2]
+        if out[1] > out[3]:
+            out[1], out[3] = lead[1], lead[3]
+        fused[q] = out
+    if return_clusters:
+        return kept, fused, members, rank, len(joined)
+    return kept, fused, members

@@ -143,6 +143,39 @@ int main() {
     std::printf("FAIL nms_merge B=0 must succeed\n");
     ++g_fail;
   }
+  const float nanf_ = __builtin_nanf("");
+  expect_error("box_fuse N=4097", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 4097, 0.25f, 0.5f, 1, 0, 300, 0.55f,
+                                                  nullptr, 0, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse max_det=1025", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 1025, 0.55f,
+                                                        nullptr, 0, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse metric=2", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 2, 0, 300, 0.55f,
+                                                    nullptr, 0, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse thr=NaN", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, nanf_, 1, 0, 300, 0.55f,
+                                                   nullptr, 0, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse fuse_thr=NaN", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, nanf_,
+                                                        nullptr, 0, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse P=-1", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, 0.55f, f32, -1,
+                                                f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse P=65", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 65, 0.25f, 0.5f, 1, 0, 300, 0.55f, f32, 65,
+                                                f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse N%P", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, 0.55f, f32, 5,
+                                               f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse windows=NULL P=4", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300,
+                                                            0.55f, nullptr, 4, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse windows misaligned", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300,
+                                                              0.55f, f32 + 1, 4, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse boxes=NULL", rtdetr_box_fuse(nullptr, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, 0.55f,
+                                                      nullptr, 0, f32, f32, i32, i32, i32, i32, s));
+  expect_error("box_fuse members=NULL", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, 0.55f,
+                                                        nullptr, 0, f32, f32, i32, i32, i32, nullptr, s));
+  expect_error("box_fuse count=NULL", rtdetr_box_fuse(f32, f32, i32, nullptr, 1, 64, 0.25f, 0.5f, 1, 0, 300, 0.55f,
+                                                      nullptr, 0, f32, f32, i32, i32, nullptr, i32, s));
+  ++g_n;
+  if (rtdetr_box_fuse(nullptr, nullptr, nullptr, nullptr, 0, 64, 0.25f, 0.5f, 1, 0, 300, 0.55f, nullptr, 0, nullptr,
+                      nullptr, nullptr, nullptr, nullptr, nullptr, s) != 0) {  // B == 0: success, no launch
+    std::printf("FAIL box_fuse B=0 must succeed\n");
+    ++g_fail;
+  }
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }

@@ -6,7 +6,8 @@ then runs engine.predict on them with MOE_PREDICT_RESIZE=1 and =0 alternately
 ``speed`` (ms per image) and a last line with the medians and spreads.
 With --tiles RxC it runs, on the same files and alternately, prediction without
 tiles, with tiles merged on the GPU (MOE_PREDICT_MERGE=1) and with tiles merged
-on the host (MOE_PREDICT_MERGE=0), all with the GPU resize.
+on the host (MOE_PREDICT_MERGE=0), all with the GPU resize; --merge fuse makes
+the tiled legs fuse the boxes (rtdetr_box_fuse / merge.fuse_reference).
 
   python tools/predict_bench.py [--model rtdetr-r50-moe8-top2] [--n 64] [--batch 16] [--rounds 3] [--workers 4]
   python tools/predict_bench.py --tiles 2x2 [--conf 0.25]
@@ -51,14 +52,15 @@ def tiles_leg(a, d: Path, engine):
             torch.manual_seed(0)
             t0 = time.perf_counter()
             res = engine.predict(a.model, d, batch=a.batch, device=a.device, conf=a.conf, workers=a.workers,
-                                 tiles=tiles)
+                                 tiles=tiles, merge=a.merge if tiles else "nms")
             line = {"round": r, "leg": name, "images": len(res.predictions),
                     "detections": sum(len(p.scores) for p in res.predictions),
                     "wall_s": round(time.perf_counter() - t0, 2), **{k: round(v, 3) for k, v in res.speed.items()}}
             print(json.dumps(line), flush=True)
             runs[name].append(res.speed)
     os.environ.pop("MOE_PREDICT_MERGE", None)
-    out = {"model": a.model, "batch": a.batch, "workers": a.workers, "tiles": a.tiles, "conf": a.conf}
+    out = {"model": a.model, "batch": a.batch, "workers": a.workers, "tiles": a.tiles, "conf": a.conf,
+           "merge": a.merge}
     for name, _, _ in legs:
         for k in ("preprocess", "inference", "postprocess"):
             v = [s[k] for s in runs[name]]
@@ -76,6 +78,8 @@ def main(argv=None):
     ap.add_argument("--device", default="0")
     ap.add_argument("--tiles", default=None, help="ROWSxCOLS: time tiled prediction against the untiled run")
     ap.add_argument("--conf", type=float, default=0.25)
+    ap.add_argument("--merge", default="nms", choices=("nms", "fuse"),
+                    help="with --tiles: the merge of the tiled legs (fuse: rtdetr_box_fuse / fuse_reference)")
     a = ap.parse_args(argv)
     from src.rtdetr_moe import engine
 
