@@ -937,7 +937,15 @@ int rtdetr_set_criterion_loss_bwd(const float* g_comps, int S, int B, int Q, int
  *     per-row max + log2(sum) of the base-2 softmax (for the backward).
  *   rtdetr_attn_bwd: dq, dk, dv from dout, the forward's o and lse; delta
  *     [B, H, L] fp32 scratch (rowsum(dout * o)).  Two launches (dQ, then dK and
- *     dV), no atomics: bitwise repeatable. */
+ *     dV), no atomics: bitwise repeatable.
+ * Any H >= 1, any scale (negative and 0 included); every operand may have a
+ * buffer and a row stride of its own.  Only columns < 32 H of rows < B L of
+ * o / dq / dk / dv and elements < B H L of lse / delta are written; the
+ * backward writes none of its inputs.  B == 0 or L == 0 is a no-op returning 0
+ * (after the argument checks: pointers must still be non-NULL and aligned).
+ * Refused (non-zero, moe_last_error(), nothing launched): head_dim != 32,
+ * B < 0, L < 0, H <= 0, a stride below 32 H or not a multiple of 8, a NULL or
+ * misaligned pointer, L H > 2^30. */
 int rtdetr_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
                     void* o, long long ldo, float* lse, int B, int H, int L, int head_dim, float scale,
                     hipStream_t stream);
@@ -949,7 +957,8 @@ int rtdetr_attn_bwd(const void* q, long long ldq, const void* k, long long ldk, 
  * seg is a device vector of L int32 ids shared by all images and heads, and key
  * k is visible to query q iff seg[k] < 0 (a shared token) or seg[k] == seg[q].
  * Every query sees itself, so lse stays finite.  No L x L mask is read: the rule
- * is evaluated in registers.  seg must be non-NULL and 4-byte aligned. */
+ * is evaluated in registers.  seg must be non-NULL and 4-byte aligned.  All ids
+ * below 0 are one and the same shared id: -2, -3 or INT32_MIN behave as -1. */
 int rtdetr_attn_fwd_seg(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
                         void* o, long long ldo, float* lse, int B, int H, int L, int head_dim, float scale,
                         hipStream_t stream, const int32_t* seg);
