@@ -903,6 +903,58 @@ int rtdetr_box_fuse(const float* boxes, const float* scores, const int32_t* labe
                     int32_t* out_labels, int32_t* out_src, int32_t* count, int32_t* out_members,
                     hipStream_t stream);
 
+/* Tracking by detection (engine.track, engine.predict(..., track=...)): links a
+ * sequence's detections from frame to frame (track.track_reference on the host,
+ * bit for bit).  One launch per batch, one workgroup per state slot; a slot's
+ * frames are walked in ascending frame index inside its workgroup, its tracks
+ * held in LDS from the first frame to the last: read from the state buffers
+ * once, written back once.  State that lives on the device between launches.
+ * Inputs: boxes fp32 [F][K][4] xyxy (16-byte aligned), scores fp32 [F][K],
+ * labels int32 [F][K], the rows of a frame best first; n_valid int32 [F] or NULL
+ * (= K; clamped into [0, K]); frame_slot int32 [F], the state slot a frame
+ * belongs to; frame_reset int32 [F], non-zero clears the slot before that frame
+ * (a new sequence taking it over: no tracks, next_id 1, dropped 0).  A slot
+ * without frames keeps its state untouched; a frame whose slot is outside
+ * [0, S) gets empty outputs and touches no state, so any table is memory-safe.
+ * State, owned by the caller (track.TrackState), T track slots per state slot:
+ *   trk_box   fp32  [S][T][8]  x1 y1 x2 y2, then one velocity per side (16-byte aligned)
+ *   trk_score fp32  [S][T]
+ *   trk_meta  int32 [S][T][4]  label, id, age, hits; hits 0: the slot is free, all of it zero (16-byte aligned)
+ *   seq_meta  int32 [S][2]     next_id (a new sequence starts at 1), dropped
+ * The rule per frame, fp32, every operation rounded on its own, no FMA:
+ *   1. every live slot: box = box + vel.
+ *   2. row d takes part if d < n_valid, its score is finite and >= track_low;
+ *      it is high if score >= track_high, else low.
+ *   3. iou = inter / ((area_t + area_d) - inter) if that denominator is > 0,
+ *      else 0 (area, inter as rtdetr_nms_merge's; correctly rounded division);
+ *      a pair is admissible if the labels are equal (or class_agnostic) and
+ *      iou > thr.
+ *   4. greedy association: repeatedly the admissible pair of an unmatched slot
+ *      and row with the largest iou; equal iou: the lower row, then the lower
+ *      slot.  Stage 1: live slots x high rows, thr = match_iou.  Stage 2: the
+ *      slots still unmatched with age == 0 and hits >= min_hits x low rows,
+ *      thr = second_iou.
+ *   5. matched: r = det - box; box = box + alpha * r; vel = vel + beta * r;
+ *      score the row's; age = 0; hits = min(hits + 1, 2^30).  Unmatched: hits <
+ *      min_hits frees the slot, otherwise age += 1 and age > max_age frees it.
+ *   6. births: the unmatched high rows with score >= new_thr, in row order,
+ *      take the free slots in slot order (vel 0, hits 1, age 0, id next_id++);
+ *      each one left without a slot adds 1 to dropped.
+ * Outputs, every element written: out_id int32 [F][K], the id of the slot row
+ * d updated or founded if that slot has hits >= min_hits, else -1; out_boxes
+ * fp32 [F][K][4] (16-byte aligned) that slot's filtered box, else zeros; count
+ * int32 [F] the reported rows.  No global atomics, no workspace.
+ * Limits: K <= 1024, T in [1, 256], F <= 1024, S <= 1024 (41.2 KiB of LDS at
+ * the largest); max_age in [0, 2^30], min_hits in [1, 2^30]; thresholds and
+ * gains not NaN.  A bad argument returns non-zero before any launch.  F == 0
+ * returns 0 without a launch. */
+int rtdetr_track_update(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                        const int32_t* frame_slot, const int32_t* frame_reset, int F, int K, int S, int T,
+                        float track_high, float track_low, float new_thr, float match_iou, float second_iou,
+                        int max_age, int min_hits, float alpha, float beta, int class_agnostic, float* trk_box,
+                        float* trk_score, int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes,
+                        int32_t* count, hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -1249,7 +1301,7 @@ int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t*
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
  * context-bias gradients, 15 training batch augmentation, 16 validation
  * matching, 17 routing statistics, 18 inference preprocessing (resize),
- * 19 tiled prediction's merge.
+ * 19 tiled prediction's merge, 20 tracking.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1272,7 +1324,8 @@ enum moe_prof_kind {
   MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match) */
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
-  MOE_PROF_MERGE = 19      /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
+  MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
+  MOE_PROF_TRACK = 20      /* tracking: a sequence's detections linked across frames (rtdetr_track_update) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

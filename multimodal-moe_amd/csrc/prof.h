@@ -37,7 +37,8 @@ enum ProfKind {
   PROF_EVAL = 16,          // validation: detections matched to ground truth (rtdetr_eval_match)
   PROF_ROUTE_STATS = 17,   // validation: per-context routing statistics (moe_route_stats)
   PROF_RESIZE = 18,        // inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8)
-  PROF_MERGE = 19          // tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse)
+  PROF_MERGE = 19,         // tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse)
+  PROF_TRACK = 20          // tracking: a sequence's detections linked across frames (rtdetr_track_update)
 };
 
 class ProfScope {

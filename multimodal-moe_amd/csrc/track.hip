@@ -1,0 +1,395 @@
+// The tracker of engine.track on the GPU (track.py: track_reference, which
+// engine.predict(track=...) runs on the host with MOE_PREDICT_TRACK=0): links
+// a sequence's detections from frame to frame by greedy IoU association in two
+// score bands (BYTE), with a fixed-gain filter on each track's box.
+//
+// One workgroup per state slot (a sequence), one thread per track slot (T
+// rounded up to whole waves).  The workgroup reads frame_slot[] front to back
+// and handles its own frames in frame order; the sequence's tracks are read
+// from HBM into LDS before its first frame and written back once after its
+// last.  A slot without frames touches nothing.  The frames of a slot outside
+// [0, S) get empty outputs from workgroup f % S.  Per frame:
+//   1. The rows go into LDS (box, score, label, and rstate: kRowOut / kRowLow /
+//      kRowHigh, later the slot that took the row); every live track predicts.
+//   2. Association, stage 1 (live tracks x high rows, match_iou), then stage 2
+//      (tracks still unmatched with age 0 and hits >= min_hits x low rows,
+//      second_iou).  Every track scans the stage's free rows (an LDS broadcast
+//      read per row) and keeps its best admissible one as a 64-bit key: iou
+//      bits << 32 | ~row << 16 | ~slot.  Each round takes the workgroup-wide
+//      maximum key (wave shuffles, then one LDS word per wave, double buffered:
+//      one barrier a round) -- the admissible pair with the largest iou, the
+//      lower row, then the lower slot -- and only the tracks whose best row was
+//      just taken scan again.  A round matches one pair, so at most min(T, K)
+//      rounds; the iou of a pair never changes within a frame, so a rescan
+//      reproduces the bits.  The division runs only where inter != 0.
+//   3. Update / age / free, each thread its own track.
+//   4. Births: the free slots are ranked (ballots + per-wave counts) into a
+//      list; the unmatched high rows with score >= new_thr are ranked in row
+//      order the same way and the j-th takes the j-th free slot, id next_id +
+//      j; the rest are counted in dropped.
+//   5. Report: every row's id and filtered box, -1 and zeros elsewhere; count.
+//
+// Decisions and boxes are track_reference's bit for bit: fp32, each operation
+// rounded on its own, no FMA contraction (pragma below), one correctly rounded
+// division.
+//
+// LDS (dynamic, every offset a multiple of 16): rows 28 K bytes, tracks 52 T
+// bytes, the free list 4 T, 192 bytes of keys and counters: 41.2 KiB at the
+// limits K = 1024, T = 256.
+#include "moe_common.h"
+#include "prof.h"
+
+#pragma clang fp contract(off)
+
+namespace moe {
+
+constexpr int kTrkMaxK = 1024, kTrkMaxT = 256, kTrkMaxF = 1024, kTrkMaxS = 1024, kTrkMaxWaves = 4;
+constexpr int kTrkHitsCap = 1 << 30;
+constexpr int kRowOut = -3, kRowLow = -2, kRowHigh = -1;  // rstate: not taking part / free low / free high; >= 0: its slot
+
+__host__ __device__ constexpr size_t trk_up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+struct TrkLds {
+  size_t rbox, rscore, rlabel, rstate, tbox, tvel, tscore, tmeta, freelist, wkey, wcnt, ctl, total;
+  __host__ __device__ TrkLds(int K, int T) {
+    rbox = 0;                                           // float4 [K]
+    rscore = rbox + (size_t)K * 16;                     // float [K]
+    rlabel = rscore + trk_up16((size_t)K * 4);          // int32 [K]
+    rstate = rlabel + trk_up16((size_t)K * 4);          // int32 [K]
+    tbox = rstate + trk_up16((size_t)K * 4);            // float4 [T]
+    tvel = tbox + (size_t)T * 16;                       // float4 [T]
+    tscore = tvel + (size_t)T * 16;                     // float [T]
+    tmeta = tscore + trk_up16((size_t)T * 4);           // int4 [T]: label, id, age, hits
+    freelist = tmeta + (size_t)T * 16;                  // int32 [T]
+    wkey = freelist + trk_up16((size_t)T * 4);          // uint64 [2][kTrkMaxWaves]
+    wcnt = wkey + 2 * kTrkMaxWaves * 8;                 // int32 [kTrkMaxWaves]
+    ctl = wcnt + trk_up16(kTrkMaxWaves * 4);            // int32 [4]: next_id, dropped, reported
+    total = ctl + 16;
+  }
+};
+
+struct TrkParams {
+  float track_high, track_low, new_thr, match_iou, second_iou, alpha, beta;
+  int max_age, min_hits, class_agnostic;
+};
+
+__device__ __forceinline__ float trk_area(float4 b) { return fmaxf(b.z - b.x, 0.f) * fmaxf(b.w - b.y, 0.f); }
+
+__device__ __forceinline__ float trk_iou(float4 t, float ta, float4 d) {
+  const float iw = fmaxf(fminf(t.z, d.z) - fmaxf(t.x, d.x), 0.f);
+  const float ih = fmaxf(fminf(t.w, d.w) - fmaxf(t.y, d.y), 0.f);
+  const float inter = iw * ih;
+  if (inter == 0.f) return 0.f;  // 0 / den and the den <= 0 case alike
+  const float den = (ta + trk_area(d)) - inter;
+  return den > 0.f ? __fdiv_rn(inter, den) : 0.f;
+}
+
+__device__ __forceinline__ unsigned long long trk_wave_max(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(v >> 32), off, 64);
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// the rank of this thread among the workgroup's threads with ``flag``, in thread order, and their number.
+// Two barriers; wcnt is free again on return.
+__device__ __forceinline__ int trk_block_rank(bool flag, int32_t* wcnt, int lane, int wave, int nwaves, int* total) {
+  const unsigned long long bal = __ballot(flag);
+  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  if (lane == 0) wcnt[wave] = __popcll(bal);
+  __syncthreads();
+  int base = 0, sum = 0;
+  for (int w = 0; w < nwaves; ++w) {
+    const int c = wcnt[w];
+    if (w < wave) base += c;
+    sum += c;
+  }
+  __syncthreads();
+  *total = sum;
+  return base + __popcll(bal & below);
+}
+
+__global__ __launch_bounds__(256) void track_update_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
+    const int32_t* __restrict__ frame_reset, int F, int K, int S, int T, TrkParams p, float* __restrict__ trk_box,
+    float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
+    int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ count) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const TrkLds o(K, T);
+  float4* rbox = reinterpret_cast<float4*>(smem + o.rbox);
+  float* rscore = reinterpret_cast<float*>(smem + o.rscore);
+  int32_t* rlabel = reinterpret_cast<int32_t*>(smem + o.rlabel);
+  int32_t* rstate = reinterpret_cast<int32_t*>(smem + o.rstate);
+  float4* tbox = reinterpret_cast<float4*>(smem + o.tbox);
+  float4* tvel = reinterpret_cast<float4*>(smem + o.tvel);
+  float* tscore = reinterpret_cast<float*>(smem + o.tscore);
+  int4* tmeta = reinterpret_cast<int4*>(smem + o.tmeta);
+  int32_t* freelist = reinterpret_cast<int32_t*>(smem + o.freelist);
+  unsigned long long* wkey = reinterpret_cast<unsigned long long*>(smem + o.wkey);
+  int32_t* wcnt = reinterpret_cast<int32_t*>(smem + o.wcnt);
+  int32_t* ctl = reinterpret_cast<int32_t*>(smem + o.ctl);
+
+  const int s = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+  const int lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
+  const bool mine = tid < T;  // this thread owns track slot tid
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4* gbox = reinterpret_cast<float4*>(trk_box) + (size_t)s * T * 2;
+  int4* gmeta = reinterpret_cast<int4*>(trk_meta) + (size_t)s * T;
+  bool loaded = false;  // block-uniform: the sequence's tracks stand in LDS
+  int parity = 0;       // which half of wkey the next round writes
+
+  for (int f = 0; f < F; ++f) {
+    const int fs = frame_slot[f];  // block-uniform
+    float4* ob = reinterpret_cast<float4*>(out_boxes) + (size_t)f * K;
+    int32_t* oi = out_id + (size_t)f * K;
+    if (fs != s) {
+      if ((fs < 0 || fs >= S) && f % S == s) {  // nobody's frame: the empty outputs
+        for (int d = tid; d < K; d += nthr) {
+          oi[d] = -1;
+          ob[d] = zero4;
+        }
+        if (tid == 0) count[f] = 0;
+      }
+      continue;
+    }
+    const bool reset = frame_reset[f] != 0;
+    if (reset || !loaded) {
+      if (reset) {
+        if (mine) {
+          tbox[tid] = zero4;
+          tvel[tid] = zero4;
+          tscore[tid] = 0.f;
+          tmeta[tid] = make_int4(0, 0, 0, 0);
+        }
+        if (tid == 0) {
+          ctl[0] = 1;
+          ctl[1] = 0;
+        }
+      } else {
+        if (mine) {
+          tbox[tid] = gbox[2 * tid];
+          tvel[tid] = gbox[2 * tid + 1];
+          tscore[tid] = trk_score[(size_t)s * T + tid];
+          tmeta[tid] = gmeta[tid];
+        }
+        if (tid == 0) {
+          ctl[0] = seq_meta[2 * s];
+          ctl[1] = seq_meta[2 * s + 1];
+        }
+      }
+      loaded = true;
+    }
+    // 1. the rows, and the prediction
+    const int n = n_valid != nullptr ? min(max(n_valid[f], 0), K) : K;
+    const float4* bx = reinterpret_cast<const float4*>(boxes) + (size_t)f * K;
+    for (int d = tid; d < K; d += nthr) {
+      const float sc = scores[(size_t)f * K + d];
+      rbox[d] = bx[d];
+      rscore[d] = sc;
+      rlabel[d] = labels[(size_t)f * K + d];
+      const bool part = d < n && sc >= p.track_low && fabsf(sc) < INFINITY;  // false for NaN
+      rstate[d] = !part ? kRowOut : (sc >= p.track_high ? kRowHigh : kRowLow);
+    }
+    int4 m = make_int4(0, 0, 0, 0);  // label, id, age, hits
+    float4 tb = zero4;
+    if (mine) {
+      m = tmeta[tid];
+      tb = tbox[tid];
+      if (m.w > 0) {
+        const float4 v = tvel[tid];
+        tb = make_float4(tb.x + v.x, tb.y + v.y, tb.z + v.z, tb.w + v.w);
+      }
+    }
+    if (tid == 0) ctl[2] = 0;
+    __syncthreads();
+
+    // 2. association
+    const float ta = trk_area(tb);
+    int matched = -1;  // the row this track took
+    for (int stage = 0; stage < 2; ++stage) {
+      const int want = stage == 0 ? kRowHigh : kRowLow;
+      const float thr = stage == 0 ? p.match_iou : p.second_iou;
+      const bool eligible = mine && m.w > 0 && matched < 0 && (stage == 0 || (m.z == 0 && m.w >= p.min_hits));
+      unsigned long long key = 0ull;
+      bool scan = eligible;
+      int taken = -1;  // the row the last round matched: taken, whether or not its rstate write has landed
+      for (;;) {
+        if (scan) {
+          key = 0ull;
+          for (int d = 0; d < K; ++d) {
+            if (rstate[d] != want || d == taken) continue;  // wave-uniform
+            if (!p.class_agnostic && rlabel[d] != m.x) continue;
+            float iou = trk_iou(tb, ta, rbox[d]);
+            if (!(iou > thr)) continue;
+            if (iou == 0.f) iou = 0.f;  // -0.0 as +0.0
+            const unsigned long long k = ((unsigned long long)__float_as_uint(iou) << 32) |
+                                         ((uint32_t)(~d & 0xFFFF) << 16) | (uint32_t)(~tid & 0xFFFF);
+            key = k > key ? k : key;  // equal iou: the lower row has the larger key
+          }
+        }
+        const unsigned long long wmax = trk_wave_max(key);
+        unsigned long long* wk = wkey + parity * kTrkMaxWaves;
+        parity ^= 1;
+        if (lane == 0) wk[wave] = wmax;
+        __syncthreads();
+        unsigned long long best = 0ull;
+        for (int w = 0; w < nwaves; ++w) best = wk[w] > best ? wk[w] : best;
+        if (best == 0ull) break;  // block-uniform
+        const int bd = (int)(~(uint32_t)(best >> 16) & 0xFFFF), bt = (int)(~(uint32_t)best & 0xFFFF);
+        taken = bd;
+        scan = false;
+        if (tid == bt) {
+          matched = bd;
+          rstate[bd] = bt;
+          key = 0ull;
+        } else if (key != 0ull && (int)(~(uint32_t)(key >> 16) & 0xFFFF) == bd) {
+          scan = true;  // lost its best row
+        }
+      }
+      __syncthreads();  // the last round's rstate write, before the next stage reads
+    }
+
+    // 3. update, age, free
+    if (mine && m.w > 0) {
+      if (matched >= 0) {
+        const float4 d = rbox[matched];
+        const float4 r = make_float4(d.x - tb.x, d.y - tb.y, d.z - tb.z, d.w - tb.w);
+        const float4 v = tvel[tid];
+        tb = make_float4(tb.x + p.alpha * r.x, tb.y + p.alpha * r.y, tb.z + p.alpha * r.z, tb.w + p.alpha * r.w);
+        tvel[tid] = make_float4(v.x + p.beta * r.x, v.y + p.beta * r.y, v.z + p.beta * r.z, v.w + p.beta * r.w);
+        tbox[tid] = tb;
+        tscore[tid] = rscore[matched];
+        m.z = 0;
+        m.w = min(m.w + 1, kTrkHitsCap);
+      } else {
+        bool drop = m.w < p.min_hits;
+        if (!drop) {
+          m.z += 1;
+          drop = m.z > p.max_age;
+        }
+        if (drop) {
+          m = make_int4(0, 0, 0, 0);
+          tb = zero4;
+          tvel[tid] = zero4;
+          tscore[tid] = 0.f;
+        }
+        tbox[tid] = tb;  // the predicted box of a coasting track
+      }
+      tmeta[tid] = m;
+    }
+
+    // 4. births
+    int nfree = 0;
+    const bool isfree = mine && m.w == 0;
+    const int frank = trk_block_rank(isfree, wcnt, lane, wave, nwaves, &nfree);
+    if (isfree) freelist[frank] = tid;
+    __syncthreads();
+    const int next_id = ctl[0];
+    int births = 0;  // block-uniform: the candidates so far
+    for (int base = 0; base < K; base += nthr) {
+      const int d = base + tid;
+      const bool cand = d < K && rstate[d] == kRowHigh && rscore[d] >= p.new_thr;
+      int nc = 0;
+      const int j = births + trk_block_rank(cand, wcnt, lane, wave, nwaves, &nc);
+      if (cand && j < nfree) {
+        const int t = freelist[j];
+        tbox[t] = rbox[d];
+        tvel[t] = zero4;
+        tscore[t] = rscore[d];
+        tmeta[t] = make_int4(rlabel[d], next_id + j, 0, 1);
+        rstate[d] = t;
+      }
+      births += nc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      ctl[0] = next_id + min(births, nfree);
+      ctl[1] += max(births - nfree, 0);
+    }
+
+    // 5. report
+    for (int base = 0; base < K; base += nthr) {
+      const int d = base + tid;
+      bool rep = false;
+      if (d < K) {
+        const int t = rstate[d];
+        int4 tm = make_int4(0, 0, 0, 0);
+        if (t >= 0) tm = tmeta[t];
+        rep = t >= 0 && tm.w >= p.min_hits;
+        oi[d] = rep ? tm.y : -1;
+        ob[d] = rep ? tbox[t] : zero4;
+      }
+      const unsigned long long bal = __ballot(rep);
+      if (lane == 0 && bal != 0ull) atomicAdd(&ctl[2], __popcll(bal));
+    }
+    __syncthreads();
+    if (tid == 0) count[f] = ctl[2];
+    __syncthreads();  // before the next frame overwrites the rows and ctl[2]
+  }
+
+  if (loaded) {
+    if (mine) {
+      gbox[2 * tid] = tbox[tid];
+      gbox[2 * tid + 1] = tvel[tid];
+      trk_score[(size_t)s * T + tid] = tscore[tid];
+      gmeta[tid] = tmeta[tid];
+    }
+    if (tid == 0) {
+      seq_meta[2 * s] = ctl[0];
+      seq_meta[2 * s + 1] = ctl[1];
+    }
+  }
+}
+
+}  // namespace moe
+
+using namespace moe;
+
+extern "C" int rtdetr_track_update(const float* boxes, const float* scores, const int32_t* labels,
+                                   const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
+                                   int F, int K, int S, int T, float track_high, float track_low, float new_thr,
+                                   float match_iou, float second_iou, int max_age, int min_hits, float alpha,
+                                   float beta, int class_agnostic, float* trk_box, float* trk_score,
+                                   int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes,
+                                   int32_t* count, hipStream_t stream) {
+  const std::string what = "rtdetr_track_update";
+  if (F < 0 || K < 0 || S < 0 || F > kTrkMaxF || K > kTrkMaxK || S > kTrkMaxS || T < 1 || T > kTrkMaxT)
+    return fail(what + ": need 0 <= F <= 1024, 0 <= K <= 1024, 0 <= S <= 1024, 1 <= T <= 256");
+  if (track_high != track_high || track_low != track_low || new_thr != new_thr || match_iou != match_iou ||
+      second_iou != second_iou || alpha != alpha || beta != beta)
+    return fail(what + ": thresholds and gains must not be NaN");
+  if (max_age < 0 || max_age > kTrkHitsCap || min_hits < 1 || min_hits > kTrkHitsCap)
+    return fail(what + ": need 0 <= max_age <= 2^30 and 1 <= min_hits <= 2^30");
+  if (F == 0) return 0;
+  if (S < 1) return fail(what + ": need S >= 1 state slots with F > 0");
+  if (!frame_slot || !frame_reset) return fail(what + ": NULL frame table");
+  if (!trk_box || !trk_score || !trk_meta || !seq_meta) return fail(what + ": NULL state pointer");
+  if (!count || (K > 0 && (!out_id || !out_boxes))) return fail(what + ": NULL output pointer");
+  if (K > 0 && (!boxes || !scores || !labels)) return fail(what + ": NULL input pointer");
+  if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_boxes) |
+       reinterpret_cast<uintptr_t>(trk_box) | reinterpret_cast<uintptr_t>(trk_meta)) & 15)
+    return fail(what + ": boxes, out_boxes, trk_box and trk_meta must be 16-byte aligned");
+  const size_t shmem = TrkLds(K, T).total;
+  if (shmem > 64 * 1024) return fail(what + ": K / T too large for LDS");
+  const int threads = (T + 63) / 64 * 64;
+  TrkParams p;
+  p.track_high = track_high;
+  p.track_low = track_low;
+  p.new_thr = new_thr;
+  p.match_iou = match_iou;
+  p.second_iou = second_iou;
+  p.alpha = alpha;
+  p.beta = beta;
+  p.max_age = max_age;
+  p.min_hits = min_hits;
+  p.class_agnostic = class_agnostic != 0 ? 1 : 0;
+  ProfScope prof(stream, PROF_TRACK,
+                 (double)F * (K * 44.0 + (n_valid ? 4.0 : 0.0) + 12.0) + (double)S * (T * 104.0 + 16.0));
+  MOE_LAUNCH(prof, track_update_kernel, dim3(S), dim3(threads), shmem, stream, boxes, scores, labels, n_valid,
+             frame_slot, frame_reset, F, K, S, T, p, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes, count);
+  return check_launch("rtdetr_track_update");
+}

@@ -13,6 +13,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --resize      the inference resize kernel against the host resize it replaces
   python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
   python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
+  python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -695,6 +696,165 @@ def box_fuse_leg(reps, rounds):
     print(json.dumps(line), flush=True)
 
 
+def track_sequence(n_obj, F, K, seed=0, first=0):
+    """A synthetic pedestrian sequence as a detector reports it: n_obj
+    constant-velocity objects with 2 px of jitter per side, 10 % of them missed
+    and 15 % scored low per frame, 3 false positives, fillers below the low band
+    up to K rows, best first.  -> boxes fp32 [F, K, 4], scores fp32 [F, K],
+    labels int32 [F, K], n_valid int32 [F] (the rows with score >= 0.1), truth
+    int64 [F, K] (the object of a row, -1 for none).  Frames first..first+F-1."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    i = np.arange(n_obj)
+    w, h = rng.uniform(30, 50, n_obj), rng.uniform(80, 120, n_obj)
+    x0, y0 = 40.0 + (i % 10) * 110.0, 60.0 + (i // 10) * 150.0
+    vx, vy = rng.uniform(-0.8, 0.8, n_obj), rng.uniform(-0.3, 0.3, n_obj)
+    boxes, scores = np.zeros((F, K, 4), np.float32), np.zeros((F, K), np.float32)
+    n_valid, truth = np.zeros(F, np.int32), np.full((F, K), -1, np.int64)
+    for f in range(F):
+        t = first + f
+        rows = []
+        for o in range(n_obj):
+            if t > 0 and rng.random() < 0.1:
+                continue
+            sc = rng.uniform(0.15, 0.45) if t > 1 and rng.random() < 0.15 else rng.uniform(0.65, 0.95)
+            x, y = x0[o] + vx[o] * t, y0[o] + vy[o] * t
+            rows.append((sc, np.array([x, y, x + w[o], y + h[o]]) + rng.normal(0, 2.0, 4), o))
+        for _ in range(3):
+            x, y, ww = rng.uniform(0, 1188), rng.uniform(0, 574), rng.uniform(25, 55)
+            rows.append((rng.uniform(0.1, 0.9), np.array([x, y, x + ww, y + 2.4 * ww]), -1))
+        rows.sort(key=lambda r: -r[0])
+        rows = rows[:K]
+        n = len(rows)
+        for d, (sc, b, o) in enumerate(rows):
+            boxes[f, d], scores[f, d], truth[f, d] = b, sc, o
+        fx, fy = rng.uniform(0, 1188, K - n), rng.uniform(0, 574, K - n)
+        boxes[f, n:] = np.stack([fx, fy, fx + 40, fy + 100], 1)
+        scores[f, n:] = np.sort(rng.uniform(0.001, 0.05, K - n))[::-1]
+        n_valid[f] = n
+    return boxes, scores, np.zeros((F, K), np.int32), n_valid, truth
+
+
+def track_leg(reps, rounds):
+    """rtdetr_track_update at predict's shape (F 16 frames of one sequence, K 300
+    rows, 40 objects: about 40 live tracks, the defaults of track.TrackArgs)
+    against track.track_reference on the host, same process, same candidates
+    (outputs and state checked equal first, bit for bit).  The state before the
+    timed batch is the one 16 earlier frames of the sequence leave; every timed
+    launch starts from a copy of it.  kernel_us: the kernel's dispatch-stamped
+    execution time per launch; device_path_ms: launch + one packed copy back,
+    wall clock; host_track_ms: one copy back of the candidates + the reference
+    loop over the 16 frames, wall clock.  forward_replay_us: one EvalForward
+    graph replay at batch 16 (rtdetr-r50-moe8-top2, 704 x 1248).  Median, min
+    and max over the rounds, the sides interleaved in each round.  Also the
+    reference's ids per object and id switches over the 32 frames (no accuracy
+    claim: synthetic constant-velocity input)."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import engine
+    from src.rtdetr_moe.model import RTDETRMoE
+    from src.rtdetr_moe.track import TrackArgs, TrackState, copy_state, new_state, states_equal, track_reference
+
+    F, K, n_obj = 16, 300, 40
+    args = TrackArgs()
+    boxes, scores, labels, n_valid, truth = track_sequence(n_obj, 2 * F, K)
+    state = TrackState(1, args.max_tracks, "cuda")
+    dev = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    zeros = torch.zeros(F, dtype=torch.int32, device="cuda")
+    ref = new_state(args.max_tracks)
+    ids, switches, events, want = {}, 0, {}, []
+    for f in range(2 * F):
+        oid, obox, cnt = track_reference(ref, boxes[f], scores[f], labels[f], n_valid[f], args, events)
+        want.append((oid, obox, cnt))
+        for d in np.nonzero((truth[f] >= 0) & (oid >= 0))[0]:
+            seen = ids.setdefault(int(truth[f, d]), [])
+            if seen and seen[-1] != oid[d]:
+                switches += 1
+            if not seen or seen[-1] != oid[d]:
+                seen.append(int(oid[d]))
+        if f == F - 1:
+            warm = copy_state(ref)
+    L.track_update(state, dev(boxes[:F]), dev(scores[:F]), dev(labels[:F]), dev(n_valid[:F]), zeros, zeros, args)
+    if not states_equal(state.export(0), warm):
+        raise SystemExit("track_update's state differs from track_reference's (frames 0..15)")
+    snap = state.snapshot()
+    db, ds, dl, dn = dev(boxes[F:]), dev(scores[F:]), dev(labels[F:]), dev(n_valid[F:])
+    out = tuple(t.cpu().numpy() for t in L.track_update(state, db, ds, dl, dn, zeros, zeros, args))
+    for f in range(F):
+        oid, obox, cnt = want[F + f]
+        if (int(out[2][f]) != cnt or not np.array_equal(out[0][f], oid)
+                or not np.array_equal(out[1][f].view(np.int32), obox.view(np.int32))):
+            raise SystemExit(f"track_update differs from track_reference (frame {F + f})")
+    if not states_equal(state.export(0), ref):
+        raise SystemExit("track_update's state differs from track_reference's (frames 16..31)")
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    def wall(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return statistics.median(ts)
+
+    def kernel():
+        state.restore(snap)  # torch copies: not among the library's profiled launches
+        return L.track_update(state, db, ds, dl, dn, zeros, zeros, args)
+
+    def device_path():
+        oid, obx, _ = kernel()
+        torch.cat([db, ds[..., None], dl[..., None].float(), oid.view(torch.float32)[..., None], obx], -1).cpu()
+
+    def host_path():
+        packed = torch.cat([db, ds[..., None], dl[..., None].float()], -1).cpu().numpy()
+        st = copy_state(warm)
+        for f in range(F):
+            track_reference(st, packed[f, :, :4], packed[f, :, 4], packed[f, :, 5], n_valid[F + f], args)
+
+    res = {"kernel_us": [], "device_path_ms": [], "host_track_ms": [], "forward_replay_us": []}
+    for _ in range(rounds):
+        res["kernel_us"].append(timed(kernel, reps))
+        res["device_path_ms"].append(wall(device_path, max(3, reps // 5)))
+        res["host_track_ms"].append(wall(host_path, 3))
+        res["forward_replay_us"].append(replay_us())
+    live = int((warm["hits"] > 0).sum())
+    line = {"kernel": "rtdetr_track_update", "shape": f"F{F} K{K} T{args.max_tracks} S1 objects{n_obj}",
+            "live_tracks": live, "reported": int(out[2].sum()),
+            "reference_32_frames": {"objects_tracked": len(ids), "ids_per_object_max": max(len(v) for v in ids.values()),
+                                    "switches": switches, "stage2": events["stage2"], "refound": events["refound"],
+                                    "tentative_freed": events["tentative_freed"]}}
+    for k, v in res.items():
+        line[k] = round(statistics.median(v), 3)
+        line[k + "_min"] = round(min(v), 3)
+        line[k + "_max"] = round(max(v), 3)
+    line["host_over_kernel"] = round(1e3 * line["host_track_ms"] / line["kernel_us"], 1)
+    line["kernel_share_of_forward"] = round(line["kernel_us"] / line["forward_replay_us"], 4)
+    print(json.dumps(line), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -755,6 +915,9 @@ def main():
     ap.add_argument("--box-fuse", action="store_true",
                     help="time rtdetr_box_fuse (B 16, 5 passes of 300, max_det 300) against rtdetr_nms_merge on the "
                          "same inputs and one EvalForward replay, after checking it against merge.fuse_reference")
+    ap.add_argument("--track", action="store_true",
+                    help="time rtdetr_track_update (16 frames of one sequence, K 300, about 40 live tracks) against "
+                         "track_reference on the host and one forward replay, and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -794,6 +957,9 @@ def main():
         return
     if a.nms_merge:
         nms_merge_leg(a.reps, a.rounds)
+        return
+    if a.track:
+        track_leg(a.reps, a.rounds)
         return
     if a.box_fuse:
         box_fuse_leg(a.reps, a.rounds)

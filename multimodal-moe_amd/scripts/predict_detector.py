@@ -5,11 +5,14 @@ with --save-img, overlays -- under RUNS_DIR/rtdetr/<run-name>_predict.
 Same flag style as scripts/eval_detector.py.  --source is a directory, a glob,
 one image file or a dataset yaml; frames may have any size.  --tiles 2x2 adds
 sliced inference: every frame is also detected on a grid of crops and the passes
-are merged (engine.predict).
+are merged (engine.predict).  --track links the detections of consecutive frames
+(a sequence: the images of one directory) by track id and also writes tracks.json
+and mot/<sequence>.txt; scripts/track_detector.py is the same thing.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import sys
 from pathlib import Path
 
@@ -45,7 +48,14 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="nms: keep the best copy of every object; fuse (with --tiles): average it with its other copies")
     ap.add_argument("--fuse-iou", type=float, default=0.55,
                     help="--merge fuse: how well a copy must agree with the kept box to be averaged in")
-    return ap.parse_args(argv)
+    ap.add_argument("--track", action="store_true",
+                    help="link the detections across the frames of a sequence (one directory): tracks.json, mot/*.txt")
+    ap.add_argument("--tracker", type=str, default=None,
+                    help="--track: JSON of track.TrackArgs fields, e.g. '{\"max_age\": 15}' (default: ByteTrack's)")
+    a = ap.parse_args(argv)
+    if a.tracker is not None and not a.track:
+        ap.error("--tracker needs --track")
+    return a
 
 
 def main(argv=None) -> None:
@@ -56,9 +66,14 @@ def main(argv=None) -> None:
                          max_det=a.max_det, contexts=a.context, workers=a.workers, project=str(RUNS_DIR / "rtdetr"),
                          name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
                          tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
-                         class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou)
+                         class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou,
+                         track=(json.loads(a.tracker) if a.tracker else True) if a.track else None)
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
+    if a.track:
+        ids = {(p.sequence, int(t)) for p in res.predictions for t in p.track_ids}
+        print(f"{len(ids)} tracks in {len({p.sequence for p in res.predictions})} sequences")
+        print(f"Saved tracks -> {res.save_dir / 'tracks.json'}, {res.save_dir / 'mot'}")
     print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))
     print(f"Saved predictions -> {res.save_dir / 'predictions.json'}")
 

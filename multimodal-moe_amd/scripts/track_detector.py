@@ -1,0 +1,29 @@
+"""Track pedestrians through image sequences with a trained RT-DETR-MoE
+checkpoint (or a bare architecture spec): scripts/predict_detector.py with
+--track on and --conf at the tracker's low band (0.1) unless given.  A sequence
+is the images of one directory, in the source's order.  Writes predictions.json,
+tracks.json (the COCO rows plus track_id and sequence) and mot/<sequence>.txt
+(frame,id,x,y,w,h,score,-1,-1,-1) under RUNS_DIR/rtdetr/<run-name>_predict.
+"""
+from __future__ import annotations
+
+import sys
+from pathlib import Path
+
+PKG_ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(PKG_ROOT)) if str(PKG_ROOT) not in sys.path else None
+
+from scripts import predict_detector  # noqa: E402
+
+
+def main(argv=None) -> None:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if "--track" not in argv:
+        argv.append("--track")
+    if not any(a == "--conf" or a.startswith("--conf=") for a in argv):
+        argv += ["--conf", "0.1"]
+    predict_detector.main(argv)
+
+
+if __name__ == "__main__":
+    main()

@@ -35,6 +35,7 @@ __all__ = [
     "save_rtdetr_training_summary", "get_rtdetr_model_size_stats_from_weights",
     "infer_model_variant_from_weights", "save_metrics_table_csv", "save_run_metadata_artifacts",
     "predict_rtdetr_detector",
+    "predict_rtdetr_tracker",
 ]
 
 DEFAULT_MODEL = "rtdetr-r50-moe8-top2"
@@ -142,6 +143,32 @@ def predict_rtdetr_detector(
                        conf=conf, project=project, name=name, tiles=tiles, tile_overlap=tile_overlap,
                        merge_iou=merge_iou, merge_metric=merge_metric, class_agnostic=class_agnostic, merge=merge,
                        fuse_iou=fuse_iou)
+
+
+def predict_rtdetr_tracker(
+    weights_path: str,
+    source,
+    imgsz: Union[int, tuple[int, int]] = (704, 1248),
+    batch: int = 16,
+    device: str = "0",
+    conf: float = 0.1,
+    tracker=None,
+    sequence_of=None,
+    project: str | None = None,
+    name: str | None = None,
+    **predict_args,
+):
+    """``predict_rtdetr_detector`` with tracking on (engine.track): the frames
+    of a sequence -- by default the images of one directory, in the source's
+    order -- are linked by track id.  ``tracker``: a dict of track.TrackArgs'
+    fields (None: the defaults, ByteTrack's, not tuned here).  Every
+    ``.predictions[i]`` holds the reported rows only and gains ``.track_ids``,
+    ``.track_boxes``, ``.sequence`` and ``.frame``; ``.save_dir`` gains
+    tracks.json and mot/<sequence>.txt.  ``predict_args``: tiles, merge, ... as
+    predict_rtdetr_detector takes them."""
+    eng = _engine()
+    return eng.track(_check_model_name(weights_path), source, imgsz=_imgsz(imgsz), batch=batch, device=device,
+                     conf=conf, tracker=tracker, sequence_of=sequence_of, project=project, name=name, **predict_args)
 
 
 def save_rtdetr_metrics_json(metrics, out_path: str | Path) -> Path:

@@ -120,6 +120,8 @@ SIGNATURES = {
     "rtdetr_resize_pad_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_nms_merge": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rtdetr_box_fuse": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "rtdetr_track_update": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _F, _F, _I, _P, _P, _P,
+                                 _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -213,7 +215,7 @@ def lib() -> ctypes.CDLL:
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
               11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
-              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge"}
+              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge", 20: "track"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -1073,6 +1075,68 @@ def box_fuse(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=30
     _check(rc, "rtdetr_box_fuse")
     if B > 0:
         _box_fuse_launches += 1
+    return out
+
+
+TRACK_MAX_K, TRACK_MAX_T, TRACK_MAX_F, TRACK_MAX_S = 1024, 256, 1024, 1024  # rtdetr_track_update's limits
+
+
+def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, args, out=None):
+    """The tracker, one launch for the batch (rtdetr_track_update:
+    track.track_reference per frame, bit for bit).  ``state``: a
+    track.TrackState (S state slots of T tracks, updated in place); boxes fp32
+    [F, K, 4] xyxy, scores fp32 [F, K], labels int32 [F, K], n_valid int32 [F] or
+    None (= K), frame_slot / frame_reset int32 [F]; ``args``: a track.TrackArgs.
+    -> (out_id int32 [F, K], out_boxes fp32 [F, K, 4], count int32 [F]), every
+    element written.  ``out``: that tuple of tensors to write into instead of
+    new ones."""
+    _need(boxes, torch.float32, "boxes")
+    _need(scores, torch.float32, "scores")
+    _need(labels, torch.int32, "labels")
+    _need(frame_slot, torch.int32, "frame_slot")
+    _need(frame_reset, torch.int32, "frame_reset")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4:
+        raise MoEKernelError("track_update: boxes must be [F, K, 4]")
+    F, K, _ = (int(v) for v in boxes.shape)
+    if tuple(scores.shape) != (F, K) or tuple(labels.shape) != (F, K):
+        raise MoEKernelError("track_update: scores / labels must be [F, K]")
+    if tuple(frame_slot.shape) != (F,) or tuple(frame_reset.shape) != (F,):
+        raise MoEKernelError("track_update: frame_slot / frame_reset must be [F]")
+    if n_valid is not None:
+        _need(n_valid, torch.int32, "n_valid")
+        if tuple(n_valid.shape) != (F,):
+            raise MoEKernelError("track_update: n_valid must be [F]")
+    S, T = state.S, state.T
+    st_shapes = ((S, T, 8), (S, T), (S, T, 4), (S, 2))
+    st_dtypes = (torch.float32, torch.float32, torch.int32, torch.int32)
+    for t, s, d, name in zip(state.tensors(), st_shapes, st_dtypes, ("state.box", "state.score", "state.meta",
+                                                                    "state.seq")):
+        _need(t, d, name)
+        if tuple(t.shape) != s:
+            raise MoEKernelError(f"track_update: {name} must be {s}, got {tuple(t.shape)}")
+    dev = boxes.device
+    shapes = ((F, K), (F, K, 4), (F,))
+    dtypes = (torch.int32, torch.float32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        if len(out) != 3:
+            raise MoEKernelError("track_update: out must be (out_id, out_boxes, count)")
+        for t, s, d, name in zip(out, shapes, dtypes, ("out_id", "out_boxes", "count")):
+            _need(t, d, name)
+            if tuple(t.shape) != s:
+                raise MoEKernelError(f"track_update: {name} must be {s}, got {tuple(t.shape)}")
+    tensors = [boxes, scores, labels, frame_slot, frame_reset, *state.tensors(), *out]
+    tensors += [n_valid] if n_valid is not None else []
+    if any(t.device != dev for t in tensors):
+        raise MoEKernelError("track_update: all tensors must be on one device")
+    a = args
+    rc = lib().rtdetr_track_update(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), _ptr(frame_slot),
+                                   _ptr(frame_reset), F, K, S, T, float(a.track_high), float(a.track_low),
+                                   float(a.new_thr), float(a.match_iou), float(a.second_iou), int(a.max_age),
+                                   int(a.min_hits), float(a.alpha), float(a.beta), int(bool(a.class_agnostic)),
+                                   *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out), _stream())
+    _check(rc, "rtdetr_track_update")
     return out
 
 

@@ -840,6 +840,12 @@ class Prediction:
     source: torch.Tensor | None = None
     # merge="fuse": the candidates averaged into each row's box, its own included, int64 [n] (>= 1); None otherwise
     members: torch.Tensor | None = None
+    # track=...: the rows are the reported ones only; each row's track id, int64 [n] (from 1 per sequence), and the
+    # track's filtered box, fp32 [n, 4], clipped to the frame; the frame's sequence key and its 1-based number in it
+    track_ids: torch.Tensor | None = None
+    track_boxes: torch.Tensor | None = None
+    sequence: str | None = None
+    frame: int | None = None
 
 
 @dataclass
@@ -869,6 +875,30 @@ def coco_results(predictions) -> list:
     return rows
 
 
+def track_results(predictions) -> list:
+    """coco_results' rows (the detections' boxes) plus ``track_id`` and ``sequence``."""
+    rows = coco_results(predictions)
+    i = 0
+    for p in predictions:
+        for t in p.track_ids.tolist():
+            rows[i]["track_id"] = int(t)
+            rows[i]["sequence"] = p.sequence
+            i += 1
+    return rows
+
+
+def mot_lines(predictions) -> dict:
+    """{sequence: MOTChallenge text}: ``frame,id,x,y,w,h,score,-1,-1,-1`` per
+    reported row, frame 1-based within its sequence, the box the track's
+    filtered one."""
+    out = {}
+    for p in predictions:
+        lines = out.setdefault(p.sequence, [])
+        for t, (x1, y1, x2, y2), s in zip(p.track_ids.tolist(), p.track_boxes.tolist(), p.scores.tolist()):
+            lines.append(f"{p.frame},{int(t)},{x1:.3f},{y1:.3f},{x2 - x1:.3f},{y2 - y1:.3f},{s:.5f},-1,-1,-1")
+    return {k: "".join(line + "\n" for line in v) for k, v in out.items()}
+
+
 def _save_overlay(pred: Prediction, out_path: Path):
     from PIL import Image, ImageDraw
 
@@ -894,10 +924,42 @@ def predict_merge_on_gpu(dev: torch.device) -> bool:
     return dev.type == "cuda" and os.environ.get("MOE_PREDICT_MERGE", "1") != "0"
 
 
+def predict_track_on_gpu(dev: torch.device) -> bool:
+    """Whether predict(track=...) links the detections on the GPU
+    (rtdetr_track_update): on a GPU device unless MOE_PREDICT_TRACK=0 asks for
+    track.track_reference on the copied-back candidates."""
+    return dev.type == "cuda" and os.environ.get("MOE_PREDICT_TRACK", "1") != "0"
+
+
+def default_sequence_of(path) -> str:
+    """A frame's sequence: its parent directory's name."""
+    return Path(path).parent.name
+
+
+def frame_sequences(paths, sequence_of=None) -> list:
+    """[(key, sequence index, 1-based frame number)] per path: consecutive
+    frames with one key form a sequence, in the given order; a key that comes
+    back after another key is a ValueError."""
+    sequence_of = sequence_of or default_sequence_of
+    out, seen, cur, j, f = [], set(), None, -1, 0
+    for p in paths:
+        key = str(sequence_of(p))
+        if j < 0 or key != cur:
+            if key in seen:
+                raise ValueError(f"sequence {key!r} comes back at {p} after another sequence: the frames of a "
+                                 f"sequence must be consecutive in the source's order")
+            seen.add(key)
+            cur, j, f = key, j + 1, 0
+        f += 1
+        out.append((key, j, f))
+    return out
+
+
 @torch.no_grad()
 def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
             workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
-            merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55) -> PredictResults:
+            merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55, track=None,
+            sequence_of=None) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -944,12 +1006,38 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     clipping bounds -- go up with the batch's other small tensors; on a GPU the
     fusion is ONE HIP launch in place of the merge's (rtdetr_box_fuse;
     MOE_PREDICT_MERGE=0 or the CPU: fuse_reference) and ``Prediction.members``
-    (the candidates averaged into each row) joins the one packed copy back."""
+    (the candidates averaged into each row) joins the one packed copy back.
+    ``track``: a track.TrackArgs or a dict of its fields (True: the defaults)
+    links the detections of consecutive frames (track.track_reference's rule;
+    the defaults are ByteTrack's and not tuned here).  ``sequence_of`` maps a
+    path to its sequence's key (default: the parent directory's name);
+    consecutive frames with one key form a sequence, in the source's order, and
+    a key that comes back after another is a ValueError.  Sequence j keeps its
+    tracks in state slot j % batch of a track.TrackState on the device and
+    clears it at its first frame, so two sequences of one batch never share a
+    slot.  The candidates are postprocess_batched's rows with n_valid = the
+    rows with score >= conf (a prefix, counted on the device) or, with tiles,
+    the merge's / the fusion's kept rows and its count; the tracker is ONE HIP
+    launch per batch after them (rtdetr_track_update; fill slots are not
+    passed) and the one packed copy back gains the id and the track's box.
+    MOE_PREDICT_TRACK=0, the CPU device, or a merge that ran on the host
+    (MOE_PREDICT_MERGE=0 with tiles: the candidates are on the host already)
+    run track_reference on the copied-back candidates instead.  A frame's
+    Prediction then holds the reported rows only -- a subset of what the same
+    call without ``track`` returns, the same bits in boxes, scores and labels
+    -- and gains ``track_ids``, ``track_boxes`` (the filtered boxes, clipped to
+    the frame), ``sequence`` and ``frame``.  Files: tracks.json (the COCO rows
+    plus track_id and sequence) and mot/<sequence>.txt (frame,id,x,y,w,h,
+    score,-1,-1,-1; frame 1-based, the box the track's).  With ``track=None``
+    nothing of this runs."""
     from .merge import (FUSE_MAX_DET, FUSE_MAX_N, FUSE_MAX_P, MERGE_MAX_DET, MERGE_MAX_N, METRICS, fuse_reference,
                         merge_reference, parse_tiles, tile_windows)
     from .preprocess import (FrameSource, HostCollate, PackCollate, TileHostCollate, TilePackCollate, iter_batches,
                              mapped_sizes, padded_hw)
 
+    from .track import TRACK_MAX_K, TrackArgs, TrackState, new_state, track_reference
+
+    targs = None if track is None or track is False else TrackArgs.parse(track)
     tiles = parse_tiles(tiles)
     if merge not in ("nms", "fuse"):
         raise ValueError(f"merge must be 'nms' or 'fuse', got {merge!r}")
@@ -996,6 +1084,51 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
                              f"{FUSE_MAX_N} candidates and max_det {FUSE_MAX_DET}")
     gpu_merge = predict_merge_on_gpu(dev)
     ds = FrameSource(source, contexts=contexts)
+    gpu_track = False
+    if targs is not None:
+        if max_det > TRACK_MAX_K:
+            raise ValueError(f"track takes at most {TRACK_MAX_K} candidates per frame, got max_det {max_det}")
+        seq_of = frame_sequences(ds.paths, sequence_of)  # a returning key's ValueError, before any work
+        gpu_track = predict_track_on_gpu(dev) and (tiles is None or gpu_merge)
+        if gpu_track:
+            trk_state = TrackState(batch, targs.max_tracks, dev)
+        else:
+            host_states = [None] * batch
+
+    def track_tables(n_done, n):
+        """frame_slot / frame_reset of the batch's n frames, the first of which is frame n_done of the source."""
+        meta = seq_of[n_done:n_done + n]
+        return torch.tensor([[j % batch for _, j, _ in meta], [int(f == 1) for _, _, f in meta]], dtype=torch.int32)
+
+    def track_launch(n_done, tb_, ts_, tl_, nv, lim_):
+        """The batch's frames through rtdetr_track_update -> [n, K, 5] fp32 to pack: the id's bits, the clipped box."""
+        tab = track_tables(n_done, tb_.shape[0]).to(tb_.device)
+        oid, obx, _ = _lib.track_update(trk_state, tb_.contiguous(), ts_.contiguous(),
+                                        tl_.to(torch.int32).contiguous(), nv.to(torch.int32).contiguous(), tab[0],
+                                        tab[1], targs)
+        obx = torch.minimum(obx.clamp(min=0.0), lim_[:, None, :])
+        return torch.cat([oid.view(torch.float32)[..., None], obx], -1)
+
+    def tracked(n_done, i, row, size):
+        """Frame i of the batch: its valid rows [m, C] on the host -> (the reported rows, ids int64, track boxes).
+        On the GPU path the last five columns hold the kernel's id bits and box."""
+        if gpu_track:
+            ids = row[:, -5].contiguous().view(torch.int32)
+            tbx = row[:, -4:]
+            row = row[:, :-5]
+        else:
+            _, j, f = seq_of[n_done + i]
+            if f == 1:
+                host_states[j % batch] = new_state(targs.max_tracks)
+            oid, obx, _ = track_reference(host_states[j % batch], row[:, :4].numpy(), row[:, 4].numpy(),
+                                          row[:, 5].numpy(), None, targs)
+            ids = torch.from_numpy(oid)
+            lim_i = torch.tensor([[size[0], size[1], size[0], size[1]]], dtype=torch.float32)
+            tbx = torch.minimum(torch.from_numpy(obx).reshape(-1, 4).clamp(min=0.0), lim_i)
+        sel = ids >= 0
+        return row[sel], dict(track_ids=ids[sel].to(torch.int64), track_boxes=tbx[sel].contiguous(),
+                              sequence=seq_of[n_done + i][0], frame=seq_of[n_done + i][2])
+
     if tiles is None:
         collate = PackCollate(out_hw, pin=True) if gpu_resize else HostCollate(out_hw, pad_hw)
     else:
@@ -1107,11 +1240,14 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
                                        for x0, y0, tw, th in wins[i * n_tiles:(i + 1) * n_tiles]]
                                     for i, (fw, fh) in enumerate(sizes[:n])], dtype=torch.float32)
             if fuse and gpu_merge:
-                ob, osc, ol, osrc, _, om = _lib.box_fuse(cb, cs, cl.to(torch.int32), None, conf, merge_iou,
-                                                         merge_metric, max_det, class_agnostic, fuse_iou,
-                                                         win.to(cb.device))
-                packed = torch.cat([ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype),
-                                    om[..., None].to(ob.dtype)], -1).cpu()  # one copy back, members with it
+                ob, osc, ol, osrc, ocnt, om = _lib.box_fuse(cb, cs, cl.to(torch.int32), None, conf, merge_iou,
+                                                            merge_metric, max_det, class_agnostic, fuse_iou,
+                                                            win.to(cb.device))
+                cols = [ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype),
+                        om[..., None].to(ob.dtype)]
+                if gpu_track:
+                    cols.append(track_launch(len(preds), ob, osc, ol, ocnt, lim[:n]))
+                packed = torch.cat(cols, -1).cpu()  # one copy back, members with it
                 rows = [packed[i][packed[i][:, 6] >= 0] for i in range(n)]
                 members = [row[:, 7].to(torch.int64) for row in rows]
             elif fuse:
@@ -1126,10 +1262,12 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
                                            keep[:, None].to(packed.dtype)], -1))
                     members.append(torch.from_numpy(mem).to(torch.int64))
             elif gpu_merge:
-                ob, osc, ol, osrc, _ = _lib.nms_merge(cb, cs, cl.to(torch.int32), None, conf, merge_iou, merge_metric,
-                                                      max_det, class_agnostic)
-                packed = torch.cat([ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype)],
-                                   -1).cpu()  # one copy back; src < 0 marks the rows past the kept ones
+                ob, osc, ol, osrc, ocnt = _lib.nms_merge(cb, cs, cl.to(torch.int32), None, conf, merge_iou,
+                                                         merge_metric, max_det, class_agnostic)
+                cols = [ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype)]
+                if gpu_track:
+                    cols.append(track_launch(len(preds), ob, osc, ol, ocnt, lim[:n]))
+                packed = torch.cat(cols, -1).cpu()  # one copy back; src < 0 marks the rows past the kept ones
                 rows = [packed[i][packed[i][:, 6] >= 0] for i in range(n)]
             else:
                 packed = torch.cat([cb, cs[..., None], cl[..., None].to(cb.dtype)], -1).cpu()
@@ -1138,22 +1276,38 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
                     keep = torch.from_numpy(merge_reference(packed[i][:, :4], packed[i][:, 4], packed[i][:, 5], None,
                                                             conf, merge_iou, merge_metric, max_det, class_agnostic))
                     rows.append(torch.cat([packed[i][keep], keep[:, None].to(packed.dtype)], -1))
+            n_done = len(preds)
             for i, row in enumerate(rows):
+                tr = {}
+                if targs is not None:
+                    # column 7: the row's number, so that the members follow the reported rows
+                    row = torch.cat([row[:, :7], torch.arange(row.shape[0], dtype=row.dtype)[:, None], row[:, 7:]], -1)
+                    row, tr = tracked(n_done, i, row, sizes[i])
+                    if members is not None:
+                        members[i] = members[i][row[:, 7].to(torch.int64)]
                 preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
                                         boxes=row[:, :4].contiguous(), scores=row[:, 4].contiguous(),
                                         labels=row[:, 5].to(torch.int64), source=row[:, 6].to(torch.int64) // k,
-                                        members=None if members is None else members[i]))
+                                        members=None if members is None else members[i], **tr))
             t_pre += t_tile[0]
             t_inf += t_tile[1]
             t_post -= t_tile[0] + t_tile[1]  # what is left of t3 - t2 is postprocessing: every pass's and the merge
         else:
-            packed = torch.cat([boxes, scores[..., None], labels[..., None].to(boxes.dtype)], -1).cpu()  # one copy back
+            cols = [boxes, scores[..., None], labels[..., None].to(boxes.dtype)]
+            if gpu_track:  # the tracker on the candidates where they stand; its id and box join the copy back
+                cols = [c[:n] for c in cols] + [track_launch(len(preds), boxes[:n], scores[:n], labels[:n],
+                                                             (scores[:n] >= conf).sum(1), lim[:n])]
+            packed = torch.cat(cols, -1).cpu()  # one copy back
+            n_done = len(preds)
             for i in range(n):
                 row = packed[i]
                 keep = row[:, 4] >= conf  # postprocess_batched's rows are already best first
+                row, tr = row[keep], {}
+                if targs is not None:
+                    row, tr = tracked(n_done, i, row, sizes[i])
                 preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
-                                        boxes=row[keep, :4].contiguous(), scores=row[keep, 4].contiguous(),
-                                        labels=row[keep, 5].to(torch.int64)))
+                                        boxes=row[:, :4].contiguous(), scores=row[:, 4].contiguous(),
+                                        labels=row[:, 5].to(torch.int64), **tr))
         t3 = time.perf_counter()
         t_pre += t1 - t0 - t_cap
         t_inf += t2 - t1
@@ -1170,7 +1324,21 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         save_dir.mkdir(parents=True, exist_ok=True)
         if save_json:
             (save_dir / "predictions.json").write_text(json.dumps(coco_results(preds)))
+        if targs is not None:
+            (save_dir / "tracks.json").write_text(json.dumps(track_results(preds)))
+            (save_dir / "mot").mkdir(exist_ok=True)
+            for key, text in mot_lines(preds).items():
+                (save_dir / "mot" / (key.replace("/", "_") + ".txt")).write_text(text)
         if save_img:
             for p in preds:
                 _save_overlay(p, save_dir / Path(p.path).name)
     return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=ModelHandle(model))
+
+
+def track(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.1, tracker=None, **kw) -> PredictResults:
+    """``predict`` with tracking on: ``tracker`` a track.TrackArgs or a dict of
+    its fields (None: the defaults); ``conf`` defaults to the tracker's low
+    band, so that low-score rows can keep a track alive.  Every other argument
+    is predict's."""
+    return predict(weights, source, imgsz=imgsz, batch=batch, device=device, conf=conf,
+                   track=True if tracker is None else tracker, **kw)

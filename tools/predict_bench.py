@@ -11,6 +11,13 @@ the tiled legs fuse the boxes (rtdetr_box_fuse / merge.fuse_reference).
 
   python tools/predict_bench.py [--model rtdetr-r50-moe8-top2] [--n 64] [--batch 16] [--rounds 3] [--workers 4]
   python tools/predict_bench.py --tiles 2x2 [--conf 0.25]
+With --track it runs, on the same files (one sequence) and alternately,
+prediction with the tracker on the GPU (MOE_PREDICT_TRACK=1), on the host
+(MOE_PREDICT_TRACK=0) and without it, at conf 0; the random weights score every
+query alike, so the tracker's bands are set at the quartiles of the distinct
+scores of an untimed first run.
+
+  python tools/predict_bench.py --track
 """
 from __future__ import annotations
 
@@ -68,6 +75,38 @@ def tiles_leg(a, d: Path, engine):
     print(json.dumps(out), flush=True)
 
 
+def track_leg(a, d: Path, engine):
+    """Tracking on the GPU, on the host and off, alternated per round."""
+    os.environ["MOE_PREDICT_RESIZE"] = "1"
+    torch.manual_seed(0)
+    res = engine.predict(a.model, d, batch=a.batch, device=a.device, conf=0.0, workers=a.workers)
+    u = torch.unique(torch.cat([p.scores for p in res.predictions]))
+    lo, hi, new = (float(u[min(len(u) * q // 4, len(u) - 1)]) for q in (1, 2, 3))
+    tracker = dict(track_low=lo, track_high=hi, new_thr=new)
+    legs = (("track_gpu", tracker, "1"), ("track_host", tracker, "0"), ("track_off", None, "1"))
+    runs = {name: [] for name, _, _ in legs}
+    for r in range(a.rounds):
+        for name, trk, switch in legs:
+            os.environ["MOE_PREDICT_TRACK"] = switch
+            torch.manual_seed(0)
+            t0 = time.perf_counter()
+            res = engine.predict(a.model, d, batch=a.batch, device=a.device, conf=0.0, workers=a.workers, track=trk)
+            line = {"round": r, "leg": name, "images": len(res.predictions),
+                    "rows": sum(len(p.scores) for p in res.predictions),
+                    "wall_s": round(time.perf_counter() - t0, 2), **{k: round(v, 3) for k, v in res.speed.items()}}
+            if trk is not None:
+                line["tracks"] = len({int(t) for p in res.predictions for t in p.track_ids})
+            print(json.dumps(line), flush=True)
+            runs[name].append(res.speed)
+    os.environ.pop("MOE_PREDICT_TRACK", None)
+    out = {"model": a.model, "batch": a.batch, "workers": a.workers, "tracker": tracker}
+    for name, _, _ in legs:
+        for k in ("preprocess", "inference", "postprocess"):
+            v = [s[k] for s in runs[name]]
+            out[f"{name}/{k}"] = [round(statistics.median(v), 3), round(min(v), 3), round(max(v), 3)]
+    print(json.dumps(out), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="rtdetr-r50-moe8-top2")
@@ -80,6 +119,8 @@ def main(argv=None):
     ap.add_argument("--conf", type=float, default=0.25)
     ap.add_argument("--merge", default="nms", choices=("nms", "fuse"),
                     help="with --tiles: the merge of the tiled legs (fuse: rtdetr_box_fuse / fuse_reference)")
+    ap.add_argument("--track", action="store_true",
+                    help="time prediction with the tracker on the GPU, on the host and off (conf 0, one sequence)")
     a = ap.parse_args(argv)
     from src.rtdetr_moe import engine
 
@@ -102,6 +143,9 @@ def main(argv=None):
             rsz.append(1e3 * (time.perf_counter() - t1))
         print(json.dumps({"jpeg_decode_ms_per_frame_one_core": round(statistics.median(dec), 2),
                           "host_resize_ms_per_frame_one_core": round(statistics.median(rsz), 2)}), flush=True)
+        if a.track:
+            track_leg(a, d, engine)
+            return
         if a.tiles:
             tiles_leg(a, d, engine)
             return
