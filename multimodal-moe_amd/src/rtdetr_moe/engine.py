@@ -34,6 +34,10 @@ from .criterion import SetCriterion
 from .data import CocoDataset, SyntheticZOD, YoloDataset, collate
 from .metrics import BoxMetrics, DetectionEvaluator, DeviceDetectionEvaluator, gt_xyxy_pixels, named_bands
 from .model import RTDETRMoE
+# prediction on image files lives in predictor.py; its names stay reachable as engine.predict, engine.Prediction, ...
+from .predictor import (Prediction, PredictResults, coco_results, default_sequence_of, frame_sequences,  # noqa: F401
+                        mot_lines, predict, predict_merge_on_gpu, predict_resize_on_gpu, predict_track_on_gpu, track,
+                        track_results)
 from .schedule import accumulate_count, schedule_at, warmup_iters
 
 
@@ -822,523 +826,3 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
     return DetMetrics(results_dict=_results_dict(box), box=box, speed=speed, model=ModelHandle(model),
                       save_dir=save_dir, moe=_moe_stats(model), context=report, size=sizes)
 
-
-# ---------------------------------------------------------------------------
-# prediction on image files
-# ---------------------------------------------------------------------------
-@dataclass
-class Prediction:
-    """One image's detections: rows with score >= conf, at most max_det, best
-    first; boxes fp32 [n, 4] xyxy in source pixels, clipped to the frame."""
-    path: str
-    size: tuple  # (w, h) of the source frame
-    ctx: int
-    boxes: torch.Tensor
-    scores: torch.Tensor
-    labels: torch.Tensor
-    # tiled prediction: the pass each row came from, int64 [n]: 0 the full frame, 1 + t tile t; None without tiles
-    source: torch.Tensor | None = None
-    # merge="fuse": the candidates averaged into each row's box, its own included, int64 [n] (>= 1); None otherwise
-    members: torch.Tensor | None = None
-    # track=...: the rows are the reported ones only; each row's track id, int64 [n] (from 1 per sequence), and the
-    # track's filtered box, fp32 [n, 4], clipped to the frame; the frame's sequence key and its 1-based number in it
-    track_ids: torch.Tensor | None = None
-    track_boxes: torch.Tensor | None = None
-    sequence: str | None = None
-    frame: int | None = None
-
-
-@dataclass
-class PredictResults:
-    predictions: list
-    speed: dict
-    save_dir: Path | None
-    model: ModelHandle | None
-
-
-def _image_id(path):
-    stem = Path(path).stem
-    return int(stem) if stem.isdigit() else stem
-
-
-def coco_results(predictions) -> list:
-    """COCO results rows as Ultralytics' save_json writes them: image_id (the
-    stem, an int when numeric), file_name, category_id, bbox xywh in source
-    pixels to 3 decimals, score to 5."""
-    rows = []
-    for p in predictions:
-        for box, s, c in zip(p.boxes.tolist(), p.scores.tolist(), p.labels.tolist()):
-            x1, y1, x2, y2 = box
-            rows.append({"image_id": _image_id(p.path), "file_name": Path(p.path).name, "category_id": int(c),
-                         "bbox": [round(x1, 3), round(y1, 3), round(x2 - x1, 3), round(y2 - y1, 3)],
-                         "score": round(s, 5)})
-    return rows
-
-
-def track_results(predictions) -> list:
-    """coco_results' rows (the detections' boxes) plus ``track_id`` and ``sequence``."""
-    rows = coco_results(predictions)
-    i = 0
-    for p in predictions:
-        for t in p.track_ids.tolist():
-            rows[i]["track_id"] = int(t)
-            rows[i]["sequence"] = p.sequence
-            i += 1
-    return rows
-
-
-def mot_lines(predictions) -> dict:
-    """{sequence: MOTChallenge text}: ``frame,id,x,y,w,h,score,-1,-1,-1`` per
-    reported row, frame 1-based within its sequence, the box the track's
-    filtered one."""
-    out = {}
-    for p in predictions:
-        lines = out.setdefault(p.sequence, [])
-        for t, (x1, y1, x2, y2), s in zip(p.track_ids.tolist(), p.track_boxes.tolist(), p.scores.tolist()):
-            lines.append(f"{p.frame},{int(t)},{x1:.3f},{y1:.3f},{x2 - x1:.3f},{y2 - y1:.3f},{s:.5f},-1,-1,-1")
-    return {k: "".join(line + "\n" for line in v) for k, v in out.items()}
-
-
-def _save_overlay(pred: Prediction, out_path: Path):
-    from PIL import Image, ImageDraw
-
-    im = Image.open(pred.path).convert("RGB")
-    draw = ImageDraw.Draw(im)
-    for (x1, y1, x2, y2), s, c in zip(pred.boxes.tolist(), pred.scores.tolist(), pred.labels.tolist()):
-        draw.rectangle([x1, y1, max(x2, x1), max(y2, y1)], outline=(255, 64, 64), width=max(1, im.width // 640))
-        draw.text((x1 + 2, y1 + 2), f"{int(c)} {s:.2f}", fill=(255, 255, 0))
-    im.save(out_path)
-
-
-def predict_resize_on_gpu(dev: torch.device) -> bool:
-    """Whether predict resizes on the GPU (rtdetr_resize_pad_u8): on a GPU
-    device unless MOE_PREDICT_RESIZE=0 asks for the loader's host path."""
-    return dev.type == "cuda" and os.environ.get("MOE_PREDICT_RESIZE", "1") != "0"
-
-
-def predict_merge_on_gpu(dev: torch.device) -> bool:
-    """Whether tiled prediction merges its passes on the GPU (rtdetr_nms_merge;
-    merge="fuse": rtdetr_box_fuse): on a GPU device unless MOE_PREDICT_MERGE=0
-    asks for merge.merge_reference (fuse_reference) on the copied-back
-    candidates."""
-    return dev.type == "cuda" and os.environ.get("MOE_PREDICT_MERGE", "1") != "0"
-
-
-def predict_track_on_gpu(dev: torch.device) -> bool:
-    """Whether predict(track=...) links the detections on the GPU
-    (rtdetr_track_update): on a GPU device unless MOE_PREDICT_TRACK=0 asks for
-    track.track_reference on the copied-back candidates."""
-    return dev.type == "cuda" and os.environ.get("MOE_PREDICT_TRACK", "1") != "0"
-
-
-def default_sequence_of(path) -> str:
-    """A frame's sequence: its parent directory's name."""
-    return Path(path).parent.name
-
-
-def frame_sequences(paths, sequence_of=None) -> list:
-    """[(key, sequence index, 1-based frame number)] per path: consecutive
-    frames with one key form a sequence, in the given order; a key that comes
-    back after another key is a ValueError."""
-    sequence_of = sequence_of or default_sequence_of
-    out, seen, cur, j, f = [], set(), None, -1, 0
-    for p in paths:
-        key = str(sequence_of(p))
-        if j < 0 or key != cur:
-            if key in seen:
-                raise ValueError(f"sequence {key!r} comes back at {p} after another sequence: the frames of a "
-                                 f"sequence must be consecutive in the source's order")
-            seen.add(key)
-            cur, j, f = key, j + 1, 0
-        f += 1
-        out.append((key, j, f))
-    return out
-
-
-@torch.no_grad()
-def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
-            workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
-            merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55, track=None,
-            sequence_of=None) -> PredictResults:
-    """Detect on image files of any size.  ``source``: a directory, a glob, a
-    list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
-    batch is one upload of the decoded uint8 frames and ONE HIP launch
-    (rtdetr_resize_pad_u8: antialiased bilinear resize to ``imgsz``, / 255,
-    padding to a multiple of 32, channels-last), the graph-replayed EvalForward
-    (a partial last batch is filled with empty slots, so one graph serves the
-    run), postprocess_batched with each image's size mapped to its source
-    frame, and one copy back.  With device="cpu" or MOE_PREDICT_RESIZE=0 the
-    frames take the datasets' host path instead (PIL resize + _padded_image).
-    ``workers`` threads decode (and, on the host path, resize) ahead of the GPU
-    (preprocess.iter_batches); 0 reads in the calling thread.
-    ``.speed``: ms per image, wall clock as ``_evaluate`` takes it (graph
-    capture excluded): "preprocess" from asking the loader for the batch to the
-    model's input standing on the device (decode, upload, the resize launch, or
-    the host resize), "inference" the forward, "postprocess" the boxes back on
-    the host.  Files, under ``project/name`` when both are given:
-    predictions.json (``save_json``; COCO results) and ``save_img`` overlays.
-    ``tiles=(rows, cols)``: sliced inference.  Each frame is also detected on
-    an overlapping grid of crops (merge.tile_windows at ``tile_overlap``), which
-    reach the model at up to rows x cols times the full frame's resolution, and
-    the passes are merged (merge.merge_reference's rule with ``conf``,
-    ``merge_iou``, ``merge_metric`` "ios" / "iou", ``class_agnostic`` and
-    ``max_det``).  On a GPU the tiles are further rows of the resize kernel's
-    descriptor table into the buffer already uploaded -- cut into chunks of
-    ``batch`` slots, each one resize launch, one replay of the same captured
-    graph and one postprocess_batched, boxes shifted by the window's origin and
-    clipped to the window -- and the merge of a batch's [B, (1 + rows cols) k,
-    4] candidates (the full frame first, then the tiles row-major; k =
-    min(max_det, queries x classes), at most 4096 in all) is ONE HIP launch
-    (rtdetr_nms_merge; MOE_PREDICT_MERGE=0: merge_reference on the host) and
-    one packed copy back.  On the CPU, or with MOE_PREDICT_RESIZE=0, the tiles
-    are cropped and resized on the host.  ``Prediction.source`` then holds the
-    pass of every row and ``.speed`` gains "passes" (1 + rows cols; the three
-    timings include every pass, the merge under "postprocess").  Without
-    ``tiles`` nothing of this runs.
-    ``merge``: "nms" (the default) keeps the best copy of every object as it
-    stands.  "fuse" (tiles only) keeps the same rows -- same scores, labels,
-    order and ``source`` -- and replaces each box by the score-weighted average
-    of the copies of its object: the candidates it suppressed whose box agrees
-    with it where both passes could see (IoU > ``fuse_iou`` after clamping both
-    into the two windows' intersection; 0.55 is the usual weighted-box-fusion
-    default, not tuned here), a side cut by a tile's edge left out of the
-    average (merge.fuse_reference).  The windows -- the frame, then the tiles'
-    clipping bounds -- go up with the batch's other small tensors; on a GPU the
-    fusion is ONE HIP launch in place of the merge's (rtdetr_box_fuse;
-    MOE_PREDICT_MERGE=0 or the CPU: fuse_reference) and ``Prediction.members``
-    (the candidates averaged into each row) joins the one packed copy back.
-    ``track``: a track.TrackArgs or a dict of its fields (True: the defaults)
-    links the detections of consecutive frames (track.track_reference's rule;
-    the defaults are ByteTrack's and not tuned here).  ``sequence_of`` maps a
-    path to its sequence's key (default: the parent directory's name);
-    consecutive frames with one key form a sequence, in the source's order, and
-    a key that comes back after another is a ValueError.  Sequence j keeps its
-    tracks in state slot j % batch of a track.TrackState on the device and
-    clears it at its first frame, so two sequences of one batch never share a
-    slot.  The candidates are postprocess_batched's rows with n_valid = the
-    rows with score >= conf (a prefix, counted on the device) or, with tiles,
-    the merge's / the fusion's kept rows and its count; the tracker is ONE HIP
-    launch per batch after them (rtdetr_track_update; fill slots are not
-    passed) and the one packed copy back gains the id and the track's box.
-    MOE_PREDICT_TRACK=0, the CPU device, or a merge that ran on the host
-    (MOE_PREDICT_MERGE=0 with tiles: the candidates are on the host already)
-    run track_reference on the copied-back candidates instead.  A frame's
-    Prediction then holds the reported rows only -- a subset of what the same
-    call without ``track`` returns, the same bits in boxes, scores and labels
-    -- and gains ``track_ids``, ``track_boxes`` (the filtered boxes, clipped to
-    the frame), ``sequence`` and ``frame``.  Files: tracks.json (the COCO rows
-    plus track_id and sequence) and mot/<sequence>.txt (frame,id,x,y,w,h,
-    score,-1,-1,-1; frame 1-based, the box the track's).  With ``track=None``
-    nothing of this runs."""
-    from .merge import (FUSE_MAX_DET, FUSE_MAX_N, FUSE_MAX_P, MERGE_MAX_DET, MERGE_MAX_N, METRICS, fuse_reference,
-                        merge_reference, parse_tiles, tile_windows)
-    from .preprocess import (FrameSource, HostCollate, PackCollate, TileHostCollate, TilePackCollate, iter_batches,
-                             mapped_sizes, padded_hw)
-
-    from .track import TRACK_MAX_K, TrackArgs, TrackState, new_state, track_reference
-
-    targs = None if track is None or track is False else TrackArgs.parse(track)
-    tiles = parse_tiles(tiles)
-    if merge not in ("nms", "fuse"):
-        raise ValueError(f"merge must be 'nms' or 'fuse', got {merge!r}")
-    fuse = merge == "fuse"
-    if fuse:
-        if tiles is None:
-            raise ValueError("merge='fuse' fuses the passes of tiled prediction: give tiles=(rows, cols)")
-        if not 0.0 <= float(fuse_iou) <= 1.0:
-            raise ValueError(f"fuse_iou must be in [0, 1], got {fuse_iou}")
-    if tiles is not None:
-        tile_windows(2 * tiles[1], 2 * tiles[0], tiles, tile_overlap)  # the overlap's ValueError, before any work
-        if merge_metric not in METRICS:
-            raise ValueError(f"merge_metric must be one of {sorted(METRICS)}, got {merge_metric!r}")
-        if not 0.0 <= float(merge_iou) <= 1.0:
-            raise ValueError(f"merge_iou must be in [0, 1], got {merge_iou}")
-    devices = parse_device(device)
-    dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
-    on_gpu = dev.type == "cuda"
-    if on_gpu:
-        torch.cuda.set_device(dev)
-        from ..moe import _lib
-
-        _lib.lib()
-    batch, max_det = int(batch), int(max_det)
-    if batch < 1 or max_det < 1:
-        raise ValueError(f"batch {batch} and max_det {max_det} must be >= 1")
-    model = load_model(weights, dev)
-    if on_gpu:
-        model = model.to(memory_format=torch.channels_last)
-    was_training = model.training
-    model.eval()
-    out_hw, pad_hw = padded_hw(imgsz)
-    gpu_resize = predict_resize_on_gpu(dev)
-    n_tiles = 0
-    if tiles is not None:
-        n_tiles = tiles[0] * tiles[1]
-        n_cand = (1 + n_tiles) * min(max_det, model.decoder.num_queries * model.num_classes)
-        if n_cand > MERGE_MAX_N or max_det > MERGE_MAX_DET:
-            raise ValueError(f"tiles {tiles[0]}x{tiles[1]} with max_det {max_det} is {n_cand} candidates per frame: "
-                             f"the merge takes at most {MERGE_MAX_N} candidates and max_det {MERGE_MAX_DET}")
-        if fuse and (n_cand > FUSE_MAX_N or max_det > FUSE_MAX_DET or 1 + n_tiles > FUSE_MAX_P):
-            raise ValueError(f"tiles {tiles[0]}x{tiles[1]} with max_det {max_det} is {1 + n_tiles} passes and "
-                             f"{n_cand} candidates per frame: the fusion takes at most {FUSE_MAX_P} passes, "
-                             f"{FUSE_MAX_N} candidates and max_det {FUSE_MAX_DET}")
-    gpu_merge = predict_merge_on_gpu(dev)
-    ds = FrameSource(source, contexts=contexts)
-    gpu_track = False
-    if targs is not None:
-        if max_det > TRACK_MAX_K:
-            raise ValueError(f"track takes at most {TRACK_MAX_K} candidates per frame, got max_det {max_det}")
-        seq_of = frame_sequences(ds.paths, sequence_of)  # a returning key's ValueError, before any work
-        gpu_track = predict_track_on_gpu(dev) and (tiles is None or gpu_merge)
-        if gpu_track:
-            trk_state = TrackState(batch, targs.max_tracks, dev)
-        else:
-            host_states = [None] * batch
-
-    def track_tables(n_done, n):
-        """frame_slot / frame_reset of the batch's n frames, the first of which is frame n_done of the source."""
-        meta = seq_of[n_done:n_done + n]
-        return torch.tensor([[j % batch for _, j, _ in meta], [int(f == 1) for _, _, f in meta]], dtype=torch.int32)
-
-    def track_launch(n_done, tb_, ts_, tl_, nv, lim_):
-        """The batch's frames through rtdetr_track_update -> [n, K, 5] fp32 to pack: the id's bits, the clipped box."""
-        tab = track_tables(n_done, tb_.shape[0]).to(tb_.device)
-        oid, obx, _ = _lib.track_update(trk_state, tb_.contiguous(), ts_.contiguous(),
-                                        tl_.to(torch.int32).contiguous(), nv.to(torch.int32).contiguous(), tab[0],
-                                        tab[1], targs)
-        obx = torch.minimum(obx.clamp(min=0.0), lim_[:, None, :])
-        return torch.cat([oid.view(torch.float32)[..., None], obx], -1)
-
-    def tracked(n_done, i, row, size):
-        """Frame i of the batch: its valid rows [m, C] on the host -> (the reported rows, ids int64, track boxes).
-        On the GPU path the last five columns hold the kernel's id bits and box."""
-        if gpu_track:
-            ids = row[:, -5].contiguous().view(torch.int32)
-            tbx = row[:, -4:]
-            row = row[:, :-5]
-        else:
-            _, j, f = seq_of[n_done + i]
-            if f == 1:
-                host_states[j % batch] = new_state(targs.max_tracks)
-            oid, obx, _ = track_reference(host_states[j % batch], row[:, :4].numpy(), row[:, 4].numpy(),
-                                          row[:, 5].numpy(), None, targs)
-            ids = torch.from_numpy(oid)
-            lim_i = torch.tensor([[size[0], size[1], size[0], size[1]]], dtype=torch.float32)
-            tbx = torch.minimum(torch.from_numpy(obx).reshape(-1, 4).clamp(min=0.0), lim_i)
-        sel = ids >= 0
-        return row[sel], dict(track_ids=ids[sel].to(torch.int64), track_boxes=tbx[sel].contiguous(),
-                              sequence=seq_of[n_done + i][0], frame=seq_of[n_done + i][2])
-
-    if tiles is None:
-        collate = PackCollate(out_hw, pin=True) if gpu_resize else HostCollate(out_hw, pad_hw)
-    else:
-        collate = TilePackCollate(out_hw, tiles, tile_overlap, pin=True) if gpu_resize \
-            else TileHostCollate(out_hw, pad_hw, tiles, tile_overlap)
-    fwd = EvalForward(model)
-    from ..moe.context import MISSING_ID
-
-    preds = []
-    t_pre = t_inf = t_post = 0.0
-    it = iter_batches(ds, batch, workers, collate)  # decoding threads (no processes forked under a GPU context)
-    while True:
-        t0 = time.perf_counter()
-        try:
-            bt = next(it)
-        except StopIteration:
-            break
-        n = len(bt["paths"])
-        fill = batch - n if on_gpu else 0  # empty slots: the captured batch size serves a partial last batch
-        ctx = bt["ctx"]
-        if fill:
-            ctx = torch.cat([ctx, torch.full((fill,), MISSING_ID, dtype=torch.int32)])
-        ctx = ctx.to(dev)
-        t_cap = 0.0
-        if gpu_resize:
-            desc = bt["desc"]
-            if fill:
-                desc = torch.cat([desc, torch.zeros((fill, 4), dtype=torch.int64)])
-            src = bt["buf"].to(dev, non_blocking=True)  # the one upload; the tile passes read it again
-            images = _lib.resize_pad(src, desc, out_hw, pad_hw)
-        else:
-            images = bt["images"]
-            if fill:
-                images = torch.cat([images, images.new_zeros((fill,) + tuple(images.shape[1:]))])
-            images = images.to(dev, non_blocking=True)
-            if on_gpu:
-                images = images.contiguous(memory_format=torch.channels_last)
-        if on_gpu:
-            tc = time.perf_counter()
-            fwd.prepare(images, ctx)  # first batch: graph capture, untimed
-            t_cap = time.perf_counter() - tc
-            torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        out = fwd(images, ctx)
-        if on_gpu:
-            torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        sizes = bt["sizes"]
-        mapped = mapped_sizes(sizes, out_hw, pad_hw) + [(1.0, 1.0)] * fill
-        boxes, scores, labels = model.postprocess_batched(out, mapped, num_top=max_det)
-        lim = torch.tensor([[w, h, w, h] for w, h in sizes] + [[1.0] * 4] * fill, dtype=boxes.dtype,
-                           device=boxes.device)
-        boxes = torch.minimum(boxes.clamp(min=0.0), lim[:, None, :])
-        if tiles is not None:
-            # the tile passes: n n_tiles slots, frame-major, in chunks of ``batch`` on the captured graph
-            wins = [w for frame_wins in bt["windows"] for w in frame_wins]
-            slot_ctx = bt["ctx"].repeat_interleave(n_tiles)
-            tb, ts, tl = [], [], []
-            t_tile = [0.0, 0.0]  # preprocess, inference of the tile passes
-            for s in range(0, len(wins), batch):
-                ta = time.perf_counter()
-                w = wins[s:s + batch]
-                cfill = batch - len(w) if on_gpu else 0
-                cctx = slot_ctx[s:s + batch]
-                if cfill:
-                    cctx = torch.cat([cctx, torch.full((cfill,), MISSING_ID, dtype=torch.int32)])
-                cctx = cctx.to(dev)
-                if gpu_resize:
-                    tdesc = bt["tile_desc"][s:s + batch]
-                    if cfill:
-                        tdesc = torch.cat([tdesc, torch.zeros((cfill, 4), dtype=torch.int64)])
-                    timg = _lib.resize_pad(src, tdesc, out_hw, pad_hw)
-                else:
-                    timg = bt["tile_images"][s:s + batch]
-                    if cfill:
-                        timg = torch.cat([timg, timg.new_zeros((cfill,) + tuple(timg.shape[1:]))])
-                    timg = timg.to(dev, non_blocking=True)
-                    if on_gpu:
-                        timg = timg.contiguous(memory_format=torch.channels_last)
-                if on_gpu:
-                    torch.cuda.synchronize()
-                tb0 = time.perf_counter()
-                tout = fwd(timg, cctx)
-                if on_gpu:
-                    torch.cuda.synchronize()
-                t_tile[0] += tb0 - ta
-                t_tile[1] += time.perf_counter() - tb0
-                tmapped = mapped_sizes([(tw, th) for _, _, tw, th in w], out_hw, pad_hw) + [(1.0, 1.0)] * cfill
-                b_, s_, l_ = model.postprocess_batched(tout, tmapped, num_top=max_det)
-                lo = torch.tensor([[x0, y0, x0, y0] for x0, y0, _, _ in w] + [[0.0] * 4] * cfill, dtype=b_.dtype,
-                                  device=b_.device)
-                hi = torch.tensor([[x0 + tw, y0 + th, x0 + tw, y0 + th] for x0, y0, tw, th in w]
-                                  + [[1.0] * 4] * cfill, dtype=b_.dtype, device=b_.device)
-                # shifted by the window's origin, clipped to the window
-                b_ = torch.minimum(torch.maximum(b_ + lo[:, None, :], lo[:, None, :]), hi[:, None, :])
-                tb.append(b_[:len(w)])
-                ts.append(s_[:len(w)])
-                tl.append(l_[:len(w)])
-            k = boxes.shape[1]
-            # candidates per frame: the full frame's k rows, then each tile's, row-major
-            cb = torch.cat([boxes[:n], torch.cat(tb).reshape(n, n_tiles * k, 4)], 1)
-            cs = torch.cat([scores[:n], torch.cat(ts).reshape(n, n_tiles * k)], 1)
-            cl = torch.cat([labels[:n], torch.cat(tl).reshape(n, n_tiles * k)], 1)
-            members = None
-            if fuse:
-                # the passes' windows per frame: the frame, then the bounds each tile's boxes were clipped with
-                win = torch.tensor([[[0.0, 0.0, float(fw), float(fh)]]
-                                    + [[float(x0), float(y0), float(x0 + tw), float(y0 + th)]
-                                       for x0, y0, tw, th in wins[i * n_tiles:(i + 1) * n_tiles]]
-                                    for i, (fw, fh) in enumerate(sizes[:n])], dtype=torch.float32)
-            if fuse and gpu_merge:
-                ob, osc, ol, osrc, ocnt, om = _lib.box_fuse(cb, cs, cl.to(torch.int32), None, conf, merge_iou,
-                                                            merge_metric, max_det, class_agnostic, fuse_iou,
-                                                            win.to(cb.device))
-                cols = [ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype),
-                        om[..., None].to(ob.dtype)]
-                if gpu_track:
-                    cols.append(track_launch(len(preds), ob, osc, ol, ocnt, lim[:n]))
-                packed = torch.cat(cols, -1).cpu()  # one copy back, members with it
-                rows = [packed[i][packed[i][:, 6] >= 0] for i in range(n)]
-                members = [row[:, 7].to(torch.int64) for row in rows]
-            elif fuse:
-                packed = torch.cat([cb, cs[..., None], cl[..., None].to(cb.dtype)], -1).cpu()
-                rows, members = [], []
-                for i in range(n):
-                    keep, fb, mem = fuse_reference(packed[i][:, :4], packed[i][:, 4], packed[i][:, 5], None, conf,
-                                                   merge_iou, merge_metric, max_det, class_agnostic, fuse_iou,
-                                                   win[i])
-                    keep = torch.from_numpy(keep)
-                    rows.append(torch.cat([torch.from_numpy(fb).reshape(-1, 4), packed[i][keep][:, 4:],
-                                           keep[:, None].to(packed.dtype)], -1))
-                    members.append(torch.from_numpy(mem).to(torch.int64))
-            elif gpu_merge:
-                ob, osc, ol, osrc, ocnt = _lib.nms_merge(cb, cs, cl.to(torch.int32), None, conf, merge_iou,
-                                                         merge_metric, max_det, class_agnostic)
-                cols = [ob, osc[..., None], ol[..., None].to(ob.dtype), osrc[..., None].to(ob.dtype)]
-                if gpu_track:
-                    cols.append(track_launch(len(preds), ob, osc, ol, ocnt, lim[:n]))
-                packed = torch.cat(cols, -1).cpu()  # one copy back; src < 0 marks the rows past the kept ones
-                rows = [packed[i][packed[i][:, 6] >= 0] for i in range(n)]
-            else:
-                packed = torch.cat([cb, cs[..., None], cl[..., None].to(cb.dtype)], -1).cpu()
-                rows = []
-                for i in range(n):
-                    keep = torch.from_numpy(merge_reference(packed[i][:, :4], packed[i][:, 4], packed[i][:, 5], None,
-                                                            conf, merge_iou, merge_metric, max_det, class_agnostic))
-                    rows.append(torch.cat([packed[i][keep], keep[:, None].to(packed.dtype)], -1))
-            n_done = len(preds)
-            for i, row in enumerate(rows):
-                tr = {}
-                if targs is not None:
-                    # column 7: the row's number, so that the members follow the reported rows
-                    row = torch.cat([row[:, :7], torch.arange(row.shape[0], dtype=row.dtype)[:, None], row[:, 7:]], -1)
-                    row, tr = tracked(n_done, i, row, sizes[i])
-                    if members is not None:
-                        members[i] = members[i][row[:, 7].to(torch.int64)]
-                preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
-                                        boxes=row[:, :4].contiguous(), scores=row[:, 4].contiguous(),
-                                        labels=row[:, 5].to(torch.int64), source=row[:, 6].to(torch.int64) // k,
-                                        members=None if members is None else members[i], **tr))
-            t_pre += t_tile[0]
-            t_inf += t_tile[1]
-            t_post -= t_tile[0] + t_tile[1]  # what is left of t3 - t2 is postprocessing: every pass's and the merge
-        else:
-            cols = [boxes, scores[..., None], labels[..., None].to(boxes.dtype)]
-            if gpu_track:  # the tracker on the candidates where they stand; its id and box join the copy back
-                cols = [c[:n] for c in cols] + [track_launch(len(preds), boxes[:n], scores[:n], labels[:n],
-                                                             (scores[:n] >= conf).sum(1), lim[:n])]
-            packed = torch.cat(cols, -1).cpu()  # one copy back
-            n_done = len(preds)
-            for i in range(n):
-                row = packed[i]
-                keep = row[:, 4] >= conf  # postprocess_batched's rows are already best first
-                row, tr = row[keep], {}
-                if targs is not None:
-                    row, tr = tracked(n_done, i, row, sizes[i])
-                preds.append(Prediction(path=bt["paths"][i], size=tuple(sizes[i]), ctx=int(bt["ctx"][i]),
-                                        boxes=row[:, :4].contiguous(), scores=row[:, 4].contiguous(),
-                                        labels=row[:, 5].to(torch.int64), **tr))
-        t3 = time.perf_counter()
-        t_pre += t1 - t0 - t_cap
-        t_inf += t2 - t1
-        t_post += t3 - t2
-    if was_training:
-        model.train()
-    n_img = max(len(preds), 1)
-    speed = {"preprocess": 1e3 * t_pre / n_img, "inference": 1e3 * t_inf / n_img,
-             "postprocess": 1e3 * t_post / n_img}
-    if tiles is not None:
-        speed["passes"] = 1 + n_tiles
-    save_dir = Path(project) / name if project and name else None
-    if save_dir is not None:
-        save_dir.mkdir(parents=True, exist_ok=True)
-        if save_json:
-            (save_dir / "predictions.json").write_text(json.dumps(coco_results(preds)))
-        if targs is not None:
-            (save_dir / "tracks.json").write_text(json.dumps(track_results(preds)))
-            (save_dir / "mot").mkdir(exist_ok=True)
-            for key, text in mot_lines(preds).items():
-                (save_dir / "mot" / (key.replace("/", "_") + ".txt")).write_text(text)
-        if save_img:
-            for p in preds:
-                _save_overlay(p, save_dir / Path(p.path).name)
-    return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=ModelHandle(model))
-
-
-def track(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.1, tracker=None, **kw) -> PredictResults:
-    """``predict`` with tracking on: ``tracker`` a track.TrackArgs or a dict of
-    its fields (None: the defaults); ``conf`` defaults to the tracker's low
-    band, so that low-score rows can keep a track alive.  Every other argument
-    is predict's."""
-    return predict(weights, source, imgsz=imgsz, batch=batch, device=device, conf=conf,
-                   track=True if tracker is None else tracker, **kw)

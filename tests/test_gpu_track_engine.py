@@ -107,6 +107,23 @@ def test_track_on_the_gpu_as_on_the_host(hip_lib, tmp_path, monkeypatch, kw):
     for name, _ in LAYOUT:  # ids restart at 1 with every sequence
         ids = sorted({int(t) for p in runs["1"].predictions if p.sequence == name for t in p.track_ids})
         assert ids and ids[0] == 1, (name, ids)
+    if kw:
+        # a merge on the host leaves the candidates there: the tracker follows them to the reference, whatever
+        # MOE_PREDICT_TRACK says, and every field is the all-GPU run's
+        monkeypatch.setenv("MOE_PREDICT_MERGE", "0")
+        monkeypatch.setenv("MOE_PREDICT_TRACK", "1")
+        L.launch_counts(reset=True)
+        host = _run(tmp_path, track=tracker, **kw)
+        assert "track" not in L.launch_counts(reset=True)
+        assert len(host.predictions) == len(runs["1"].predictions)
+        for a, b in zip(runs["1"].predictions, host.predictions):
+            assert (a.path, a.size, a.ctx, a.sequence, a.frame) == (b.path, b.size, b.ctx, b.sequence, b.frame)
+            for f in ("boxes", "scores", "track_boxes"):
+                assert torch.equal(getattr(a, f).view(torch.int32), getattr(b, f).view(torch.int32)), (a.path, f)
+            for f in ("labels", "source", "track_ids"):
+                assert torch.equal(getattr(a, f), getattr(b, f)), (a.path, f)
+            assert (a.members is None and b.members is None) if a.members is None \
+                else torch.equal(a.members, b.members)
 
 
 def test_predict_without_track_is_unchanged(hip_lib, tmp_path):

@@ -143,7 +143,9 @@ def _two_sequences(root):
             Image.open(srcs[i]).convert("RGB").resize((256, 128), Image.BILINEAR).save(root / name / f"{f:03d}.png")
 
 
-def test_engine_track_on_the_cpu(tmp_path):
+@pytest.mark.parametrize("tiled", [dict(), dict(tiles=(2, 1)), dict(tiles=(2, 1), merge="fuse")],
+                         ids=["plain", "tiles", "fuse"])
+def test_engine_track_on_the_cpu(tmp_path, tiled):
     from src.rtdetr_moe import engine
 
     src = tmp_path / "frames"
@@ -151,9 +153,9 @@ def test_engine_track_on_the_cpu(tmp_path):
     _two_sequences(src)
     kw = dict(imgsz=IMGSZ, batch=2, device="cpu", conf=0.0, workers=0)
     torch.manual_seed(0)
-    plain = engine.predict(SPEC, src, **kw)
+    plain = engine.predict(SPEC, src, **kw, **tiled)
     torch.manual_seed(0)
-    res = engine.track(SPEC, src, tracker=TRACKER, project=str(tmp_path), name="run", **kw)
+    res = engine.track(SPEC, src, tracker=TRACKER, project=str(tmp_path), name="run", **kw, **tiled)
     assert all(p.track_ids is None and p.track_boxes is None and p.sequence is None for p in plain.predictions)
     assert [(p.sequence, p.frame) for p in res.predictions] == [("seqA", f) for f in (1, 2, 3, 4)] + \
         [("seqB", f) for f in (1, 2, 3)]
@@ -164,15 +166,26 @@ def test_engine_track_on_the_cpu(tmp_path):
         assert p.path == q.path and p.track_ids.dtype == torch.int64 and tuple(p.track_boxes.shape) == (n, 4)
         assert p.frame > 1 or n == 0  # min_hits 2: nothing reported in a sequence's first frame
         # the rows are a subset of predict's, in its order, with the same bits
-        rows = torch.cat([q.boxes, q.scores[:, None], q.labels[:, None].float()], 1).view(torch.int32).tolist()
-        pos = [rows.index(r) for r in
-               torch.cat([p.boxes, p.scores[:, None], p.labels[:, None].float()], 1).view(torch.int32).tolist()]
+        cols = [q.boxes, q.scores[:, None], q.labels[:, None].float()]
+        mine = [p.boxes, p.scores[:, None], p.labels[:, None].float()]
+        if tiled:
+            cols.append(q.source[:, None].float())
+            mine.append(p.source[:, None].float())
+        if tiled.get("merge") == "fuse":
+            cols.append(q.members[:, None].float())
+            mine.append(p.members[:, None].float())
+        rows = torch.cat(cols, 1).view(torch.int32).tolist()
+        pos = [rows.index(r) for r in torch.cat(mine, 1).view(torch.int32).tolist()]
         assert pos == sorted(pos) and len(set(pos)) == n
         w, h = p.size
         assert bool((p.track_boxes >= 0).all() and (p.track_boxes[:, [0, 2]] <= w).all()
                     and (p.track_boxes[:, [1, 3]] <= h).all())
         assert len(set(p.track_ids.tolist())) == n and bool((p.track_ids >= 1).all())
     assert total >= 6
+    if tiled:  # the full frame and both tiles have rows among the reported ones
+        assert {int(v) for p in res.predictions for v in p.source} == {0, 1, 2}
+    if tiled.get("merge") == "fuse":
+        assert any(bool((p.members > 1).any()) for p in res.predictions)
     # ids restart at 1 per sequence
     for name in ("seqA", "seqB"):
         ids = sorted({int(t) for p in res.predictions if p.sequence == name for t in p.track_ids})
