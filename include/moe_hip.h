@@ -922,7 +922,7 @@ int rtdetr_box_fuse(const float* boxes, const float* scores, const int32_t* labe
  *   trk_meta  int32 [S][T][4]  label, id, age, hits; hits 0: the slot is free, all of it zero (16-byte aligned)
  *   seq_meta  int32 [S][2]     next_id (a new sequence starts at 1), dropped
  * The rule per frame, fp32, every operation rounded on its own, no FMA:
- *   1. every live slot: box = box + vel.
+ *   1. every live slot: box = box + vel (rtdetr_track_update_shift: plus the frame's shift).
  *   2. row d takes part if d < n_valid, its score is finite and >= track_low;
  *      it is high if score >= track_high, else low.
  *   3. iou = inter / ((area_t + area_d) - inter) if that denominator is > 0,
@@ -954,6 +954,62 @@ int rtdetr_track_update(const float* boxes, const float* scores, const int32_t* 
                         int max_age, int min_hits, float alpha, float beta, int class_agnostic, float* trk_box,
                         float* trk_score, int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes,
                         int32_t* count, hipStream_t stream);
+
+/* rtdetr_track_update with camera-motion compensation: frame_shift fp32 [F][2]
+ * (sx, sy in the boxes' pixels, e.g. rtdetr_frame_shift's output scaled to the
+ * source frame) or NULL.  Step 1 becomes box = (box + vel) + (sx, sy, sx, sy)
+ * of the frame, for every live slot, coasting ones included, each operation
+ * rounded on its own; vel is untouched, so the filter learns the residual
+ * motion.  NULL adds nothing (it does not add zero: -0.0 + 0.0 is +0.0) and is
+ * rtdetr_track_update bit for bit, which forwards here with NULL.  Everything
+ * else -- operands, limits, refusals, the profiler kind -- as above. */
+int rtdetr_track_update_shift(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                              const int32_t* frame_slot, const int32_t* frame_reset, int F, int K, int S, int T,
+                              float track_high, float track_low, float new_thr, float match_iou, float second_iou,
+                              int max_age, int min_hits, float alpha, float beta, int class_agnostic, float* trk_box,
+                              float* trk_score, int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id,
+                              float* out_boxes, int32_t* count, const float* frame_shift, hipStream_t stream);
+
+/* Camera-motion compensation for the tracker (TrackArgs.cmc): the global shift
+ * of each frame against its predecessor, motion.sequence_shifts on the host bit
+ * for bit (the rule: src/rtdetr_moe/motion.py).  It measures on the model's
+ * input of the full-frame pass.  Three launches per batch whatever F is: grey +
+ * coarse images; the coarse search (a workgroup per frame and band of 8 window
+ * rows, a thread per shift, the band and its halo in LDS, v_sad_u8); the fine
+ * search (a workgroup per frame and band, a thread per four pixels, 25 sums;
+ * the frame's last band to arrive picks the winner).  Integer atomics only.
+ * Inputs: images fp32 [F][pad_h][pad_w][3] channels-last as rtdetr_resize_pad_u8
+ * writes it, the content out_h x out_w top-left; frame_slot / frame_reset int32
+ * [F], the tracker's tables: frame f's predecessor is the nearest earlier frame
+ * of the launch with the same slot, or else the slot's stored image if
+ * prev_valid says it has one; frame_reset[f] != 0: no predecessor.  radius in
+ * input pixels, a multiple of 4 in [4, 64]; gate_permille in [0, 999]; r0, r1:
+ * the coarse rows [r0, r1) the windows may use (clamped to [0, out_h / 4]).
+ * State, owned by the caller (motion.MotionState), updated in place: after the
+ * launch a slot holds its last frame of the launch.  A slot without frames is
+ * untouched, as is everything for a frame whose slot is outside [0, S).
+ *   prev_grey   uint8 [S][out_h][out_w]          (4-byte aligned)
+ *   prev_coarse uint8 [S][out_h / 4][out_w / 4]
+ *   prev_valid  int32 [S]
+ * Workspace, contents meaningless between launches: work_grey uint8
+ * [work_images][out_h][out_w] (4-byte aligned), work_coarse uint8 [work_images]
+ * [out_h / 4][out_w / 4], sums int32 [work_images - S][1121]; work_images >=
+ * F + S.
+ * Outputs, every element written: out_shift int32 [F][2] (dx, dy in input
+ * pixels; content that moved right by dx gives +dx); out_info int32 [F][4]:
+ * status (0 no estimate: no predecessor or a window under 8 x 8; 1 estimated;
+ * 2 gated), SAD(0, 0), the coarse winner's SAD, the fine winner's SAD, zeros
+ * where a stage did not run.
+ * Limits: out_h, out_w <= 2048 and out_h * out_w <= 2^22 (every SAD fits int32:
+ * 255 * 2^22 < 2^31), F <= 1024, S <= 1024; at most 37.5 KiB of LDS.  A bad
+ * argument (NULL operands, radius, gate, out > pad, sizes above the limits,
+ * S == 0 with frames, a workspace under F + S images) returns non-zero before
+ * any launch.  F == 0 returns 0 without a launch. */
+int rtdetr_frame_shift(const float* images, int F, int out_h, int out_w, int pad_h, int pad_w,
+                       const int32_t* frame_slot, const int32_t* frame_reset, int S, int radius, int gate_permille,
+                       int r0, int r1, uint8_t* prev_grey, uint8_t* prev_coarse, int32_t* prev_valid,
+                       uint8_t* work_grey, uint8_t* work_coarse, int32_t* sums, int work_images, int32_t* out_shift,
+                       int32_t* out_info, hipStream_t stream);
 
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
@@ -1301,7 +1357,7 @@ int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t*
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
  * context-bias gradients, 15 training batch augmentation, 16 validation
  * matching, 17 routing statistics, 18 inference preprocessing (resize),
- * 19 tiled prediction's merge, 20 tracking.
+ * 19 tiled prediction's merge, 20 tracking, 21 camera-motion estimation.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1325,7 +1381,8 @@ enum moe_prof_kind {
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
   MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
-  MOE_PROF_TRACK = 20      /* tracking: a sequence's detections linked across frames (rtdetr_track_update) */
+  MOE_PROF_TRACK = 20,     /* tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift]) */
+  MOE_PROF_MOTION = 21     /* tracking: a frame's global shift against its predecessor (rtdetr_frame_shift) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

@@ -10,7 +10,9 @@
 // last.  A slot without frames touches nothing.  The frames of a slot outside
 // [0, S) get empty outputs from workgroup f % S.  Per frame:
 //   1. The rows go into LDS (box, score, label, and rstate: kRowOut / kRowLow /
-//      kRowHigh, later the slot that took the row); every live track predicts.
+//      kRowHigh, later the slot that took the row); every live track predicts:
+//      box = box + vel and, with a frame_shift table (rtdetr_track_update_shift:
+//      camera-motion compensation), box = (box + vel) + the frame's shift.
 //   2. Association, stage 1 (live tracks x high rows, match_iou), then stage 2
 //      (tracks still unmatched with age 0 and hits >= min_hits x low rows,
 //      second_iou).  Every track scans the stage's free rows (an LDS broadcast
@@ -115,7 +117,8 @@ __device__ __forceinline__ int trk_block_rank(bool flag, int32_t* wcnt, int lane
 __global__ __launch_bounds__(256) void track_update_kernel(
     const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
-    const int32_t* __restrict__ frame_reset, int F, int K, int S, int T, TrkParams p, float* __restrict__ trk_box,
+    const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
+    TrkParams p, float* __restrict__ trk_box,
     float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
     int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -202,6 +205,10 @@ __global__ __launch_bounds__(256) void track_update_kernel(
       if (m.w > 0) {
         const float4 v = tvel[tid];
         tb = make_float4(tb.x + v.x, tb.y + v.y, tb.z + v.z, tb.w + v.w);
+        if (frame_shift != nullptr) {  // NULL adds nothing: -0.0 + 0.0 would be +0.0
+          const float sx = frame_shift[2 * f], sy = frame_shift[2 * f + 1];
+          tb = make_float4(tb.x + sx, tb.y + sy, tb.z + sx, tb.w + sy);
+        }
       }
     }
     if (tid == 0) ctl[2] = 0;
@@ -349,14 +356,12 @@ __global__ __launch_bounds__(256) void track_update_kernel(
 
 using namespace moe;
 
-extern "C" int rtdetr_track_update(const float* boxes, const float* scores, const int32_t* labels,
-                                   const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
-                                   int F, int K, int S, int T, float track_high, float track_low, float new_thr,
-                                   float match_iou, float second_iou, int max_age, int min_hits, float alpha,
-                                   float beta, int class_agnostic, float* trk_box, float* trk_score,
-                                   int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes,
-                                   int32_t* count, hipStream_t stream) {
-  const std::string what = "rtdetr_track_update";
+static int track_update(const std::string& what, const float* boxes, const float* scores, const int32_t* labels,
+                        const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
+                        const float* frame_shift, int F, int K, int S, int T, float track_high, float track_low,
+                        float new_thr, float match_iou, float second_iou, int max_age, int min_hits, float alpha,
+                        float beta, int class_agnostic, float* trk_box, float* trk_score, int32_t* trk_meta,
+                        int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* count, hipStream_t stream) {
   if (F < 0 || K < 0 || S < 0 || F > kTrkMaxF || K > kTrkMaxK || S > kTrkMaxS || T < 1 || T > kTrkMaxT)
     return fail(what + ": need 0 <= F <= 1024, 0 <= K <= 1024, 0 <= S <= 1024, 1 <= T <= 256");
   if (track_high != track_high || track_low != track_low || new_thr != new_thr || match_iou != match_iou ||
@@ -388,8 +393,36 @@ extern "C" int rtdetr_track_update(const float* boxes, const float* scores, cons
   p.min_hits = min_hits;
   p.class_agnostic = class_agnostic != 0 ? 1 : 0;
   ProfScope prof(stream, PROF_TRACK,
-                 (double)F * (K * 44.0 + (n_valid ? 4.0 : 0.0) + 12.0) + (double)S * (T * 104.0 + 16.0));
+                 (double)F * (K * 44.0 + (n_valid ? 4.0 : 0.0) + (frame_shift ? 8.0 : 0.0) + 12.0) +
+                     (double)S * (T * 104.0 + 16.0));
   MOE_LAUNCH(prof, track_update_kernel, dim3(S), dim3(threads), shmem, stream, boxes, scores, labels, n_valid,
-             frame_slot, frame_reset, F, K, S, T, p, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes, count);
-  return check_launch("rtdetr_track_update");
+             frame_slot, frame_reset, frame_shift, F, K, S, T, p, trk_box, trk_score, trk_meta, seq_meta, out_id,
+             out_boxes, count);
+  return check_launch(what.c_str());
+}
+
+extern "C" int rtdetr_track_update(const float* boxes, const float* scores, const int32_t* labels,
+                                   const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
+                                   int F, int K, int S, int T, float track_high, float track_low, float new_thr,
+                                   float match_iou, float second_iou, int max_age, int min_hits, float alpha,
+                                   float beta, int class_agnostic, float* trk_box, float* trk_score,
+                                   int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes,
+                                   int32_t* count, hipStream_t stream) {
+  return track_update("rtdetr_track_update", boxes, scores, labels, n_valid, frame_slot, frame_reset, nullptr, F, K,
+                      S, T, track_high, track_low, new_thr, match_iou, second_iou, max_age, min_hits, alpha, beta,
+                      class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes, count, stream);
+}
+
+extern "C" int rtdetr_track_update_shift(const float* boxes, const float* scores, const int32_t* labels,
+                                         const int32_t* n_valid, const int32_t* frame_slot,
+                                         const int32_t* frame_reset, int F, int K, int S, int T, float track_high,
+                                         float track_low, float new_thr, float match_iou, float second_iou,
+                                         int max_age, int min_hits, float alpha, float beta, int class_agnostic,
+                                         float* trk_box, float* trk_score, int32_t* trk_meta, int32_t* seq_meta,
+                                         int32_t* out_id, float* out_boxes, int32_t* count, const float* frame_shift,
+                                         hipStream_t stream) {
+  return track_update("rtdetr_track_update_shift", boxes, scores, labels, n_valid, frame_slot, frame_reset,
+                      frame_shift, F, K, S, T, track_high, track_low, new_thr, match_iou, second_iou, max_age,
+                      min_hits, alpha, beta, class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes,
+                      count, stream);
 }

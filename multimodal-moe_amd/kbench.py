@@ -14,6 +14,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
   python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
   python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
+  python multimodal-moe_amd/kbench.py --frame-shift the camera-motion estimator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -855,6 +856,113 @@ def track_leg(reps, rounds):
     print(json.dumps(line), flush=True)
 
 
+def frame_shift_leg(reps, rounds):
+    """rtdetr_frame_shift at predict's shape (F 16 frames of one sequence, 704 x
+    1248, the defaults of track.TrackArgs: radius 48, gate 0.1) against
+    motion.sequence_shifts on the host, same process, same frames (shifts, SADs
+    and state checked equal first).  The frames are views of a scene of 8 x 8
+    blocks plus noise, panning by up to 45 px a frame; the checked launch starts
+    from the state 16 earlier frames leave, a timed one from the state the
+    batch itself left (its first frame then measures against its last, the
+    other 15 as checked).  kernel_us: the three
+    launches' dispatch-stamped execution time per batch, and each launch's
+    (grey, coarse, fine); host_ms: sequence_shifts on the 16 frames already on
+    the host (the copy back of the model's input is not in it), wall clock.
+    forward_replay_us: one EvalForward graph replay at batch 16
+    (rtdetr-r50-moe8-top2, 704 x 1248).  Median, min and max over the rounds,
+    the sides interleaved in each round."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import engine, motion
+    from src.rtdetr_moe.model import RTDETRMoE
+    from src.rtdetr_moe.track import TrackArgs
+
+    F, h, w, m = 16, 704, 1248, 64
+    args = TrackArgs()
+    rng = np.random.default_rng(0)
+    small = rng.random(((h + 2 * m) // 8 + 1, (w + 2 * m) // 8 + 1, 3)).astype(np.float32)
+    scene = np.repeat(np.repeat(small, 8, 0), 8, 1)
+    steps = rng.integers(-45, 46, (2 * F, 2))
+    steps[::5] = 0
+    pos = np.clip(np.cumsum(steps, 0), -m, m)  # the views stay inside the scene
+    frames = np.stack([scene[m - y:m - y + h, m - x:m - x + w] + rng.normal(0, 0.02, (h, w, 3)).astype(np.float32)
+                       for x, y in pos]).astype(np.float32)
+    gate = round(1000 * args.cmc_gate)
+    ref = motion.new_motion_state(1, h, w)
+    zeros = np.zeros(F, np.int32)
+    motion.sequence_shifts(frames[:F], zeros, zeros, ref, args.cmc_radius, gate, args.cmc_rows)
+    warm = {k: v.copy() for k, v in ref.items()}
+    want = motion.sequence_shifts(frames[F:], zeros, zeros, ref, args.cmc_radius, gate, args.cmc_rows)
+    true = np.diff(pos, axis=0)[F - 1:]
+    state = motion.MotionState(1, h, w, "cuda", frames=F)
+    up = lambda a: torch.from_numpy(a).cuda().permute(0, 3, 1, 2)  # noqa: E731
+    tab = torch.zeros(F, dtype=torch.int32, device="cuda")
+    x = up(frames[F:])
+    L.frame_shift(state, up(frames[:F]), (h, w), tab, tab, args.cmc_radius, args.cmc_gate, args.cmc_rows)
+    got = L.frame_shift(state, x, (h, w), tab, tab, args.cmc_radius, args.cmc_gate, args.cmc_rows)
+    exp = state.export()
+    if not (np.array_equal(got[0].cpu().numpy(), want[0]) and np.array_equal(got[1].cpu().numpy(), want[1])
+            and np.array_equal(exp["grey"], ref["grey"]) and np.array_equal(exp["valid"], ref["valid"])):
+        raise SystemExit("frame_shift differs from sequence_shifts")
+    def kernel():  # the state after it is the same every time: the slot's image is the batch's last frame
+        return L.frame_shift(state, x, (h, w), tab, tab, args.cmc_radius, args.cmc_gate, args.cmc_rows)
+
+    def parts(n):
+        kernel()
+        torch.cuda.synchronize()
+        L.lib().moe_profile_enable(1)
+        try:
+            for _ in range(n):
+                kernel()
+            ms = [r[1] for r in L.profile_records()]
+        finally:
+            L.lib().moe_profile_enable(0)
+        return [1e3 * statistics.median(ms[i::3]) for i in range(3)]
+
+    def host_ms():
+        st = {k: v.copy() for k, v in warm.items()}
+        t0 = time.perf_counter()
+        motion.sequence_shifts(frames[F:], zeros, zeros, st, args.cmc_radius, gate, args.cmc_rows)
+        return 1e3 * (time.perf_counter() - t0)
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    xin = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(xin, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(xin, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    res = {"kernel_us": [], "grey_us": [], "coarse_us": [], "fine_us": [], "host_ms": [], "forward_replay_us": []}
+    for _ in range(rounds):
+        res["kernel_us"].append(timed(kernel, reps))
+        for k, v in zip(("grey_us", "coarse_us", "fine_us"), parts(reps)):
+            res[k].append(v)
+        res["host_ms"].append(host_ms())
+        res["forward_replay_us"].append(replay_us())
+    line = {"kernel": "rtdetr_frame_shift", "shape": f"F{F} {h}x{w} S1 radius{args.cmc_radius} gate{gate}",
+            "status": want[1][:, 0].tolist(), "shifts_found": int((want[0] == true).all(1).sum())}
+    for k, v in res.items():
+        line[k] = round(statistics.median(v), 3)
+        line[k + "_min"] = round(min(v), 3)
+        line[k + "_max"] = round(max(v), 3)
+    line["host_over_kernel"] = round(1e3 * line["host_ms"] / line["kernel_us"], 1)
+    line["kernel_share_of_forward"] = round(line["kernel_us"] / line["forward_replay_us"], 4)
+    print(json.dumps(line), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -918,6 +1026,9 @@ def main():
     ap.add_argument("--track", action="store_true",
                     help="time rtdetr_track_update (16 frames of one sequence, K 300, about 40 live tracks) against "
                          "track_reference on the host and one forward replay, and exit")
+    ap.add_argument("--frame-shift", action="store_true",
+                    help="check rtdetr_frame_shift against motion.sequence_shifts, then time it against the host and "
+                         "a forward replay, and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -963,6 +1074,9 @@ def main():
         return
     if a.box_fuse:
         box_fuse_leg(a.reps, a.rounds)
+        return
+    if a.frame_shift:
+        frame_shift_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

@@ -52,10 +52,41 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="link the detections across the frames of a sequence (one directory): tracks.json, mot/*.txt")
     ap.add_argument("--tracker", type=str, default=None,
                     help="--track: JSON of track.TrackArgs fields, e.g. '{\"max_age\": 15}' (default: ByteTrack's)")
+    ap.add_argument("--cmc", action="store_true",
+                    help="--track: camera-motion compensation, the tracks move by each frame's global shift "
+                         "(camera_motion.json)")
+    ap.add_argument("--cmc-radius", type=int, default=None,
+                    help="--cmc: search radius in pixels of the model's input, a multiple of 4 in [4, 64] (default 48)")
+    ap.add_argument("--cmc-gate", type=float, default=None,
+                    help="--cmc: a non-zero shift must beat no shift by this share (default 0.1)")
+    ap.add_argument("--cmc-rows", type=str, default=None,
+                    help="--cmc: T,B the fractions of the height the estimator looks at, e.g. 0,0.8 to leave the "
+                         "bonnet out (default 0,1)")
     a = ap.parse_args(argv)
     if a.tracker is not None and not a.track:
         ap.error("--tracker needs --track")
+    given = a.cmc_radius is not None or a.cmc_gate is not None or a.cmc_rows is not None
+    if (a.cmc or given) and not a.track:
+        ap.error("--cmc needs --track")
+    if given and not a.cmc:
+        ap.error("--cmc-radius, --cmc-gate and --cmc-rows need --cmc")
     return a
+
+
+def tracker_args(a):
+    """engine.predict's ``track`` from the command line: --tracker's JSON, the --cmc options over it."""
+    if not a.track:
+        return None
+    t = json.loads(a.tracker) if a.tracker else {}
+    if a.cmc:
+        t["cmc"] = True
+        if a.cmc_radius is not None:
+            t["cmc_radius"] = a.cmc_radius
+        if a.cmc_gate is not None:
+            t["cmc_gate"] = a.cmc_gate
+        if a.cmc_rows is not None:
+            t["cmc_rows"] = tuple(float(v) for v in a.cmc_rows.split(","))
+    return t or True
 
 
 def main(argv=None) -> None:
@@ -67,13 +98,15 @@ def main(argv=None) -> None:
                          name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
                          tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
                          class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou,
-                         track=(json.loads(a.tracker) if a.tracker else True) if a.track else None)
+                         track=tracker_args(a))
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
     if a.track:
         ids = {(p.sequence, int(t)) for p in res.predictions for t in p.track_ids}
         print(f"{len(ids)} tracks in {len({p.sequence for p in res.predictions})} sequences")
         print(f"Saved tracks -> {res.save_dir / 'tracks.json'}, {res.save_dir / 'mot'}")
+        if a.cmc:
+            print(f"Saved camera shifts -> {res.save_dir / 'camera_motion.json'}")
     print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))
     print(f"Saved predictions -> {res.save_dir / 'predictions.json'}")
 

@@ -4,6 +4,8 @@ checkpoint (or a bare architecture spec): scripts/predict_detector.py with
 is the images of one directory, in the source's order.  Writes predictions.json,
 tracks.json (the COCO rows plus track_id and sequence) and mot/<sequence>.txt
 (frame,id,x,y,w,h,score,-1,-1,-1) under RUNS_DIR/rtdetr/<run-name>_predict.
+--cmc (with --cmc-radius, --cmc-gate, --cmc-rows T,B) turns on camera-motion
+compensation and adds camera_motion.json.
 """
 from __future__ import annotations
 

@@ -122,6 +122,10 @@ SIGNATURES = {
     "rtdetr_box_fuse": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "rtdetr_track_update": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _F, _F, _I, _P, _P, _P,
                                  _P, _P, _P, _P, _P]),
+    "rtdetr_track_update_shift": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _F, _F, _I,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rtdetr_frame_shift": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P,
+                                _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -215,7 +219,7 @@ def lib() -> ctypes.CDLL:
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
               11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
-              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge", 20: "track"}
+              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge", 20: "track", 21: "motion"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -1081,12 +1085,14 @@ def box_fuse(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=30
 TRACK_MAX_K, TRACK_MAX_T, TRACK_MAX_F, TRACK_MAX_S = 1024, 256, 1024, 1024  # rtdetr_track_update's limits
 
 
-def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, args, out=None):
+def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, args, out=None, shift=None):
     """The tracker, one launch for the batch (rtdetr_track_update:
     track.track_reference per frame, bit for bit).  ``state``: a
     track.TrackState (S state slots of T tracks, updated in place); boxes fp32
     [F, K, 4] xyxy, scores fp32 [F, K], labels int32 [F, K], n_valid int32 [F] or
     None (= K), frame_slot / frame_reset int32 [F]; ``args``: a track.TrackArgs.
+    ``shift``: fp32 [F, 2], every frame's camera shift in the boxes' pixels
+    (rtdetr_track_update_shift: the predicted boxes move by it), or None.
     -> (out_id int32 [F, K], out_boxes fp32 [F, K, 4], count int32 [F]), every
     element written.  ``out``: that tuple of tensors to write into instead of
     new ones."""
@@ -1128,15 +1134,75 @@ def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset,
                 raise MoEKernelError(f"track_update: {name} must be {s}, got {tuple(t.shape)}")
     tensors = [boxes, scores, labels, frame_slot, frame_reset, *state.tensors(), *out]
     tensors += [n_valid] if n_valid is not None else []
+    if shift is not None:
+        _need(shift, torch.float32, "shift")
+        if tuple(shift.shape) != (F, 2):
+            raise MoEKernelError("track_update: shift must be [F, 2]")
+        tensors.append(shift)
     if any(t.device != dev for t in tensors):
         raise MoEKernelError("track_update: all tensors must be on one device")
     a = args
-    rc = lib().rtdetr_track_update(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), _ptr(frame_slot),
-                                   _ptr(frame_reset), F, K, S, T, float(a.track_high), float(a.track_low),
-                                   float(a.new_thr), float(a.match_iou), float(a.second_iou), int(a.max_age),
-                                   int(a.min_hits), float(a.alpha), float(a.beta), int(bool(a.class_agnostic)),
-                                   *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out), _stream())
-    _check(rc, "rtdetr_track_update")
+    common = (_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), _ptr(frame_slot), _ptr(frame_reset), F, K, S, T,
+              float(a.track_high), float(a.track_low), float(a.new_thr), float(a.match_iou), float(a.second_iou),
+              int(a.max_age), int(a.min_hits), float(a.alpha), float(a.beta), int(bool(a.class_agnostic)),
+              *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out))
+    if shift is None:
+        _check(lib().rtdetr_track_update(*common, _stream()), "rtdetr_track_update")
+    else:
+        _check(lib().rtdetr_track_update_shift(*common, _ptr(shift), _stream()), "rtdetr_track_update_shift")
+    return out
+
+
+def frame_shift(state, images, out_hw, frame_slot, frame_reset, radius=48, gate=0.1, rows=(0.0, 1.0), out=None):
+    """Every frame's global shift against its predecessor, three launches for the
+    batch (rtdetr_frame_shift: motion.sequence_shifts bit for bit).  ``state``:
+    a motion.MotionState of the content size ``out_hw`` (updated in place);
+    ``images``: the model's input, fp32 channels-last [F, 3, pad_h, pad_w] as
+    resize_pad returns it; frame_slot / frame_reset int32 [F], the tracker's
+    tables; ``radius`` in input pixels, ``gate`` a share in [0, 0.999],
+    ``rows`` the fractions of the height the windows may use.  -> (shift int32
+    [F, 2] in input pixels, info int32 [F, 4]: status, SAD(0, 0), the coarse
+    and the fine winner's SAD), every element written.  ``out``: that pair of
+    tensors to write into instead of new ones."""
+    from ..rtdetr_moe import motion
+
+    if not (images.is_cuda and images.dtype == torch.float32 and images.dim() == 4 and images.shape[1] == 3
+            and images.permute(0, 2, 3, 1).is_contiguous()):
+        raise MoEKernelError("frame_shift: images must be a channels-last fp32 GPU tensor [F, 3, pad_h, pad_w]")
+    _need(frame_slot, torch.int32, "frame_slot")
+    _need(frame_reset, torch.int32, "frame_reset")
+    F, _, ph, pw = (int(v) for v in images.shape)
+    oh, ow = (int(v) for v in out_hw)
+    if (oh, ow) != (state.out_h, state.out_w):
+        raise MoEKernelError(f"frame_shift: the state is for {state.out_h} x {state.out_w}, got out_hw {oh} x {ow}")
+    if tuple(frame_slot.shape) != (F,) or tuple(frame_reset.shape) != (F,):
+        raise MoEKernelError("frame_shift: frame_slot / frame_reset must be [F]")
+    try:
+        radius, permille = motion.check_search(radius, gate)
+        r0, r1 = motion.coarse_rows(rows, oh)
+    except ValueError as e:
+        raise MoEKernelError(f"frame_shift: {e}") from None
+    if F > motion.MOTION_MAX_F:
+        raise MoEKernelError(f"frame_shift: at most {motion.MOTION_MAX_F} frames a launch, got {F}")
+    state.reserve(F)
+    dev = images.device
+    shapes, names = ((F, 2), (F, 4)), ("out_shift", "out_info")
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.int32, device=dev) for s in shapes)
+    else:
+        if len(out) != 2:
+            raise MoEKernelError("frame_shift: out must be (shift, info)")
+        for t, s, name in zip(out, shapes, names):
+            _need(t, torch.int32, name)
+            if tuple(t.shape) != s:
+                raise MoEKernelError(f"frame_shift: {name} must be {s}, got {tuple(t.shape)}")
+    st = (state.prev_grey, state.prev_coarse, state.prev_valid, state.work_grey, state.work_coarse, state.sums)
+    if any(t.device != dev for t in (frame_slot, frame_reset, *st, *out)):
+        raise MoEKernelError("frame_shift: all tensors must be on one device")
+    rc = lib().rtdetr_frame_shift(_ptr(images), F, oh, ow, ph, pw, _ptr(frame_slot), _ptr(frame_reset), state.S, radius,
+                                  permille, r0, r1, *(_ptr(t) for t in st), state.frames + state.S, _ptr(out[0]),
+                                  _ptr(out[1]), _stream())
+    _check(rc, "rtdetr_frame_shift")
     return out
 
 

@@ -35,7 +35,8 @@ from .data import CocoDataset, SyntheticZOD, YoloDataset, collate
 from .metrics import BoxMetrics, DetectionEvaluator, DeviceDetectionEvaluator, gt_xyxy_pixels, named_bands
 from .model import RTDETRMoE
 # prediction on image files lives in predictor.py; its names stay reachable as engine.predict, engine.Prediction, ...
-from .predictor import (Prediction, PredictResults, coco_results, default_sequence_of, frame_sequences,  # noqa: F401
+from .predictor import (Prediction, PredictResults, camera_motion, coco_results, default_sequence_of,  # noqa: F401
+                        frame_sequences,
                         mot_lines, predict, predict_merge_on_gpu, predict_resize_on_gpu, predict_track_on_gpu, track,
                         track_results)
 from .schedule import accumulate_count, schedule_at, warmup_iters

@@ -28,6 +28,7 @@ from ..moe import _lib
 from ..moe.context import MISSING_ID
 from .merge import (FUSE_MAX_DET, FUSE_MAX_N, FUSE_MAX_P, MERGE_MAX_DET, MERGE_MAX_N, METRICS, fuse_reference,
                     merge_reference, parse_tiles, tile_windows)
+from .motion import MotionState, new_motion_state, sequence_shifts
 from .preprocess import mapped_sizes
 from .track import TRACK_MAX_K, TrackArgs, TrackState, new_state, track_reference
 
@@ -58,6 +59,10 @@ class Prediction:
     track_boxes: torch.Tensor | None = None
     sequence: str | None = None
     frame: int | None = None
+    # track with cmc: the frame's camera shift (dx, dy) against its predecessor in source pixels, fp32 values, and
+    # the estimator's status (motion.py: 0 no estimate -- a sequence's first frame --, 1 estimated, 2 gated)
+    camera_shift: tuple | None = None
+    camera_status: int | None = None
 
 
 @dataclass
@@ -109,6 +114,14 @@ def mot_lines(predictions) -> dict:
         for t, (x1, y1, x2, y2), s in zip(p.track_ids.tolist(), p.track_boxes.tolist(), p.scores.tolist()):
             lines.append(f"{p.frame},{int(t)},{x1:.3f},{y1:.3f},{x2 - x1:.3f},{y2 - y1:.3f},{s:.5f},-1,-1,-1")
     return {k: "".join(line + "\n" for line in v) for k, v in out.items()}
+
+
+def camera_motion(predictions) -> dict:
+    """{sequence: [[frame, dx, dy, status], ...]} of a run tracked with cmc (camera_motion.json)."""
+    out = {}
+    for p in predictions:
+        out.setdefault(p.sequence, []).append([p.frame, p.camera_shift[0], p.camera_shift[1], p.camera_status])
+    return out
 
 
 def _save_overlay(pred: Prediction, out_path: Path):
@@ -173,9 +186,12 @@ def frame_sequences(paths, sequence_of=None) -> list:
 # A frame's rows on the host, fp32 [m, C], best first: the box, the score, the label; with tiles CAND, the row's
 # number among the frame's candidates (pass * k + row; the device merge marks the rows past the kept ones < 0);
 # with merge="fuse" MEMBERS; and, where the tracker ran on the device, its TRACK_COLS columns last: TRACK_ID, the
-# id's int32 bits, then TRACK_BOX, the track's box.  Columns that a run does not have are not there: no padding.
+# id's int32 bits, then TRACK_BOX, the track's box; with cmc the frame's CMC_COLS columns stand before those, the
+# same in every row: the camera shift in source pixels and the estimator's status.  Columns that a run does not have
+# are not there: no padding.
 BOX, SCORE, LABEL, CAND, MEMBERS = slice(0, 4), 4, 5, 6, 7
 TRACK_COLS, TRACK_ID, TRACK_BOX = 5, -5, slice(-4, None)
+CMC_COLS, CMC = 3, slice(-8, -5)
 
 
 def _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track):
@@ -232,9 +248,9 @@ def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False):
     one upload; the tile passes take the device's copy), the first call captures the graph (untimed), and the boxes
     are clipped without the shift by the origin (adding a zero origin would turn a -0.0 into +0.0).  -> a namespace:
     boxes [S, k, 4] in source pixels, scores, labels [S, k] and lim [S, 4], the clipping limits, of all S slots, the
-    m real ones first; src on the device; the clock at t_ready, the input standing on the device, and at t_done,
-    after the forward, and t_cap, the capture's seconds before t_ready.  ``run``: the run's model, fwd (its
-    EvalForward), dev, batch, max_det, out_hw and pad_hw."""
+    m real ones first; src, and images, the model's input, on the device; the clock at t_ready, the input standing on
+    the device, and at t_done, after the forward, and t_cap, the capture's seconds before t_ready.  ``run``: the
+    run's model, fwd (its EvalForward), dev, batch, max_det, out_hw and pad_hw."""
     on_gpu = run.dev.type == "cuda"
     slots = run.batch if on_gpu else len(windows)
     fill = slots - len(windows)
@@ -268,7 +284,7 @@ def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False):
         lo = torch.tensor([[x0, y0, x0, y0] for x0, y0, _, _ in windows] + [[0.0] * 4] * fill, dtype=boxes.dtype,
                           device=boxes.device)
         boxes = torch.minimum(torch.maximum(boxes + lo[:, None, :], lo[:, None, :]), lim[:, None, :])
-    return SimpleNamespace(boxes=boxes, scores=scores, labels=labels, lim=lim, src=src, t_cap=t_cap,
+    return SimpleNamespace(boxes=boxes, scores=scores, labels=labels, lim=lim, src=src, images=images, t_cap=t_cap,
                            t_ready=t_ready, t_done=t_done)
 
 
@@ -308,13 +324,14 @@ def _pass_windows(sizes, windows):
                          for (fw, fh), wins in zip(sizes, windows)], dtype=torch.float32)
 
 
-def _merge_rows(cb, cs, cl, rule, fuse_iou, win, on_device, track_block=None) -> list:
+def _merge_rows(cb, cs, cl, rule, fuse_iou, win, on_device, track_block=None, heads=None) -> list:
     """The merge of a batch's candidates [n, N, ...] (the full frame's k rows, then each tile's) -> the frames' kept
     rows on the host: BOX, SCORE, LABEL, CAND and, fused, MEMBERS.  ``rule``: (conf, merge_iou, merge_metric,
     max_det, class_agnostic); ``win`` fp32 [n, P, 4], the passes' windows: fuse with ``fuse_iou`` (None: NMS).
     ``on_device``: ONE launch (rtdetr_nms_merge / rtdetr_box_fuse) and one packed copy back, which
-    ``track_block(boxes, scores, labels, counts)``'s TRACK_COLS columns join; else one copy of the candidates and
-    merge_reference / fuse_reference per frame."""
+    ``track_block(boxes, scores, labels, counts)``'s columns join (``heads``: a list that takes every frame's first
+    row as copied back, kept or not -- the frame's CMC columns); else one copy of the candidates and merge_reference
+    / fuse_reference per frame."""
     n = cb.shape[0]
     if on_device:
         if win is None:
@@ -328,6 +345,8 @@ def _merge_rows(cb, cs, cl, rule, fuse_iou, win, on_device, track_block=None) ->
         if track_block is not None:
             cols.append(track_block(ob, osc, ol, ocnt))
         packed = torch.cat(cols, -1).cpu()  # one copy back; CAND < 0 marks the rows past the kept ones
+        if heads is not None:
+            heads.extend(packed[:, 0])
         return [packed[i][packed[i][:, CAND] >= 0] for i in range(n)]
     packed = torch.cat([cb, cs[..., None], cl[..., None].to(cb.dtype)], -1).cpu()
     rows = []
@@ -345,64 +364,116 @@ def _merge_rows(cb, cs, cl, rule, fuse_iou, win, on_device, track_block=None) ->
     return rows
 
 
-def _untiled_rows(full, n, conf, track_block=None) -> list:
+def _untiled_rows(full, n, conf, track_block=None, heads=None) -> list:
     """Without tiles: the full-frame pass's rows (``full``: _detect's; its first n slots are frames) in one copy
     back -> per frame those with score >= conf (a prefix: they are best first already): BOX, SCORE, LABEL.
     ``track_block`` as in _merge_rows: the tracker on the frames' candidates where they stand, the valid rows
-    counted on the device; the copy is then of the n frames only."""
+    counted on the device; the copy is then of the n frames only.  ``heads`` as in _merge_rows."""
     cols = [full.boxes, full.scores[..., None], full.labels[..., None].to(full.boxes.dtype)]
     if track_block is not None:
         cols = [c[:n] for c in cols] + [track_block(full.boxes[:n], full.scores[:n], full.labels[:n],
                                                     (full.scores[:n] >= conf).sum(1))]
     packed = torch.cat(cols, -1).cpu()  # one copy back
+    if heads is not None:
+        heads.extend(packed[:n, 0])
     return [packed[i][packed[i][:, SCORE] >= conf] for i in range(n)]
 
 
 class _Tracker:
     """predict(track=...)'s state over the run: the frames' sequences, and the sequences' tracks -- sequence j's in
     slot j % batch of a TrackState on the device (``on_device``: rtdetr_track_update) or of track_reference's host
-    states.  Refuses max_det above the tracker's limit and a sequence key that comes back (frame_sequences)."""
+    states.  Refuses max_det above the tracker's limit and a sequence key that comes back (frame_sequences).
+    With targs.cmc it also owns the camera-motion estimator's state, slot for slot beside the tracks': a
+    motion.MotionState on the device (rtdetr_frame_shift) or sequence_shifts' host state, which measure every
+    frame's shift on the full-frame pass's model input (``out_hw``: its content size)."""
 
-    def __init__(self, targs, paths, sequence_of, batch, max_det, dev, on_device):
+    def __init__(self, targs, paths, sequence_of, batch, max_det, dev, on_device, out_hw):
         if max_det > TRACK_MAX_K:
             raise ValueError(f"track takes at most {TRACK_MAX_K} candidates per frame, got max_det {max_det}")
         self.seq_of = frame_sequences(paths, sequence_of)  # a returning key's ValueError, before any work
-        self.targs, self.batch, self.on_device = targs, batch, on_device
+        self.targs, self.batch, self.on_device, self.out_hw = targs, batch, on_device, tuple(out_hw)
         self.state = TrackState(batch, targs.max_tracks, dev) if on_device else [None] * batch
+        self.cmc = bool(targs.cmc)
+        self.host_shift = {}  # the host path: frame -> (dx, dy, status), shift in source pixels
+        if self.cmc:
+            self.motion = MotionState(batch, *out_hw, dev) if on_device else new_motion_state(batch, *out_hw)
 
-    def device_block(self, n_done, boxes, scores, labels, n_valid, lim):
+    def _tables(self, n_done, n):
+        """frame_slot and frame_reset of the batch's n frames, int32 [2, n] on the host."""
+        meta = self.seq_of[n_done:n_done + n]
+        return torch.tensor([[j % self.batch for _, j, _ in meta], [int(f == 1) for _, _, f in meta]],
+                            dtype=torch.int32)
+
+    def _scale(self, sizes):
+        """Input pixels -> source pixels per frame, fp32 [n, 2] on the host."""
+        return torch.tensor([[w / self.out_hw[1], h / self.out_hw[0]] for w, h in sizes], dtype=torch.float32)
+
+    def device_block(self, n_done, boxes, scores, labels, n_valid, lim, images=None, sizes=None):
         """The batch's n frames, the first of which is frame ``n_done`` of the source, through ONE
         rtdetr_track_update launch -> the TRACK_COLS columns [n, K, 5] fp32 to pack: the id's bits, the track's box
-        clipped to the frame (``lim`` [n, 4])."""
-        meta = self.seq_of[n_done:n_done + boxes.shape[0]]
-        tab = torch.tensor([[j % self.batch for _, j, _ in meta], [int(f == 1) for _, _, f in meta]],
-                           dtype=torch.int32).to(boxes.device)  # frame_slot, frame_reset
+        clipped to the frame (``lim`` [n, 4]).  With cmc, before it and without a host synchronisation in between:
+        rtdetr_frame_shift on the first n slots of ``images`` (the full-frame pass's model input) with the same
+        tables, the int shifts to source pixels by one fp32 multiply with a host-made table (``sizes``: the source
+        frames'), and rtdetr_track_update_shift; the CMC_COLS columns then stand before the tracker's."""
+        n, K = boxes.shape[0], boxes.shape[1]
+        tab = self._tables(n_done, n).to(boxes.device)  # frame_slot, frame_reset
+        shift, cols = None, []
+        if self.cmc:
+            a = self.targs
+            ish, info = _lib.frame_shift(self.motion, images[:n], self.out_hw, tab[0], tab[1], a.cmc_radius, a.cmc_gate,
+                                         a.cmc_rows)
+            shift = ish.to(torch.float32) * self._scale(sizes).to(boxes.device)
+            cols = [torch.cat([shift, info[:, :1].to(torch.float32)], -1)[:, None, :].expand(n, K, CMC_COLS)]
         oid, obx, _ = _lib.track_update(self.state, boxes.contiguous(), scores.contiguous(),
                                         labels.to(torch.int32).contiguous(), n_valid.to(torch.int32).contiguous(),
-                                        tab[0], tab[1], self.targs)
+                                        tab[0], tab[1], self.targs, shift=shift)
         obx = torch.minimum(obx.clamp(min=0.0), lim[:, None, :])
-        return torch.cat([oid.view(torch.float32)[..., None], obx], -1)
+        return torch.cat(cols + [oid.view(torch.float32)[..., None], obx], -1)
 
-    def report(self, frame, row, size):
+    def host_block(self, n_done, images, sizes):
+        """The host path's camera shifts of the batch's n frames: the model's input copied back (its content area,
+        n out_h out_w 12 bytes a batch: slow, this is the off-switch path) through motion.sequence_shifts with the
+        tracker's tables; report() hands each frame's to track_reference."""
+        n = len(sizes)
+        oh, ow = self.out_hw
+        content = images[:n].permute(0, 2, 3, 1)[:, :oh, :ow].contiguous().cpu().numpy()
+        tab = self._tables(n_done, n).numpy()
+        a = self.targs
+        ish, info = sequence_shifts(content, tab[0], tab[1], self.motion, a.cmc_radius, round(1000 * a.cmc_gate),
+                                    a.cmc_rows)
+        shift = torch.from_numpy(ish).to(torch.float32) * self._scale(sizes)
+        for i in range(n):
+            self.host_shift[n_done + i] = (float(shift[i, 0]), float(shift[i, 1]), int(info[i, 0]))
+
+    def report(self, frame, row, size, head=None):
         """Frame ``frame`` of the source: its rows on the host -> (the reported rows, without the tracker's columns,
-        and Prediction's track_ids, track_boxes, sequence and frame).  The rows either carry the device's TRACK_COLS
-        columns or go through track_reference here."""
+        and Prediction's track_ids, track_boxes, sequence and frame; with cmc camera_shift and camera_status).  The
+        rows either carry the device's columns (``head``: the frame's first row as copied back, for the CMC columns
+        of a frame without rows) or go through track_reference here."""
         key, j, f = self.seq_of[frame]
+        cam = {}
         if self.on_device:
             ids = row[:, TRACK_ID].contiguous().view(torch.int32)
             tbx = row[:, TRACK_BOX]
-            row = row[:, :-TRACK_COLS]
+            row = row[:, :-(TRACK_COLS + (CMC_COLS if self.cmc else 0))]
+            if self.cmc:
+                dx, dy, status = head[CMC].tolist()
+                cam = dict(camera_shift=(dx, dy), camera_status=int(status))
         else:
             if f == 1:
                 self.state[j % self.batch] = new_state(self.targs.max_tracks)
+            shift = None
+            if self.cmc:
+                dx, dy, status = self.host_shift.pop(frame)
+                shift, cam = (dx, dy), dict(camera_shift=(dx, dy), camera_status=status)
             oid, obx, _ = track_reference(self.state[j % self.batch], row[:, BOX].numpy(), row[:, SCORE].numpy(),
-                                          row[:, LABEL].numpy(), None, self.targs)
+                                          row[:, LABEL].numpy(), None, self.targs, shift=shift)
             ids = torch.from_numpy(oid)
             lim = torch.tensor([[size[0], size[1], size[0], size[1]]], dtype=torch.float32)
             tbx = torch.minimum(torch.from_numpy(obx).reshape(-1, 4).clamp(min=0.0), lim)
         sel = ids >= 0
         return row[sel], dict(track_ids=ids[sel].to(torch.int64), track_boxes=tbx[sel].contiguous(), sequence=key,
-                              frame=f)
+                              frame=f, **cam)
 
 
 def _prediction(path, size, ctx, row, k=None, fused=False, **tracked) -> Prediction:
@@ -413,8 +484,9 @@ def _prediction(path, size, ctx, row, k=None, fused=False, **tracked) -> Predict
                       members=row[:, MEMBERS].to(torch.int64) if fused else None, **tracked)
 
 
-def _write_files(save_dir, preds, save_json, tracked, save_img):
-    """predictions.json, with a tracker tracks.json and mot/<sequence>.txt, and the overlays."""
+def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False):
+    """predictions.json, with a tracker tracks.json and mot/<sequence>.txt (with cmc camera_motion.json), and the
+    overlays."""
     save_dir.mkdir(parents=True, exist_ok=True)
     if save_json:
         (save_dir / "predictions.json").write_text(json.dumps(coco_results(preds)))
@@ -423,6 +495,8 @@ def _write_files(save_dir, preds, save_json, tracked, save_img):
         (save_dir / "mot").mkdir(exist_ok=True)
         for key, text in mot_lines(preds).items():
             (save_dir / "mot" / (key.replace("/", "_") + ".txt")).write_text(text)
+        if cmc:
+            (save_dir / "camera_motion.json").write_text(json.dumps(camera_motion(preds)))
     if save_img:
         for p in preds:
             _save_overlay(p, save_dir / Path(p.path).name)
@@ -502,7 +576,24 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     the frame), ``sequence`` and ``frame``.  Files: tracks.json (the COCO rows
     plus track_id and sequence) and mot/<sequence>.txt (frame,id,x,y,w,h,
     score,-1,-1,-1; frame 1-based, the box the track's).  With ``track=None``
-    nothing of this runs."""
+    nothing of this runs.
+    ``track`` with ``cmc`` (TrackArgs.cmc, off by default): camera-motion
+    compensation.  Every frame's global shift against its predecessor in the
+    sequence is measured on the full-frame pass's model input (motion.py's rule:
+    one translation, a coarse and a fine search of ``cmc_radius`` input pixels,
+    a gate ``cmc_gate`` against frames without structure, ``cmc_rows`` to keep
+    the window off the car's bonnet) and the tracks' predicted boxes move by it
+    before the association.  On the device that is three more launches per batch
+    (rtdetr_frame_shift) ahead of the tracker's (rtdetr_track_update_shift), the
+    shifts scaled to source pixels on the device, no host synchronisation in
+    between; the packed copy back gains the shift and the status.  The host
+    paths above run motion.sequence_shifts instead, on the model's input copied
+    back -- the off-switch path: that copy is n out_h out_w 12 bytes a batch and
+    slow -- and give the same shifts and the same track bits.  Tiles and the
+    fusion are unaffected.  ``Prediction.camera_shift`` (dx, dy in source
+    pixels) and ``.camera_status`` are set, and camera_motion.json ({sequence:
+    [[frame, dx, dy, status], ...]}) is written beside tracks.json.  Without
+    ``cmc`` nothing of this runs."""
     # engine imports this module, and tests replace engine.EvalForward and preprocess.FrameSource: looked up per call
     from . import engine, preprocess
 
@@ -529,8 +620,9 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     tracker = None
     if targs is not None:  # on the device unless the merge left the candidates on the host
         tracker = _Tracker(targs, ds.paths, sequence_of, batch, max_det, dev,
-                           predict_track_on_gpu(dev) and (tiles is None or gpu_merge))
+                           predict_track_on_gpu(dev) and (tiles is None or gpu_merge), out_hw)
     gpu_track = tracker is not None and tracker.on_device
+    cmc = tracker is not None and tracker.cmc
     if tiles is None:
         collate = preprocess.PackCollate(out_hw, pin=True) if gpu_resize else preprocess.HostCollate(out_hw, pad_hw)
     else:
@@ -553,19 +645,23 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         full = _detect(run, bt["ctx"], [(0, 0, w, h) for w, h in sizes], bt.get("buf"), bt.get("desc"),
                        bt.get("images"), full=True)
         # the tracker's launch: after the merge's (untiled: on postprocess_batched's rows), before the copy back
-        track_block = partial(tracker.device_block, n_done, lim=full.lim[:n]) if gpu_track else None
+        track_block = partial(tracker.device_block, n_done, lim=full.lim[:n], images=full.images,
+                              sizes=sizes) if gpu_track else None
+        heads = [] if cmc and gpu_track else None  # every frame's first row: its CMC columns
+        if cmc and not gpu_track:
+            tracker.host_block(n_done, full.images, sizes)
         t_pre = t_inf = 0.0  # of the tile passes
         if tiles is None:
-            rows, k = _untiled_rows(full, n, conf, track_block), None
+            rows, k = _untiled_rows(full, n, conf, track_block, heads), None
         else:
             k = full.boxes.shape[1]
             cb, cs, cl, t_pre, t_inf = _tile_candidates(run, bt, full, n_tiles)
             win = _pass_windows(sizes, bt["windows"]) if fuse else None
-            rows = _merge_rows(cb, cs, cl, rule, fuse_iou, win, gpu_merge, track_block)
+            rows = _merge_rows(cb, cs, cl, rule, fuse_iou, win, gpu_merge, track_block, heads)
         for i, row in enumerate(rows):
             tr = {}
             if tracker is not None:
-                row, tr = tracker.report(n_done + i, row, sizes[i])
+                row, tr = tracker.report(n_done + i, row, sizes[i], heads[i] if heads else None)
             preds.append(_prediction(bt["paths"][i], sizes[i], bt["ctx"][i], row, k, fuse, **tr))
         t3 = time.perf_counter()
         # from asking for the batch to the input on the device, the capture taken out; the forward; the rest: every
@@ -580,7 +676,7 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         speed["passes"] = 1 + n_tiles
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
-        _write_files(save_dir, preds, save_json, tracker is not None, save_img)
+        _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc)
     return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=engine.ModelHandle(model))
 
 

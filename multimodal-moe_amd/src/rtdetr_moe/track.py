@@ -5,7 +5,8 @@ that links a sequence's detections from frame to frame, stated once.
   has them (track_high, track_low, new_thr, max_age) and are NOT tuned here:
   this tree has no trained weights and no sequence ground truth.
 * ``track_reference``: one frame of one sequence, plain numpy.  The HIP kernel
-  rtdetr_track_update (_lib.track_update) takes the same decisions and computes
+  rtdetr_track_update / rtdetr_track_update_shift (_lib.track_update) takes the
+  same decisions and computes
   the same boxes bit for bit and is tested against this function; it is also
   the tracker of the CPU device and of MOE_PREDICT_TRACK=0.
 * ``TrackState``: the device buffers the kernel keeps its tracks in between
@@ -16,7 +17,11 @@ score, label, id, age, hits (0: the slot is free), and per sequence next_id
 (starts at 1) and dropped.  The candidates are the frame's rows in the order
 given (best first, as postprocess_batched and the merges deliver them); nothing
 is sorted.  All arithmetic is fp32, every operation rounded on its own, no FMA.
- 1. Predict: every live slot box = box + vel, per coordinate.
+ 1. Predict: every live slot, coasting ones included, box = box + vel, per
+    coordinate; with a camera shift (sx, sy) of the frame (TrackArgs.cmc:
+    motion.py) box = (box + vel) + (sx, sy, sx, sy), each operation rounded on
+    its own.  vel is untouched, so the filter learns the residual motion.
+    Without a shift nothing is added (adding zero would turn -0.0 into +0.0).
  2. Bands: row d takes part if d < n_valid, its score is finite and score >=
     track_low; it is high if score >= track_high, else low.  Coordinates must
     be finite.
@@ -67,8 +72,24 @@ class TrackArgs:
     beta: float = 0.25          # filter gain on the velocity
     class_agnostic: bool = False  # ignore labels when matching
     max_tracks: int = 64        # track slots T per sequence, at most 256
+    # camera-motion compensation (motion.py): the tracks' predicted boxes move by the frame's global shift
+    cmc: bool = False
+    cmc_radius: int = 48        # search radius in pixels of the model's input, a multiple of 4 in [4, 64]; not tuned
+    cmc_gate: float = 0.1       # a non-zero shift must beat SAD(0, 0) by this share; not tuned
+    cmc_rows: tuple = (0.0, 1.0)  # the (top, bottom) fractions of the height the estimator looks at
 
     def __post_init__(self):
+        from .motion import check_rows, check_search
+
+        if not isinstance(self.cmc, (bool, np.bool_)):
+            raise ValueError(f"TrackArgs.cmc must be a bool, got {self.cmc!r}")
+        self.cmc = bool(self.cmc)
+        try:
+            self.cmc_radius, _ = check_search(self.cmc_radius, self.cmc_gate)
+            self.cmc_gate = float(self.cmc_gate)
+            self.cmc_rows = check_rows(self.cmc_rows)
+        except ValueError as e:
+            raise ValueError(f"TrackArgs.cmc_*: {e}") from None
         for name in ("track_high", "track_low", "new_thr", "match_iou", "second_iou", "alpha", "beta"):
             v = float(getattr(self, name))
             if v != v:
@@ -157,12 +178,13 @@ def _associate(slots, rows, box, label, b, lab, thr, agnostic, events):
     return out
 
 
-def track_reference(state, boxes, scores, labels, n_valid, args, events=None):
+def track_reference(state, boxes, scores, labels, n_valid, args, events=None, shift=None):
     """One frame of one sequence: boxes fp32 [K, 4] xyxy, scores fp32 [K], labels
     [K] (tensors or arrays), ``n_valid`` None (= K) or the number of leading
     rows that count.  Updates ``state`` (new_state) in place -> (out_id int32
     [K], out_box fp32 [K, 4], count: the reported rows).  ``events``: a dict the
-    frame's event counts (EVENTS) are added to."""
+    frame's event counts (EVENTS) are added to.  ``shift``: the frame's camera
+    shift (sx, sy) in the boxes' pixels, or None: nothing is added."""
     a = TrackArgs.parse(args)
     f32 = np.float32
     b = np.ascontiguousarray(np.asarray(boxes, dtype=f32)).reshape(-1, 4)
@@ -178,6 +200,9 @@ def track_reference(state, boxes, scores, labels, n_valid, args, events=None):
     # 1. predict
     live = hits > 0
     box[live] = box[live] + vel[live]
+    if shift is not None:
+        sx, sy = f32(shift[0]), f32(shift[1])
+        box[live] = box[live] + np.array([sx, sy, sx, sy], dtype=f32)
     # 2. bands
     with np.errstate(invalid="ignore"):
         part = (np.arange(K) < n) & np.isfinite(s) & (s >= f32(a.track_low))

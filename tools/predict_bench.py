@@ -18,6 +18,11 @@ query alike, so the tracker's bands are set at the quartiles of the distinct
 scores of an untimed first run.
 
   python tools/predict_bench.py --track
+With --track --cmc a fourth leg joins them: the tracker on the GPU with
+camera-motion compensation (TrackArgs.cmc; the frames are unrelated to each
+other, so the estimator runs its whole search and its gate refuses the result).
+
+  python tools/predict_bench.py --track --cmc
 """
 from __future__ import annotations
 
@@ -84,6 +89,8 @@ def track_leg(a, d: Path, engine):
     lo, hi, new = (float(u[min(len(u) * q // 4, len(u) - 1)]) for q in (1, 2, 3))
     tracker = dict(track_low=lo, track_high=hi, new_thr=new)
     legs = (("track_gpu", tracker, "1"), ("track_host", tracker, "0"), ("track_off", None, "1"))
+    if a.cmc:
+        legs = (("track_cmc_gpu", dict(tracker, cmc=True), "1"),) + legs
     runs = {name: [] for name, _, _ in legs}
     for r in range(a.rounds):
         for name, trk, switch in legs:
@@ -96,6 +103,8 @@ def track_leg(a, d: Path, engine):
                     "wall_s": round(time.perf_counter() - t0, 2), **{k: round(v, 3) for k, v in res.speed.items()}}
             if trk is not None:
                 line["tracks"] = len({int(t) for p in res.predictions for t in p.track_ids})
+            if trk is not None and trk.get("cmc"):
+                line["cmc_status"] = [sum(p.camera_status == v for p in res.predictions) for v in (0, 1, 2)]
             print(json.dumps(line), flush=True)
             runs[name].append(res.speed)
     os.environ.pop("MOE_PREDICT_TRACK", None)
@@ -121,7 +130,10 @@ def main(argv=None):
                     help="with --tiles: the merge of the tiled legs (fuse: rtdetr_box_fuse / fuse_reference)")
     ap.add_argument("--track", action="store_true",
                     help="time prediction with the tracker on the GPU, on the host and off (conf 0, one sequence)")
+    ap.add_argument("--cmc", action="store_true", help="with --track: add a leg with camera-motion compensation")
     a = ap.parse_args(argv)
+    if a.cmc and not a.track:
+        ap.error("--cmc needs --track")
     from src.rtdetr_moe import engine
 
     with tempfile.TemporaryDirectory(prefix="predict_bench_") as td:
