@@ -423,6 +423,12 @@ class _SetLossHip(torch.autograd.Function):
 PAD_BOX = (0.5, 0.5, 0.1, 0.1)  # finite stand-in for padded target slots (masked out of every loss)
 
 
+def pad_capacity(n):
+    """The capacity M that targets are padded to when the fullest image holds
+    ``n`` boxes: n rounded up to a multiple of 16, at least 16."""
+    return max(16, (int(n) + 15) // 16 * 16)
+
+
 def pad_targets(targets, M, boxes_out=None, labels_out=None, n_valid_out=None):
     """Targets (list of {"boxes" [n,4], "labels" [n]}) -> padded device tensors
     ([B, M, 4], [B, M], int32 [B]) for ``SetCriterion.forward_padded``; writes

@@ -1,45 +1,64 @@
-"""One RT-DETR-MoE training step, optionally with the model's forward and
-backward captured as hipGraphs.
+"""One RT-DETR-MoE training step (TrainStep), in one of three modes.
 
-Why graphs: the model's forward + backward launch ~4,000 kernels (MIOpen
-convolutions + BatchNorm, element-wise ops, 13 MoE launches x 7 layers);
-issued eagerly from Python and the autograd engine, the host takes longer to
-enqueue the backward than the GPU takes to run it.  Captured (GraphedModel),
-the forward and the backward are one hipGraph replay each.  The backward graph
-computes torch.autograd.grad of the forward outputs w.r.t. every trainable
-parameter into static gradient buffers that the optimizer reads directly (no
-per-parameter AccumulateGrad copies).  What stays eager: the Hungarian
-matching (host linear_sum_assignment, one device->host copy of all cost
-matrices), the batched set criterion, and the optimizer: when world > 1
-the data-parallel reduction (one fp32 reduce-scatter over RCCL, AdamW on this
-rank's slice, one all-gather of the weights: optim.ShardedDPAdamW), gradient
-clipping and the fused AdamW update.
+Whole-step graph (GPU, graphs=True with targets=; GraphedStep): the model's
+forward through the project's HIP kernels, the set criterion with the GPU
+Hungarian matcher (fused: matching + losses in three HIP launches), the
+denoising losses and the backward to every parameter are ONE hipGraph.  Its
+inputs -- images, context ids, padded targets, box count, the denoising pack
+-- live in static buffers refreshed by device copies before each replay; no
+host round trip inside the step.  Issued eagerly from Python and the autograd
+engine the same launches take the host longer to enqueue than the GPU takes to
+run them.  This is what bench.py times and engine.train drives.
 
+Graph pair (GPU, graphs=True without targets; GraphedModel): the forward and
+the backward are one replay each; between them the batched set criterion runs
+eagerly on the list of targets, with the Hungarian matching on the host (one
+device->host copy of all cost matrices).  The backward graph computes
+torch.autograd.grad of the forward outputs w.r.t. every trainable parameter.
 The captured forward keeps the MoE aux losses as an explicit graph output so
 their gradients reach the router through the captured backward.
 
-Batch augmentation (an -aug model spec, augment.BatchAugment) runs in front of
-the step, outside every graph: with the whole-step graph its two HIP launches
-write the graph's static images, padded targets and box count directly.
-With mosaic (a -mosaic spec, TrainStep(mosaic=p)) an image carries the boxes
-of up to four, so the padding M is reserved from the augmenter's host bound
-(BatchAugment.need) before the launches.
+Eager (GPU with graphs=False or after use_eager(); CPU): forward, criterion
+and loss.backward() issued from Python; on the CPU in fp32 with
+torch.optim.AdamW, at world > 1 under DDP.
 
-Gradient accumulation (an -nbs<N> spec, TrainStep(accumulate=K)): a replay
-overwrites the static gradient buffers, so after each one a HIP launch adds
-them to an fp32 sum (optim.GradAccumulator); every K-th call runs the
-data-parallel exchange and the optimizer once, on the mean gradient.
+In both graph modes the gradients land in static buffers that the optimizer
+reads directly (no per-parameter AccumulateGrad copies).  Every capture goes
+through one skeleton, _capture_session: warm-up and capture on the same side
+stream, which keeps the captured graph a single chain.
+
+What stays outside every graph:
+- the optimizer (optim.FlatAdamW: gradient clip + AdamW + bf16 weight refresh
+  in three HIP launches; at world > 1 optim.ShardedDPAdamW: one fp32
+  reduce-scatter over RCCL, AdamW on this rank's slice, one all-gather of the
+  weights), and inside its AdamW launch the weight average (ema.ModelEMA);
+- batch augmentation (an -aug model spec, augment.BatchAugment), in front of
+  the step: with the whole-step graph its two HIP launches write the graph's
+  static images, padded targets and box count directly.  With mosaic (a
+  -mosaic spec, TrainStep(mosaic=p)) an image carries the boxes of up to four,
+  so the padding M is reserved from the augmenter's host bound
+  (BatchAugment.need) before the launches;
+- the denoising queries' noise (a -dn<N> spec, DenoisingState.pack), drawn
+  into the graph's static pack next to the targets;
+- gradient accumulation (an -nbs<N> spec, TrainStep(accumulate=K)): a replay
+  overwrites the static gradient buffers, so after each one a HIP launch adds
+  them to an fp32 sum (optim.GradAccumulator); every K-th call runs the
+  data-parallel exchange and the optimizer once, on the mean gradient.
 """
 from __future__ import annotations
 
 import os
 import time
+from contextlib import contextmanager
 
 import torch
 import torch.distributed as dist
 from torch import nn
 
+from .augment import targets_from_padded
 from .conv import check_grad_slots
+from .criterion import pad_capacity, pad_targets
+from .denoising import DenoisingConfig, dn_shapes, make_denoising
 from .linear import TokenSelfAttention, deferred_weight_grads, merge_deferred
 from .model import RTDETRMoE
 from .schedule import accumulate_count
@@ -128,6 +147,44 @@ def release_graphs():
         torch.cuda.synchronize()
 
 
+@contextmanager
+def _capture_session(warm, warmup, fn):
+    """The skeleton of every step capture (GraphedModel's pair, GraphedStep's
+    one graph).  Before the body: ``warmup`` calls of ``warm()`` (one forward +
+    backward each) on a new side stream, the streams joined, the device
+    drained and quiesce_collectives.  The body gets ``(pool, capture)``:
+    ``with capture(graph):`` captures ``graph`` into the session's pool ON THE
+    WARM-UP STREAM -- the autograd nodes the warm-up created (AccumulateGrad
+    keeps the stream it was made on) then match the capture stream, so the
+    backward needs no cross-stream syncs: a single chain, no fork/join branches
+    for the HIP runtime to spread over parallel streams.  The body drops its
+    own references to the captured passes' tensors; after it the autograd
+    graphs of ``fn`` (when a Module) are released and the device drained."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # warm-up: convolution search, library attributes, allocator
+        for _ in range(warmup):
+            warm()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    quiesce_collectives()
+    pool = torch.cuda.graph_pool_handle()
+    yield pool, lambda graph: torch.cuda.graph(graph, pool=pool, stream=side, capture_error_mode=CAPTURE_MODE)
+    _drop_autograd_graphs(fn if isinstance(fn, nn.Module) else None)
+    torch.cuda.synchronize()
+
+
+def _most_boxes(targets):
+    """The largest box count of one image in a batch of targets."""
+    return max((len(t["boxes"]) for t in targets), default=0)
+
+
+def _dense_grads(grads, params):
+    """A capture's gradient outputs as the static buffers the optimizer reads:
+    zeros where autograd found no path to a parameter."""
+    return [g if g is not None else torch.zeros_like(p) for g, p in zip(grads, params)]
+
+
 class FlatOutputs(nn.Module):
     """Model wrapper whose forward returns a flat tuple of tensors (a graph
     output signature): final, auxiliary and encoder logits/boxes, then -- with
@@ -197,40 +254,27 @@ class GraphedModel:
         self.autocast = autocast
         self.static_images = images.clone()
         self.static_ctx = ctx.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up: convolution search, library attributes, allocator
-            for _ in range(warmup):
+        with _capture_session(self._warm, warmup, fn) as (self.pool, capture):
+            self.g_fwd = torch.cuda.CUDAGraph()
+            with capture(self.g_fwd):
                 out = self._run()
-                grads = torch.autograd.grad([o for o in out if o.requires_grad],
-                                            params, [torch.ones_like(o) for o in out if o.requires_grad],
-                                            allow_unused=True)
+            self.static_out = out
+            self.diff = [i for i, o in enumerate(out) if o.requires_grad]
+            self.static_gout = [torch.zeros_like(o) for o in out]
+            self.g_bwd = torch.cuda.CUDAGraph()
+            with capture(self.g_bwd):
+                grads = torch.autograd.grad([out[i] for i in self.diff], params,
+                                            [self.static_gout[i] for i in self.diff], allow_unused=True)
                 check_grad_slots()
-                del out, grads
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        quiesce_collectives()
-        self.pool = torch.cuda.graph_pool_handle()
-        self.g_fwd = torch.cuda.CUDAGraph()
-        # captured on the warm-up stream: the autograd nodes the warm-up created
-        # (AccumulateGrad keeps the stream it was made on) then match the capture
-        # stream, so the backward needs no cross-stream syncs -- a single chain,
-        # no fork/join branches for the HIP runtime to spread over parallel streams
-        with torch.cuda.graph(self.g_fwd, pool=self.pool, stream=side, capture_error_mode=CAPTURE_MODE):
-            out = self._run()
-        self.static_out = out
-        self.diff = [i for i, o in enumerate(out) if o.requires_grad]
-        self.static_gout = [torch.zeros_like(o) for o in out]
-        self.g_bwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_bwd, pool=self.pool, stream=side, capture_error_mode=CAPTURE_MODE):
-            grads = torch.autograd.grad([out[i] for i in self.diff], params,
-                                        [self.static_gout[i] for i in self.diff], allow_unused=True)
-            check_grad_slots()
-        self.static_grads = [g if g is not None else torch.zeros_like(p) for g, p in zip(grads, params)]
-        self.anchor = torch.zeros((), device=images.device, requires_grad=True)
-        del grads
-        _drop_autograd_graphs(self.fn if isinstance(self.fn, nn.Module) else None)
-        torch.cuda.synchronize()
+            self.static_grads = _dense_grads(grads, params)
+            self.anchor = torch.zeros((), device=images.device, requires_grad=True)
+            del grads
+
+    def _warm(self):
+        out = self._run()
+        diff = [o for o in out if o.requires_grad]
+        torch.autograd.grad(diff, self.params, [torch.ones_like(o) for o in diff], allow_unused=True)
+        check_grad_slots()
 
     def _run(self):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.autocast, cache_enabled=False):
@@ -251,8 +295,6 @@ class DenoisingState:
     and seeded from the run's seed and the rank."""
 
     def __init__(self, model: RTDETRMoE, device, seed=0, cfg=None):
-        from .denoising import DenoisingConfig
-
         self.num_denoising = model.decoder.num_denoising
         self.num_classes = model.decoder.num_classes
         self.num_layers = len(model.decoder.layers)
@@ -261,10 +303,15 @@ class DenoisingState:
         self.generator = torch.Generator(device=device)
         self.generator.manual_seed(int(seed) * 1000 + rank)
 
-    def make(self, tgt_boxes, tgt_labels, n_valid, G, out=None):
-        from .denoising import make_denoising
-
-        return make_denoising(tgt_boxes, tgt_labels, n_valid, self.num_classes, G, self.cfg, self.generator, out)
+    def pack(self, tgt_boxes, tgt_labels, n_valid, M, out=None):
+        """The denoising pack ``(labels [B, Qdn], boxes [B, Qdn, 4], G)`` of
+        targets padded to M (G and Qdn follow M: denoising.dn_shapes), drawn
+        from the generator into new tensors, or into ``out`` (an earlier pack
+        for the same M: a graphed step's static buffers), which is returned."""
+        G, _ = dn_shapes(M, self.num_denoising)
+        labels, boxes = make_denoising(tgt_boxes, tgt_labels, n_valid, self.num_classes, G, self.cfg,
+                                       self.generator, None if out is None else out[:2])
+        return labels, boxes, G
 
 
 class GraphedStep:
@@ -285,8 +332,6 @@ class GraphedStep:
 
     def __init__(self, fn, criterion, params, images, ctx, targets, num_boxes, *, warmup=3, autocast=False,
                  max_boxes=None, on_capture=None, dn=None):
-        from .criterion import pad_targets
-
         self.fn, self.criterion, self.params, self.autocast = fn, criterion, params, autocast
         self.dn = dn
         self.on_capture = on_capture  # called with static_grads after every (re-)capture
@@ -294,8 +339,7 @@ class GraphedStep:
         dev = images.device
         self.static_images = images.clone()
         self.static_ctx = ctx.clone()
-        need = max((len(t["boxes"]) for t in targets), default=0)
-        self.M = max_boxes or max(16, (need + 15) // 16 * 16)
+        self.M = max_boxes or pad_capacity(_most_boxes(targets))
         self.tb, self.tl, self.nv = pad_targets(targets, self.M)
         self.nb = torch.full((), float(num_boxes), dtype=torch.float32, device=dev)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -304,25 +348,18 @@ class GraphedStep:
         self._capture()
 
     def _dn_alloc(self):
-        """Static denoising buffers for the current M (G and Qdn follow M),
-        filled once for the warm-up and the capture without advancing the
-        generator: the first replay draws what an eager first step draws."""
+        """The static denoising pack for the current M, drawn once for the
+        warm-up and the capture without advancing the generator: the first
+        replay draws what an eager first step draws."""
         self.dn_pack = None
-        if self.dn is None:
-            return
-        from .denoising import dn_shapes
-
-        G, Qdn = dn_shapes(self.M, self.dn.num_denoising)
-        B, dev = self.tb.shape[0], self.tb.device
-        self.dn_pack = (torch.empty((B, Qdn), dtype=torch.int64, device=dev),
-                        torch.empty((B, Qdn, 4), dtype=torch.float32, device=dev), G)
-        state = self.dn.generator.get_state()
-        self._dn_refresh()
-        self.dn.generator.set_state(state)
+        if self.dn is not None:
+            state = self.dn.generator.get_state()
+            self.dn_pack = self.dn.pack(self.tb, self.tl, self.nv, self.M)
+            self.dn.generator.set_state(state)
 
     def _dn_refresh(self):
         if self.dn_pack is not None:
-            self.dn.make(self.tb, self.tl, self.nv, self.dn_pack[2], out=self.dn_pack[:2])
+            self.dn.pack(self.tb, self.tl, self.nv, self.M, out=self.dn_pack)
 
     def _loss(self):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.autocast, cache_enabled=False):
@@ -362,29 +399,20 @@ class GraphedStep:
         self.deferred_layers = 0 if deferred is None else len(deferred.items)
         return merge_deferred(self.params, grads, deferred)
 
+    def _warm(self):
+        loss, _ = self._loss()
+        self._grads(loss)
+
     def _capture(self):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up: convolution search, library attributes, allocator
-            for _ in range(self.warmup):
-                loss, _ = self._loss()
+        with _capture_session(self._warm, self.warmup, self.fn) as (self.pool, capture):
+            self.graph = torch.cuda.CUDAGraph()
+            with capture(self.graph):
+                loss, losses = self._loss()
                 grads = self._grads(loss)
-                del loss, grads
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        quiesce_collectives()
-        self.pool = torch.cuda.graph_pool_handle()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=self.pool, stream=side,
-                              capture_error_mode=CAPTURE_MODE):  # warm-up stream: see GraphedModel
-            loss, losses = self._loss()
-            grads = self._grads(loss)
-            self.static_loss = loss.detach()
-            self.static_losses = {k: v.detach() for k, v in losses.items()}
-        self.static_grads = [g if g is not None else torch.zeros_like(p) for g, p in zip(grads, self.params)]
-        del loss, losses, grads
-        _drop_autograd_graphs(self.fn if isinstance(self.fn, nn.Module) else None)
-        torch.cuda.synchronize()
+                self.static_loss = loss.detach()
+                self.static_losses = {k: v.detach() for k, v in losses.items()}
+            self.static_grads = _dense_grads(grads, self.params)
+            del loss, losses, grads
         self.captures += 1
         if self.on_capture is not None:
             self.on_capture(self.static_grads)
@@ -394,12 +422,10 @@ class GraphedStep:
         captured padding re-captures at the next multiple of 16 (rare).
         ``need``: the boxes an image may hold when that is not the batch's
         largest count (mosaic: BatchAugment.need)."""
-        from .criterion import pad_targets
-
         if need is None:
-            need = max((len(t["boxes"]) for t in targets), default=0)
+            need = _most_boxes(targets)
         if need > self.M:
-            self.M = (need + 15) // 16 * 16
+            self.M = pad_capacity(need)
             self.tb, self.tl, self.nv = pad_targets(targets, self.M)
             self.graph = None
             self._dn_alloc()  # G and Qdn follow M
@@ -410,8 +436,6 @@ class GraphedStep:
         called ``reserve`` and written this step's images, padded targets and
         box count into ``static_images``, ``tb`` / ``tl`` / ``nv`` and ``nb``;
         nothing but the context ids is copied."""
-        from .criterion import pad_targets
-
         if not in_place:
             self.reserve(targets)
             if images.data_ptr() != self.static_images.data_ptr():
@@ -499,52 +523,69 @@ class TrainStep:
              flat fp32 masters and rewrites the bf16 weights;
       "amp"  -- fp32 parameters under bf16 autocast (same optimizer).
     On CPU the model runs in fp32 with torch.optim.AdamW and
-    clip_grad_norm_ (the semantics FlatAdamW restates)."""
+    clip_grad_norm_ (the semantics FlatAdamW restates).
+
+    accumulate: micro-steps (calls) per optimizer step, K.  None takes
+    the model spec's nominal batch size (-nbs<N>): K = max(1, round(nbs /
+    (batch * world))), 1 without the token.  With K = 1 the step is
+    unchanged (no accumulator, the same launches).  With K > 1 every call
+    adds its gradients to an fp32 sum on the device (optim.GradAccumulator,
+    one HIP launch after the graph replay) and the K-th call runs the
+    data-parallel exchange, the clip and AdamW (and the weight average)
+    once on the mean gradient over micro-steps and ranks; every call
+    returns its own loss.  ``self.accumulate`` may be changed between calls
+    (the engine's warm-up ramp); ``micro_steps`` / ``opt_steps`` count the
+    calls and the optimizer steps.  ``set_lr_scale`` scales the learning
+    rates given here (the engine's schedule).
+    seed: the run's seed (the denoising queries' noise generator, the
+    augmentation parameters' generator).
+    augment: batch augmentation (augment.BatchAugment: scale / translate
+    jitter, flip, HSV jitter of images and boxes, on the GPU two HIP
+    launches in front of the step graph); None takes the model spec's
+    -aug token, False leaves the step unchanged (``self.aug`` is None).
+    With it the step takes uint8 or fp32 images in any layout.  With
+    graphs=True it needs targets= (the whole-step graph, whose static
+    inputs the kernels write; the forward / backward graph pair without
+    targets is refused with a ValueError).  The eager / CPU step takes any
+    batch size up to the first batch's.
+    mosaic: the probability that a training image becomes a four-image
+    mosaic of its batch (augment.py); None takes the model spec's -mosaic
+    token; a positive value implies ``augment`` unless that is False.
+    ``self.aug.mosaic`` may be changed between steps (the engine's
+    close_mosaic).  With graphs=True the first capture pads the targets to
+    max(16, 4 x the example batch's largest count rounded up to 16) -- a
+    heuristic start that spares re-captures, not a bound: every step
+    reserves the augmenter's bound and re-captures when it is larger.
+    content_hw: the (h, w) of the image content inside the padded tensor
+    (the augmentation's frame; default: the whole tensor).
+    ema_decay / ema_tau: the weight average (ema.ModelEMA: updated once per
+    optimizer step, on the GPU inside the AdamW launch); None takes the
+    model spec's values (-ema / -ematau<N> tokens), a decay of 0 is off
+    (``self.ema`` is None and the step is unchanged).
+    zero: the ZeRO-1 optimizer (optim.ShardedDPAdamW) -- default: at
+    world > 1 unless MOE_ZERO=0; True also at world 1 (a world-1 process
+    group: the RCCL reduce-scatter / all-gather branch on one GPU, tests)."""
 
     def __init__(self, model: RTDETRMoE, criterion, images, ctx, *, lr=1e-4, lr_backbone=1e-5,
                  weight_decay=1e-4, clip_norm=0.1, graphs=True, ddp_local=None, world=1, precision="bf16",
                  targets=None, num_boxes=1.0, zero=None, seed=0, ema_decay=None, ema_tau=None, augment=None,
                  content_hw=None, mosaic=None, accumulate=None):
-        """accumulate: micro-steps (calls) per optimizer step, K.  None takes
-        the model spec's nominal batch size (-nbs<N>): K = max(1, round(nbs /
-        (batch * world))), 1 without the token.  With K = 1 the step is
-        unchanged (no accumulator, the same launches).  With K > 1 every call
-        adds its gradients to an fp32 sum on the device (optim.GradAccumulator,
-        one HIP launch after the graph replay) and the K-th call runs the
-        data-parallel exchange, the clip and AdamW (and the weight average)
-        once on the mean gradient over micro-steps and ranks; every call
-        returns its own loss.  ``self.accumulate`` may be changed between calls
-        (the engine's warm-up ramp); ``micro_steps`` / ``opt_steps`` count the
-        calls and the optimizer steps.  ``set_lr_scale`` scales the learning
-        rates given here (the engine's schedule).
-        seed: the run's seed (the denoising queries' noise generator, the
-        augmentation parameters' generator).
-        augment: batch augmentation (augment.BatchAugment: scale / translate
-        jitter, flip, HSV jitter of images and boxes, on the GPU two HIP
-        launches in front of the step graph); None takes the model spec's
-        -aug token, False leaves the step unchanged (``self.aug`` is None).
-        With it the step takes uint8 or fp32 images in any layout.  With
-        graphs=True it needs targets= (the whole-step graph, whose static
-        inputs the kernels write; the forward / backward graph pair without
-        targets is refused with a ValueError).  The eager / CPU step takes any
-        batch size up to the first batch's.
-        mosaic: the probability that a training image becomes a four-image
-        mosaic of its batch (augment.py); None takes the model spec's -mosaic
-        token; a positive value implies ``augment`` unless that is False.
-        ``self.aug.mosaic`` may be changed between steps (the engine's
-        close_mosaic).  With graphs=True the first capture pads the targets to
-        max(16, 4 x the example batch's largest count rounded up to 16) -- a
-        heuristic start that spares re-captures, not a bound: every step
-        reserves the augmenter's bound and re-captures when it is larger.
-        content_hw: the (h, w) of the image content inside the padded tensor
-        (the augmentation's frame; default: the whole tensor).
-        ema_decay / ema_tau: the weight average (ema.ModelEMA: updated once per
-        optimizer step, on the GPU inside the AdamW launch); None takes the
-        model spec's values (-ema / -ematau<N> tokens), a decay of 0 is off
-        (``self.ema`` is None and the step is unchanged).
-        zero: the ZeRO-1 optimizer (optim.ShardedDPAdamW) -- default: at
-        world > 1 unless MOE_ZERO=0; True also at world 1 (a world-1 process
-        group: the RCCL reduce-scatter / all-gather branch on one GPU, tests)."""
+        """The stages run in this order, and the order is the contract:
+          1. bf16 cast of gemm_params (precision "bf16")
+          2. broadcast from rank 0 (the flat A/B path only)   } _build_optimizer
+          3. the optimizer takes over the parameters: fp32    }
+             ones become views of its flat spaces
+          4. the accumulator, when accumulate > 1 (GPU)
+          5. ep_grad_scale = 1.0 on expert-parallel MoE layers
+          6. augmenter, image conversion and _cast_in           _build_augmenter
+          7. DenoisingState (its generator)
+          8. warm-up and capture                                _build_runner
+          9. EMA                                                _build_ema
+        3 to 7 precede the capture because the graph bakes in their addresses
+        and values.  The EMA comes last because it starts from the state the
+        first step sees: after the optimizer took over the parameters and after
+        the captures' warm-up passes (they move the BatchNorm statistics, not
+        the weights)."""
         self.model = model
         self.criterion = criterion
         self.clip_norm = clip_norm
@@ -552,55 +593,20 @@ class TrainStep:
         self.world = world
         self.graphs = graphs
         self.precision = precision if images.is_cuda else "fp32"
+        spec = getattr(model, "spec", None)
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         self.params = [p for _, p in named]
         if self.precision == "bf16":
             for p in gemm_params(model):
                 p.data = p.data.to(torch.bfloat16)
-        bb = [p for n, p in named if n.startswith("backbone.")]
-        rest = [p for n, p in named if not n.startswith("backbone.")]
         self.ep_params = [p for p in self.params if getattr(p, "expert_parallel", False)]
         self.dp_params = [p for p in self.params if not getattr(p, "expert_parallel", False)]
         self.ep_group = _ep_group(model)
-        if images.is_cuda:
-            # flat fp32 masters + moments, clip + AdamW + bf16 weight refresh in
-            # three HIP launches (optim.py); fp32 parameters become views of
-            # their master segment -- before any graph capture bakes addresses.
-            # Expert-parallel shards enter the clip norm through a sum over the
-            # EP group (the same global norm on every rank)
-            from .optim import FlatAdamW, ShardedDPAdamW
-
-            use_zero = (world > 1 and _ZERO) if zero is None else bool(zero)
-            if world > 1 and not use_zero:
-                # (A/B flat path) every replica starts from rank 0's weights, as DDP
-                # does, before FlatAdamW copies its masters
-                from .optim import DPGradReducer
-
-                self.reducer = DPGradReducer(self.dp_params)
-                self.reducer.broadcast_params()
-            if use_zero:
-                # C3 data parallelism: reduce-scatter of the fp32 gradients,
-                # AdamW on this rank's 1/world slice, all-gather of the weights
-                # (optim.ShardedDPAdamW); the replicated parameters become views
-                # of its flat spaces here, before any graph capture
-                self.opt = ShardedDPAdamW([(bb, lr_backbone), (rest, lr)], weight_decay=weight_decay,
-                                          clip_norm=clip_norm, sharded=self.ep_params)
-            else:
-                self.opt = FlatAdamW([(bb, lr_backbone), (rest, lr)], weight_decay=weight_decay,
-                                     clip_norm=clip_norm, sharded=self.ep_params, shard_group=self.ep_group)
-            self.opt_params = None
-        else:
-            self.opt_params = bb + rest
-            self.opt = torch.optim.AdamW([{"params": bb, "lr": lr_backbone}, {"params": rest, "lr": lr}], lr=lr,
-                                         weight_decay=weight_decay)
+        self.opt, self.opt_params, self.reducer = self._build_optimizer(named, images.is_cuda, lr, lr_backbone,
+                                                                        weight_decay, zero)
         self.flat = FlatOutputs(model)
-        self.reducer = getattr(self, "reducer", None)
         self.base_lrs = [float(lr_backbone), float(lr)]  # per LR group (backbone, rest): set_lr_scale scales these
-        if accumulate is None:
-            accumulate = accumulate_count(int(getattr(getattr(model, "spec", None), "nbs", 0)), images.shape[0], world)
-        if int(accumulate) < 1:
-            raise ValueError(f"accumulate must be >= 1, got {accumulate}")
-        self.accumulate = int(accumulate)
+        self.accumulate = self._resolve_accumulate(accumulate, spec, images.shape[0])
         self.micro_steps = 0  # calls
         self.opt_steps = 0    # optimizer steps
         self.acc = None       # optim.GradAccumulator (GPU), allocated when a cycle of more than one micro-step starts
@@ -608,77 +614,123 @@ class TrainStep:
         if self.accumulate > 1 and self.opt_params is None:
             self._accumulator()
         if world > 1 and images.is_cuda:
-            from ..moe.layer import MoEFFN
-
-            # expert-parallel weights are not reduced (their gradients already
-            # hold every rank's tokens), so their layers must not pre-scale by
-            # 1/world: the optimizer applies 1/world to every gradient
-            for m in model.modules():
-                if isinstance(m, MoEFFN) and m.ep_size > 1:
-                    m.ep_grad_scale = 1.0
-        spec = getattr(model, "spec", None)
-        self.aug = None
+            self._unscale_expert_parallel()
         self._m_in = 16  # the mosaic path's raw-target padding: grows with the batches' counts
-        mosaic = float(getattr(spec, "mosaic", 0.0) if mosaic is None else mosaic)
-        max_boxes = None
-        if (bool(getattr(spec, "augment", False)) or mosaic > 0) if augment is None else bool(augment):
-            from .augment import BatchAugment
-
-            if graphs and targets is None:
-                raise ValueError("batch augmentation needs targets= for graphs=True (the whole-step graph)")
-            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-            padded_hw = tuple(images.shape[-2:])
-            self.aug = BatchAugment(images.shape[0], content_hw or padded_hw, padded_hw, images.device, seed=seed,
-                                    rank=rank,
-                                    out_dtype=torch.bfloat16 if self.precision == "bf16" else torch.float32,
-                                    mosaic=mosaic)
-            if self.aug.mosaic_path and targets is not None:
-                most = max((len(t["boxes"]) for t in targets), default=0)
-                max_boxes = max(16, (4 * most + 15) // 16 * 16)   # a starting point, see ``mosaic`` above
-            # the static image buffer is what the kernel writes: float, channels_last
-            if images.dtype == torch.uint8:
-                images = images.float() / 255.0
-            if images.is_cuda:
-                images = images.contiguous(memory_format=torch.channels_last)
+        self.aug, images, max_boxes = self._build_augmenter(spec, augment, mosaic, images, targets, content_hw, seed)
         images = self._cast_in(images)
-        self.runner = None
-        self.stepper = None
         # contrastive denoising queries (a -dn<N> spec): one generator per TrainStep
         self.dn = DenoisingState(model, images.device, seed) if model.decoder.num_denoising > 0 else None
         self.last_losses = None  # {component: detached value} of the last step (criterion sets, _dn sets)
-        if graphs and self.dn is not None and targets is None:
-            raise ValueError("a model with denoising queries needs targets= for graphs=True (the whole-step graph)")
-        if graphs and targets is not None:  # whole step as one graph (GPU matcher)
-            self.stepper = GraphedStep(self.flat, criterion, self.params, images, ctx, targets, num_boxes,
-                                       autocast=self.precision == "amp", on_capture=self._bind_grads, dn=self.dn,
-                                       max_boxes=max_boxes)
-            self.fn = None
-            self.ddp = None
-        elif graphs:
-            self.runner = GraphedModel(self.flat, self.params, images, ctx, autocast=self.precision == "amp")
-            self.fn = self.runner
-            self.ddp = None
-            # the optimizer reads the static gradient buffers of the backward graph
-            for p, g in zip(self.params, self.runner.static_grads):
-                p.grad = g
-        elif world > 1 and not images.is_cuda:  # CPU (gloo): DDP buckets overlapped with the backward
+        self.stepper, self.runner, self.fn, self.ddp = self._build_runner(images, ctx, targets, num_boxes, max_boxes,
+                                                                           ddp_local)
+        self.ema = self._build_ema(spec, ema_decay, ema_tau)
+
+    def _build_optimizer(self, named, on_gpu, lr, lr_backbone, weight_decay, zero):
+        """-> (opt, opt_params, reducer).  GPU: flat fp32 masters + moments,
+        clip + AdamW + bf16 weight refresh in three HIP launches (optim.py);
+        fp32 parameters become views of their master segment.  Expert-parallel
+        shards enter the clip norm through a sum over the EP group (the same
+        global norm on every rank).  ``opt_params`` is None on the GPU, the
+        optimizer's parameter list on the CPU (torch.optim.AdamW); ``reducer``
+        is the flat A/B path's all-reduce, None everywhere else."""
+        bb = [p for n, p in named if n.startswith("backbone.")]
+        rest = [p for n, p in named if not n.startswith("backbone.")]
+        if not on_gpu:
+            opt = torch.optim.AdamW([{"params": bb, "lr": lr_backbone}, {"params": rest, "lr": lr}], lr=lr,
+                                    weight_decay=weight_decay)
+            return opt, bb + rest, None
+        from .optim import DPGradReducer, FlatAdamW, ShardedDPAdamW
+
+        use_zero = (self.world > 1 and _ZERO) if zero is None else bool(zero)
+        if use_zero:
+            # C3 data parallelism: reduce-scatter of the fp32 gradients, AdamW on this rank's 1/world
+            # slice, all-gather of the weights; the replicated parameters become views of its flat spaces
+            opt = ShardedDPAdamW([(bb, lr_backbone), (rest, lr)], weight_decay=weight_decay,
+                                 clip_norm=self.clip_norm, sharded=self.ep_params)
+            return opt, None, None
+        reducer = None
+        if self.world > 1:
+            # (A/B flat path) every replica starts from rank 0's weights, as DDP does, before
+            # FlatAdamW copies its masters
+            reducer = DPGradReducer(self.dp_params)
+            reducer.broadcast_params()
+        opt = FlatAdamW([(bb, lr_backbone), (rest, lr)], weight_decay=weight_decay, clip_norm=self.clip_norm,
+                        sharded=self.ep_params, shard_group=self.ep_group)
+        return opt, None, reducer
+
+    def _resolve_accumulate(self, accumulate, spec, batch):
+        if accumulate is None:
+            accumulate = accumulate_count(int(getattr(spec, "nbs", 0)), batch, self.world)
+        if int(accumulate) < 1:
+            raise ValueError(f"accumulate must be >= 1, got {accumulate}")
+        return int(accumulate)
+
+    def _unscale_expert_parallel(self):
+        """Expert-parallel weights are not reduced (their gradients already
+        hold every rank's tokens), so their layers must not pre-scale by
+        1/world: the optimizer applies 1/world to every gradient."""
+        from ..moe.layer import MoEFFN
+
+        for m in self.model.modules():
+            if isinstance(m, MoEFFN) and m.ep_size > 1:
+                m.ep_grad_scale = 1.0
+
+    def _build_augmenter(self, spec, augment, mosaic, images, targets, content_hw, seed):
+        """-> (aug or None, the images as the step's example input, the first
+        capture's padding or None).  With an augmenter the images become what
+        its kernels read and the static buffer holds: float, channels_last."""
+        mosaic = float(getattr(spec, "mosaic", 0.0) if mosaic is None else mosaic)
+        if not ((bool(getattr(spec, "augment", False)) or mosaic > 0) if augment is None else bool(augment)):
+            return None, images, None
+        from .augment import BatchAugment
+
+        if self.graphs and targets is None:
+            raise ValueError("batch augmentation needs targets= for graphs=True (the whole-step graph)")
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        padded_hw = tuple(images.shape[-2:])
+        aug = BatchAugment(images.shape[0], content_hw or padded_hw, padded_hw, images.device, seed=seed, rank=rank,
+                           out_dtype=torch.bfloat16 if self.precision == "bf16" else torch.float32, mosaic=mosaic)
+        max_boxes = None
+        if aug.mosaic_path and targets is not None:
+            max_boxes = pad_capacity(4 * _most_boxes(targets))  # a starting point, see ``mosaic`` (class docstring)
+        if images.dtype == torch.uint8:
+            images = images.float() / 255.0
+        if images.is_cuda:
+            images = images.contiguous(memory_format=torch.channels_last)
+        return aug, images, max_boxes
+
+    def _build_runner(self, images, ctx, targets, num_boxes, max_boxes, ddp_local):
+        """Warm-up and capture -> (stepper, runner, fn, ddp): the whole-step
+        graph, or the graph pair (``fn`` is the runner), or the eager callable
+        ``fn`` (on the CPU at world > 1 under DDP)."""
+        autocast = self.precision == "amp"
+        if self.graphs and targets is not None:  # whole step as one graph (GPU matcher)
+            stepper = GraphedStep(self.flat, self.criterion, self.params, images, ctx, targets, num_boxes,
+                                  autocast=autocast, on_capture=self._bind_grads, dn=self.dn, max_boxes=max_boxes)
+            return stepper, None, None, None
+        if self.graphs:
+            if self.dn is not None:
+                raise ValueError("a model with denoising queries needs targets= for graphs=True "
+                                 "(the whole-step graph)")
+            runner = GraphedModel(self.flat, self.params, images, ctx, autocast=autocast)
+            self._bind_grads(runner.static_grads)  # the optimizer reads the backward graph's static buffers
+            return None, runner, runner, None
+        if self.world > 1 and not images.is_cuda:  # CPU (gloo): DDP buckets overlapped with the backward
             from .engine import wrap_ddp
 
-            self.ddp = wrap_ddp(self.flat, ddp_local)
-            self.fn = self.ddp
-        else:
-            self.fn = self.flat
-            self.ddp = None
+            ddp = wrap_ddp(self.flat, ddp_local)
+            return None, None, ddp, ddp
+        return None, None, self.flat, None
+
+    def _build_ema(self, spec, ema_decay, ema_tau):
+        """-> ema.ModelEMA or None (a decay of 0); allocates, moves nothing."""
         ema_decay = float(getattr(spec, "ema_decay", 0.0) if ema_decay is None else ema_decay)
         ema_tau = float(getattr(spec, "ema_tau", 2000.0) if ema_tau is None else ema_tau)
-        self.ema = None
-        if ema_decay > 0.0:
-            # the average starts at the state the first step sees: after the optimizer took over
-            # the parameters (fp32 views, flat spaces) and after the captures' warm-up passes
-            # (they move the BatchNorm statistics, not the weights); allocates, moves nothing
-            from .ema import ModelEMA
+        if not ema_decay > 0.0:
+            return None
+        from .ema import ModelEMA
 
-            self.ema = ModelEMA(model, self.opt, decay=ema_decay, tau=ema_tau)
+        return ModelEMA(self.model, self.opt, decay=ema_decay, tau=ema_tau)
 
     def _bind_grads(self, static_grads):
         """Point every parameter's .grad at the (new) static gradient buffers of
@@ -692,26 +744,20 @@ class TrainStep:
         images, padded targets, counts -- and the box count (the batch sum of
         the surviving boxes; at world > 1 its mean over the ranks, clamped at
         1, as the engine forms the host count), all on the device."""
-        from .criterion import pad_targets
-
         st = self.stepper
+        counts = [len(t["boxes"]) for t in targets]
+        # reserve the host bound for this step's table: on the mosaic path an image holds the boxes of up
+        # to four (a plain table's bound is the batch's largest count)
+        table = self.aug.draw(len(targets))
+        st.reserve(targets, need=self.aug.need(counts, table))
         if self.aug.mosaic_path:
-            # an image holds the boxes of up to four: reserve the host bound for this step's table, then
             # compact from raw buffers of the batch's own padding (M_in) into the graph's (M_out = st.M)
-            counts = [len(t["boxes"]) for t in targets]
-            table = self.aug.draw(len(targets))
-            st.reserve(targets, need=self.aug.need(counts, table))
-            self._m_in = max(self._m_in, (max(counts, default=0) + 15) // 16 * 16)
-            raw = self.aug.raw_targets(self._m_in)
-            pad_targets(targets, self._m_in, *raw)
-            _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images,
-                                         out_targets=(st.tb, st.tl, st.nv), table=table)
-        else:
-            st.reserve(targets)
-            raw = self.aug.raw_targets(st.M)
-            pad_targets(targets, st.M, *raw)
-            _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images,
-                                         out_targets=(st.tb, st.tl, st.nv))
+            self._m_in = max(self._m_in, pad_capacity(max(counts, default=0)))
+        m_in = self._m_in if self.aug.mosaic_path else st.M  # the plain kernels keep the inputs' M
+        raw = self.aug.raw_targets(m_in)
+        pad_targets(targets, m_in, *raw)
+        _, _, _, _, total = self.aug(images, *raw, out_images=st.static_images, out_targets=(st.tb, st.tl, st.nv),
+                                     table=table)
         self._box_count(total, st.nb)
 
     def _box_count(self, total, out):
@@ -725,19 +771,13 @@ class TrainStep:
     def _augment_eager(self, images, targets):
         """Eager / CPU step: augment, then back to the list of dicts the eager
         criterion takes (one host read of the counts)."""
-        from .augment import targets_from_padded
-        from .criterion import pad_targets
-
-        need = max((len(t["boxes"]) for t in targets), default=0)
-        M = max(16, (need + 15) // 16 * 16)
+        M = pad_capacity(_most_boxes(targets))
         raw = self.aug.raw_targets(M, len(targets))  # a shorter batch (an epoch's last) uses the leading slots
         pad_targets(targets, M, *raw)
+        table, M_out = self.aug.draw(len(targets)), None
         if self.aug.mosaic_path:  # the output capacity from the same host bound as the graphed step's
-            table = self.aug.draw(len(targets))
-            bound = self.aug.need([len(t["boxes"]) for t in targets], table)
-            img, tb, tl, nv, total = self.aug(images, *raw, table=table, M_out=max(16, (bound + 15) // 16 * 16))
-        else:
-            img, tb, tl, nv, total = self.aug(images, *raw)
+            M_out = pad_capacity(self.aug.need([len(t["boxes"]) for t in targets], table))
+        img, tb, tl, nv, total = self.aug(images, *raw, table=table, M_out=M_out)
         nb = self._box_count(total, torch.empty_like(total))
         return img, targets_from_padded(tb, tl, nv), nb if img.is_cuda else float(nb)
 
@@ -779,47 +819,53 @@ class TrainStep:
 
     def __call__(self, images, ctx, targets, num_boxes):
         self._mark("start")
-        if self.aug is not None and self.stepper is None:
+        if self.stepper is not None:
+            return self._step_graphed(images, ctx, targets, num_boxes)
+        return self._step_eager(images, ctx, targets, num_boxes)
+
+    def _step_graphed(self, images, ctx, targets, num_boxes):
+        """The whole-step graph: refresh its static inputs, replay, optimizer."""
+        if self.aug is not None:  # the kernels write the graph's static inputs
+            self._augment_in_place(images, targets)
+            self._mark("augment")
+            loss = self.stepper(None, ctx, targets, None, in_place=True)
+        else:
+            loss = self.stepper(self._cast_in(images), ctx, targets, num_boxes)
+        self.last_losses = self.stepper.static_losses
+        self._mark("step_graph")
+        self._optimizer_step()
+        self._mark("optimizer")
+        return loss
+
+    def _step_eager(self, images, ctx, targets, num_boxes):
+        """Forward, host criterion, backward, optimizer: ``self.fn`` is the
+        graph pair (``self.runner``: its two replays), or the eager model on
+        the GPU or the CPU (there under DDP at world > 1)."""
+        if self.aug is not None:
             images, targets, num_boxes = self._augment_eager(images, targets)
             self._mark("augment")
-        if self.stepper is not None:
-            if self.aug is not None:  # the kernels write the graph's static inputs
-                self._augment_in_place(images, targets)
-                self._mark("augment")
-                loss = self.stepper(None, ctx, targets, None, in_place=True)
-            else:
-                loss = self.stepper(self._cast_in(images), ctx, targets, num_boxes)
-            self.last_losses = self.stepper.static_losses
-            self._mark("step_graph")
-            self._optimizer_step()
-            self._mark("optimizer")
-            return loss
-        if self.runner is None and self._pending == 0:  # (CPU, inside a cycle: autograd accumulates in .grad)
+        autograd_grads = self.runner is None  # the graph pair's gradients land in its static buffers
+        if autograd_grads and self._pending == 0:  # (CPU, inside a cycle: autograd accumulates in .grad)
             for p in self.params:
                 p.grad = None
         dn_pack = None
         if self.dn is not None:  # as GraphedStep, without static buffers
-            from .criterion import pad_targets
-            from .denoising import dn_shapes
-
-            need = max((len(t["boxes"]) for t in targets), default=0)
-            M = max(16, (need + 15) // 16 * 16)
+            M = pad_capacity(_most_boxes(targets))
             tb, tl, nv = pad_targets(targets, M)
-            G, _ = dn_shapes(M, self.dn.num_denoising)
-            dn_pack = (*self.dn.make(tb, tl, nv, G), G)
+            dn_pack = self.dn.pack(tb, tl, nv, M)
+        inputs = (self._cast_in(images), ctx) if dn_pack is None else (self._cast_in(images), ctx, dn_pack)
         with torch.autocast(images.device.type, dtype=torch.bfloat16, enabled=self.precision == "amp"):
-            flat = self.fn(self._cast_in(images), ctx) if dn_pack is None else \
-                self.fn(self._cast_in(images), ctx, dn_pack)
+            flat = self.fn(*inputs)
         self._mark("forward")
         out, aux = FlatOutputs.unflatten(flat, 0 if dn_pack is None else self.dn.num_layers)
         losses = self.criterion(out, targets, num_boxes)
         if dn_pack is not None:
-            losses.update(self.criterion.dn_losses(out["dn_outputs"], tb, tl, nv, num_boxes, G,
+            losses.update(self.criterion.dn_losses(out["dn_outputs"], tb, tl, nv, num_boxes, dn_pack[2],
                                                    fused=None if _FUSED_CRIT else False))
         self.last_losses = {k: v.detach() for k, v in losses.items()}
         loss = sum(losses.values()) + aux
         self._mark("criterion")
-        if self.ddp is None and self.runner is None and images.is_cuda:
+        if autograd_grads and self.ddp is None and images.is_cuda:
             # dense weight gradients batched after the backward (DDP's reducer
             # needs every gradient during the backward, so not under DDP)
             with deferred_weight_grads() as deferred:
@@ -860,44 +906,53 @@ class TrainStep:
         return list(self.opt.lrs) if self.opt_params is None else [g["lr"] for g in self.opt.param_groups]
 
     def _optimizer_step(self):
+        """One micro-step done: the optimizer runs on the last one of a cycle."""
         self.micro_steps += 1
-        if self.opt_params is None:  # GPU: FlatAdamW / ShardedDPAdamW (reduction + clip inside)
-            # with a weight average, ModelEMA.update runs the optimizer step with this update's decay
-            opt_step = self.opt.step if self.ema is None else self.ema.update
-            if self.accumulate <= 1 and (self.acc is None or self.acc.count == 0):
-                if self.reducer is not None:
-                    opt_step(self._allreduce_grads(), inv_world=1.0 / self.world)
-                else:
-                    opt_step()
-                self.opt_steps += 1
-                return
-            # accumulation: this micro-step's gradients into the fp32 sum; on the last one of the
-            # cycle the exchange + clip + AdamW once, on the mean over micro-steps and ranks
-            acc = self._accumulator()
-            acc.add([p.grad for p in self.opt.params])
-            if acc.count < self.accumulate:
-                return
-            grads, count = acc.take()
-            if self.reducer is not None:
-                grads = self._allreduce_grads(grads)
-            opt_step(grads, inv_world=1.0 / (self.world * count))
-            self.opt_steps += 1
+        if self.opt_params is None:
+            self._optimizer_step_gpu()
         else:
-            self._pending += 1
-            if self._pending < self.accumulate:
-                return
-            if self._pending > 1:  # autograd summed the cycle's backward passes: the mean
-                with torch.no_grad():
-                    for p in self.opt_params:
-                        if p.grad is not None:
-                            p.grad.div_(self._pending)
-            self._pending = 0
-            if self.clip_norm > 0:
-                clip_grad_norm_sharded(self.dp_params, self.ep_params, self.clip_norm, self.ep_group)
-            self.opt.step()
-            if self.ema is not None:
-                self.ema.update()
+            self._optimizer_step_cpu()
+
+    def _optimizer_step_gpu(self):
+        """FlatAdamW / ShardedDPAdamW (reduction + clip inside)."""
+        # with a weight average, ModelEMA.update runs the optimizer step with this update's decay
+        opt_step = self.opt.step if self.ema is None else self.ema.update
+        if self.accumulate <= 1 and (self.acc is None or self.acc.count == 0):
+            if self.reducer is not None:
+                opt_step(self._allreduce_grads(), inv_world=1.0 / self.world)
+            else:
+                opt_step()
             self.opt_steps += 1
+            return
+        # accumulation: this micro-step's gradients into the fp32 sum; on the last one of the
+        # cycle the exchange + clip + AdamW once, on the mean over micro-steps and ranks
+        acc = self._accumulator()
+        acc.add([p.grad for p in self.opt.params])
+        if acc.count < self.accumulate:
+            return
+        grads, count = acc.take()
+        if self.reducer is not None:
+            grads = self._allreduce_grads(grads)
+        opt_step(grads, inv_world=1.0 / (self.world * count))
+        self.opt_steps += 1
+
+    def _optimizer_step_cpu(self):
+        """torch.optim.AdamW on the gradients autograd summed in ``.grad``."""
+        self._pending += 1
+        if self._pending < self.accumulate:
+            return
+        if self._pending > 1:  # autograd summed the cycle's backward passes: the mean
+            with torch.no_grad():
+                for p in self.opt_params:
+                    if p.grad is not None:
+                        p.grad.div_(self._pending)
+        self._pending = 0
+        if self.clip_norm > 0:
+            clip_grad_norm_sharded(self.dp_params, self.ep_params, self.clip_norm, self.ep_group)
+        self.opt.step()
+        if self.ema is not None:
+            self.ema.update()
+        self.opt_steps += 1
 
     def phase_summary(self):
         """{phase: (gpu ms, host ms)} averaged over the marked steps (syncs)."""
