@@ -1011,6 +1011,52 @@ int rtdetr_frame_shift(const float* images, int F, int out_h, int out_w, int pad
                        uint8_t* work_grey, uint8_t* work_coarse, int32_t* sums, int work_images, int32_t* out_shift,
                        int32_t* out_info, hipStream_t stream);
 
+/* Tracking evaluation (moteval.evaluate, engine.track(..., gt=...)): the
+ * CLEAR-MOT counts and the identity table of a tracker's rows against ground
+ * truth, moteval.mot_reference on the host bit for bit (the rule:
+ * src/rtdetr_moe/moteval.py).  One launch per batch of frames, one 64-lane
+ * workgroup per state slot; a slot's frames are walked in ascending frame index
+ * inside its workgroup (a frame's matching prefers the pairs of the frame
+ * before: the kernel is latency bound by construction, parallel across
+ * sequences and across the solver's column scans).  frame_slot / frame_reset
+ * int32 [F] as rtdetr_track_update's: the slot a frame belongs to (outside
+ * [0, S): the frame is skipped), non-zero clears the slot before that frame.
+ * Inputs, the host having mapped raw ids to dense indices per sequence:
+ *   gt_boxes  fp32  [F][M][4] xyxy (16-byte aligned), gt_idx int32 [F][M] in
+ *             [0, NG), gt_flag int32 [F][M] (non-zero scored, 0 ignore region),
+ *             n_gt int32 [F] (clamped into [0, M])
+ *   trk_boxes fp32  [F][K][4] xyxy (16-byte aligned), trk_idx int32 [F][K] in
+ *             [0, NT), n_trk int32 [F] (clamped into [0, K])
+ * An index may appear once per frame and side (the caller checks); coordinates
+ * finite.  State, owned by the caller (moteval.MotEvalState), updated in place:
+ *   prev_step int32 [S][NG]     this frame's match of g, else -1 / -2 (a new slot: -1)
+ *   last_ever int32 [S][NG]     the last tracker index g was matched to, else -1
+ *   per_gt    int32 [S][NG][3]  frames present, frames matched, frag
+ *   counts    int64 [S][8]      TP, FN, FP, IDSW, removed, frames, 0, 0
+ *   motp_sum  fp64  [S]         the matched pairs' iou, added in frame then row order
+ *   pmc       int32 [S][NG][NT] frames in which g and t overlap at iou >= thr
+ *   gt_count  int32 [S][NG]     trk_count int32 [S][NT]
+ *   status    int32 [1]         set non-zero, never cleared: 1 / 2 the solver
+ *             refused a problem (cannot happen with finite boxes), 4 an index
+ *             outside its range (that frame is left out)
+ * Per frame: iou as rtdetr_track_update's step 3; with a flag-0 row, the
+ * assignment of all tracker rows x all ground-truth rows at cost iou >= thr ?
+ * -iou : 0 removes the tracker rows assigned to a flag-0 row at iou >= thr;
+ * the assignment of the rest at cost -(iou, 1000 + iou where prev_step[g] == t,
+ * 0 where iou < thr) gives the matches (score > 0).  Both are scipy 1.15's
+ * linear_sum_assignment, ties included, the side with more rows first, tracker
+ * rows on a tie, evaluated from the boxes in LDS.  No atomics on the state, no
+ * workspace.
+ * Limits: 1 <= M <= 256, 1 <= K <= 1024, 1 <= NG <= 1024, 1 <= NT <= 4096, F <=
+ * 1024, S <= 1024, thr in (0, 1]; 63.8 KiB of LDS at the largest.  A bad
+ * argument returns non-zero before any launch.  F == 0 returns 0 without a
+ * launch.  Profiled and counted under MOE_PROF_EVAL. */
+int rtdetr_mot_eval(const float* gt_boxes, const int32_t* gt_idx, const int32_t* gt_flag, const int32_t* n_gt,
+                    const float* trk_boxes, const int32_t* trk_idx, const int32_t* n_trk, const int32_t* frame_slot,
+                    const int32_t* frame_reset, int F, int M, int K, int S, int NG, int NT, float thr,
+                    int32_t* prev_step, int32_t* last_ever, int32_t* per_gt, int64_t* counts, double* motp_sum,
+                    int32_t* pmc, int32_t* gt_count, int32_t* trk_count, int32_t* status, hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -1377,7 +1423,7 @@ enum moe_prof_kind {
   MOE_PROF_CONV = 13,     /* implicit-GEMM convolutions (rtdetr_conv_*) */
   MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
   MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
-  MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match) */
+  MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match[_bands]), tracks scored (rtdetr_mot_eval) */
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
   MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */

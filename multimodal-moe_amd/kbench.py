@@ -15,6 +15,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
   python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
   python multimodal-moe_amd/kbench.py --frame-shift the camera-motion estimator against the host and a forward replay
+  python multimodal-moe_amd/kbench.py --mot-eval    the tracking evaluator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -963,6 +964,167 @@ def frame_shift_leg(reps, rounds):
     print(json.dumps(line), flush=True)
 
 
+def mot_sequence(seed, F, n_gt, n_trk):
+    """A sequence for the tracking evaluator with dense indices: n_gt
+    constant-velocity pedestrians, every one a ground-truth row in every frame;
+    tracker index t < n_gt follows one of them with 2 px of jitter per side
+    (every 40 frames or so two tracker indices swap their objects: identity
+    switches), the other n_trk - n_gt rows are random false positives.  -> the
+    frames as moteval.mot_reference takes them."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    i = np.arange(n_gt)
+    wh = np.stack([rng.uniform(30, 50, n_gt), rng.uniform(80, 120, n_gt)], 1)
+    xy0 = np.stack([40.0 + (i % 10) * 110.0, 60.0 + (i // 10) * 150.0], 1)
+    v = np.stack([rng.uniform(-0.8, 0.8, n_gt), rng.uniform(-0.3, 0.3, n_gt)], 1)
+    follows = np.arange(n_gt)
+    gi, ti, flags = np.arange(n_gt, dtype=np.int32), np.arange(n_trk, dtype=np.int32), np.ones(n_gt, np.int32)
+    frames = []
+    for f in range(F):
+        if rng.random() < 1 / 40:
+            a, b = rng.choice(n_gt, 2, replace=False)
+            follows[a], follows[b] = follows[b], follows[a]
+        xy = xy0 + v * f
+        gb = np.concatenate([xy, xy + wh], 1).astype(np.float32)
+        fx, fy = rng.uniform(0, 1188, n_trk - n_gt), rng.uniform(0, 574, n_trk - n_gt)
+        tb = np.concatenate([gb[follows] + rng.normal(0, 2.0, (n_gt, 4)), np.stack([fx, fy, fx + 40, fy + 100], 1)])
+        frames.append((gb, gi, flags, tb.astype(np.float32), ti))
+    return frames
+
+
+def mot_eval_leg(reps, rounds):
+    """rtdetr_mot_eval at about MOT17's training split (8 sequences of 600
+    frames, 30 truths and 35 tracker rows a frame) against moteval.mot_reference
+    on the host, same process, same rows (every state array checked equal
+    first, bit for bit).  The 4800 frames are 5 launches (moteval.pack_chunks:
+    128 frames of each sequence a launch, one 64-lane workgroup per sequence --
+    the kernel is latency bound by construction: the frames of a sequence are
+    serial).  kernel_us: the 5 launches' dispatch-stamped execution time;
+    device_path_ms: new state, the launches, the state copied back and
+    mot_metrics, wall clock, the rows already on the device; host_ms: the
+    reference loop over the 4800 frames and mot_metrics, wall clock.
+    forward_replay_us: one EvalForward graph replay at batch 16
+    (rtdetr-r50-moe8-top2, 704 x 1248).  Median, min and max over the rounds,
+    the sides interleaved in each round.
+    Also, on the synthetic pedestrians of --track seen through the camera pan of
+    --frame-shift (every box of frame f moved by the pan's position; the
+    tracker's shift is the pan's step, which --frame-shift checks the estimator
+    finds): MOTA, IDF1 and IDSW of track.track_reference's output against the
+    clean boxes, with cmc off and on.  Synthetic input: no accuracy claim beyond
+    it."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import engine, moteval
+    from src.rtdetr_moe.model import RTDETRMoE
+    from src.rtdetr_moe.track import TrackArgs, new_state, track_reference
+
+    S, F, n_gt, n_trk, thr = 8, 600, 30, 35, 0.5
+    seqs = [{"NG": n_gt, "NT": n_trk, "frames": mot_sequence(s, F, n_gt, n_trk)} for s in range(S)]
+    chunks, M, K = moteval.pack_chunks(seqs)
+    dev_chunks = [{k: torch.from_numpy(v).cuda() for k, v in c.items()} for c in chunks]
+    order = ("gt_boxes", "gt_idx", "gt_flag", "n_gt", "trk_boxes", "trk_idx", "n_trk", "frame_slot", "frame_reset")
+    made = []
+
+    def kernel():
+        st = moteval.MotEvalState(S, n_gt, n_trk, "cuda")  # torch fills: not among the library's profiled launches
+        for c in dev_chunks:
+            L.mot_eval(st, *(c[k] for k in order), thr)
+        made[:] = [st]
+
+    def device_path():
+        kernel()
+        L.mot_eval_check(made[0])
+        return [moteval.mot_metrics(made[0].export(s)) for s in range(S)]
+
+    def host_path():
+        return [moteval.mot_metrics(st) for st in moteval.run_reference(seqs, thr)]
+
+    want = moteval.run_reference(seqs, thr)
+    kernel()
+    L.mot_eval_check(made[0])
+    for s in range(S):
+        if not moteval.states_equal(made[0].export(s), want[s]):
+            raise SystemExit(f"mot_eval's state differs from mot_reference's (sequence {s})")
+    combined = moteval.combine(device_path())
+
+    # the pan: --track's pedestrians through --frame-shift's camera
+    Fp, Kp, n_obj = 32, 300, 40
+    boxes, scores, labels, n_valid, _ = track_sequence(n_obj, Fp, Kp)
+    rng = np.random.default_rng(0)  # track_sequence's first draws: the objects' clean boxes
+    i = np.arange(n_obj)
+    w, h = rng.uniform(30, 50, n_obj), rng.uniform(80, 120, n_obj)
+    x0, y0 = 40.0 + (i % 10) * 110.0, 60.0 + (i // 10) * 150.0
+    vx, vy = rng.uniform(-0.8, 0.8, n_obj), rng.uniform(-0.3, 0.3, n_obj)
+    steps = np.random.default_rng(0).integers(-45, 46, (Fp, 2))
+    steps[::5] = 0
+    pos = np.clip(np.cumsum(steps, 0), -64, 64).astype(np.float32)
+    shift = np.diff(pos, axis=0, prepend=pos[:1])
+    pan = {}
+    for cmc in (False, True):
+        st, ev = new_state(TrackArgs().max_tracks), moteval.new_state(n_obj, 4096)
+        for f in range(Fp):
+            move = np.tile(pos[f], 2)
+            oid, obox, _ = track_reference(st, boxes[f] + move, scores[f], labels[f], n_valid[f], TrackArgs(),
+                                           shift=shift[f] if cmc else None)
+            rows = np.nonzero(oid >= 0)[0]
+            truth = np.stack([x0 + vx * f, y0 + vy * f, x0 + vx * f + w, y0 + vy * f + h], 1) + move
+            moteval.mot_reference(ev, (truth.astype(np.float32), i, np.ones(n_obj, np.int32)),
+                                  (obox[rows], oid[rows] - 1), thr)
+        m = moteval.mot_metrics(ev)
+        pan["cmc_on" if cmc else "cmc_off"] = {"MOTA": round(m["MOTA"], 4), "IDF1": round(m["IDF1"], 4),
+                                               "IDSW": m["IDSW"], "FN": m["FN"], "FP": m["FP"]}
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    def wall(fn, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return statistics.median(ts)
+
+    res = {"kernel_us": [], "device_path_ms": [], "host_ms": [], "forward_replay_us": []}
+    for _ in range(rounds):
+        res["kernel_us"].append(timed(kernel, max(3, reps // 10)))
+        res["device_path_ms"].append(wall(device_path, 3))
+        res["host_ms"].append(wall(host_path, 1))
+        res["forward_replay_us"].append(replay_us())
+    line = {"kernel": "rtdetr_mot_eval", "shape": f"S{S} F{F} M{M} K{K} NG{n_gt} NT{n_trk}", "launches": len(chunks),
+            "combined": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in combined.items()
+                         if k in ("MOTA", "MOTP", "IDF1", "IDSW", "TP", "FN", "FP", "Frag")},
+            "pan_32_frames": pan}
+    for k, v in res.items():
+        line[k] = round(statistics.median(v), 3)
+        line[k + "_min"] = round(min(v), 3)
+        line[k + "_max"] = round(max(v), 3)
+    line["host_over_kernel"] = round(1e3 * line["host_ms"] / line["kernel_us"], 1)
+    line["host_over_device_path"] = round(line["host_ms"] / line["device_path_ms"], 1)
+    line["kernel_over_forward"] = round(line["kernel_us"] / line["forward_replay_us"], 3)
+    print(json.dumps(line), flush=True)
+
+
 def grad_accum_leg(reps, rounds):
     """train_grad_accum over C2's parameter list (rtdetr-r50-moe8-top2, GEMM /
     convolution operands in bf16 as in the training step): us per launch
@@ -1029,6 +1191,10 @@ def main():
     ap.add_argument("--frame-shift", action="store_true",
                     help="check rtdetr_frame_shift against motion.sequence_shifts, then time it against the host and "
                          "a forward replay, and exit")
+    ap.add_argument("--mot-eval", action="store_true",
+                    help="check rtdetr_mot_eval against moteval.mot_reference (8 sequences of 600 frames), time it "
+                         "against the host reference and a forward replay, print MOTA / IDF1 / IDSW on the synthetic "
+                         "pan with cmc off and on, and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -1077,6 +1243,9 @@ def main():
         return
     if a.frame_shift:
         frame_shift_leg(a.reps, a.rounds)
+        return
+    if a.mot_eval:
+        mot_eval_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

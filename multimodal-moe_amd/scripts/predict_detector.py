@@ -62,7 +62,17 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--cmc-rows", type=str, default=None,
                     help="--cmc: T,B the fractions of the height the estimator looks at, e.g. 0,0.8 to leave the "
                          "bonnet out (default 0,1)")
+    ap.add_argument("--gt", type=str, default=None,
+                    help="--track: a directory of MOTChallenge ground truth (<key>/gt/gt.txt or <key>.txt per "
+                         "sequence); the tracks are scored against it (mot_metrics.json)")
+    ap.add_argument("--gt-classes", type=str, default=None,
+                    help="--gt: the classes scored, e.g. 1 (default: all)")
+    ap.add_argument("--gt-ignore-classes", type=str, default="",
+                    help="--gt: the classes that are ignore regions, e.g. 2,7,8,12")
+    ap.add_argument("--eval-iou", type=float, default=0.5, help="--gt: the IoU a match needs")
     a = ap.parse_args(argv)
+    if a.gt is not None and not a.track:
+        ap.error("--gt needs --track")
     if a.tracker is not None and not a.track:
         ap.error("--tracker needs --track")
     given = a.cmc_radius is not None or a.cmc_gate is not None or a.cmc_rows is not None
@@ -89,6 +99,26 @@ def tracker_args(a):
     return t or True
 
 
+def int_list(text) -> list:
+    return [int(v) for v in text.split(",") if v.strip()]
+
+
+def gt_args(a) -> dict:
+    """engine.predict's ground-truth arguments from the command line; nothing without --gt."""
+    if a.gt is None:
+        return {}
+    return dict(gt=a.gt, gt_classes=int_list(a.gt_classes) if a.gt_classes else None,
+                gt_ignore_classes=int_list(a.gt_ignore_classes), eval_iou=a.eval_iou)
+
+
+def print_mot(mot) -> None:
+    """One line per sequence and the combined row."""
+    cols = ("MOTA", "MOTP", "IDF1", "IDP", "IDR", "Recall", "Precision")
+    ints = ("TP", "FN", "FP", "IDSW", "Frag", "MT", "PT", "ML", "GT", "removed", "frames")
+    for key, m in mot.items():
+        print(f"{key}: " + " ".join(f"{c} {m[c]:.4f}" for c in cols) + " " + " ".join(f"{c} {m[c]}" for c in ints))
+
+
 def main(argv=None) -> None:
     a = parse_args(argv)
     from src.rtdetr_moe import engine
@@ -98,7 +128,7 @@ def main(argv=None) -> None:
                          name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
                          tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
                          class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou,
-                         track=tracker_args(a))
+                         track=tracker_args(a), **gt_args(a))
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
     if a.track:
@@ -107,6 +137,9 @@ def main(argv=None) -> None:
         print(f"Saved tracks -> {res.save_dir / 'tracks.json'}, {res.save_dir / 'mot'}")
         if a.cmc:
             print(f"Saved camera shifts -> {res.save_dir / 'camera_motion.json'}")
+        if res.mot is not None:
+            print_mot(res.mot)
+            print(f"Saved tracking metrics -> {res.save_dir / 'mot_metrics.json'}")
     print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))
     print(f"Saved predictions -> {res.save_dir / 'predictions.json'}")
 

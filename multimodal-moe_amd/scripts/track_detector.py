@@ -6,6 +6,11 @@ tracks.json (the COCO rows plus track_id and sequence) and mot/<sequence>.txt
 (frame,id,x,y,w,h,score,-1,-1,-1) under RUNS_DIR/rtdetr/<run-name>_predict.
 --cmc (with --cmc-radius, --cmc-gate, --cmc-rows T,B) turns on camera-motion
 compensation and adds camera_motion.json.
+--gt DIR (with --gt-classes 1 --gt-ignore-classes 2,7,8,12 --eval-iou 0.5)
+scores the tracks against MOTChallenge ground truth (DIR/<sequence>/gt/gt.txt or
+DIR/<sequence>.txt): MOTA, MOTP, IDF1 and the counts per sequence and combined,
+printed and written to mot_metrics.json; scripts/eval_tracks.py scores the
+written mot/ directory again later, without a model.
 """
 from __future__ import annotations
 

@@ -126,6 +126,8 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rtdetr_frame_shift": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P,
                                 _P]),
+    "rtdetr_mot_eval": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P,
+                             _P, _P, _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -302,20 +304,24 @@ def launch_counts(reset=False) -> dict:
     (host-side counts, graph capture included: moe_launch_counts).
     "eval_match_bands" -- the launches of eval_match_bands(), which the library
     counts with eval_match's -- is reported apart and taken out of "eval_match";
-    likewise "box_fuse" (box_fuse()), which the library counts under "merge"."""
-    global _eval_match_bands_launches, _box_fuse_launches
+    likewise "mot_eval" (mot_eval()), also counted with eval_match's, and
+    "box_fuse" (box_fuse()), which the library counts under "merge"."""
+    global _eval_match_bands_launches, _box_fuse_launches, _mot_eval_launches
     n = max(PROF_KINDS) + 1
     buf = (ctypes.c_longlong * n)()
     _check(lib().moe_launch_counts(ctypes.cast(buf, ctypes.c_void_p), n), "moe_launch_counts")
     out = {PROF_KINDS[i]: int(buf[i]) for i in range(n)}
     out["eval_match_bands"] = min(_eval_match_bands_launches, out["eval_match"])
     out["eval_match"] -= out["eval_match_bands"]
+    out["mot_eval"] = min(_mot_eval_launches, out["eval_match"])
+    out["eval_match"] -= out["mot_eval"]
     out["box_fuse"] = min(_box_fuse_launches, out["merge"])
     out["merge"] -= out["box_fuse"]
     if reset:
         lib().moe_launch_counts_reset()
         _eval_match_bands_launches = 0
         _box_fuse_launches = 0
+        _mot_eval_launches = 0
     return {k: v for k, v in out.items() if v}
 
 
@@ -1151,6 +1157,65 @@ def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset,
     else:
         _check(lib().rtdetr_track_update_shift(*common, _ptr(shift), _stream()), "rtdetr_track_update_shift")
     return out
+
+
+# rtdetr_mot_eval's limits
+MOT_MAX_K, MOT_MAX_M, MOT_MAX_NG, MOT_MAX_NT, MOT_MAX_F, MOT_MAX_S = 1024, 256, 1024, 4096, 1024, 1024
+# rtdetr_mot_eval shares the library's eval_match launch counter (and profiler kind); launch_counts() reports its
+# launches, counted here, under their own name
+_mot_eval_launches = 0
+
+
+def mot_eval(state, gt_boxes, gt_idx, gt_flag, n_gt, trk_boxes, trk_idx, n_trk, frame_slot, frame_reset, thr=0.5):
+    """The tracking evaluator, one launch for the batch of frames
+    (rtdetr_mot_eval: moteval.mot_reference per frame, bit for bit).  ``state``:
+    a moteval.MotEvalState (S slots for NG ground-truth and NT tracker indices,
+    updated in place); gt_boxes fp32 [F, M, 4] xyxy, gt_idx / gt_flag int32
+    [F, M], n_gt int32 [F]; trk_boxes fp32 [F, K, 4], trk_idx int32 [F, K], n_trk
+    int32 [F]; frame_slot / frame_reset int32 [F], the tracker's tables.  The
+    launch is asynchronous; ``mot_eval_check(state)`` after the last one raises
+    if the kernel refused anything (state.status)."""
+    global _mot_eval_launches
+    _need(gt_boxes, torch.float32, "gt_boxes")
+    _need(trk_boxes, torch.float32, "trk_boxes")
+    ints = {"gt_idx": gt_idx, "gt_flag": gt_flag, "n_gt": n_gt, "trk_idx": trk_idx, "n_trk": n_trk,
+            "frame_slot": frame_slot, "frame_reset": frame_reset}
+    for name, t in ints.items():
+        _need(t, torch.int32, name)
+    if gt_boxes.dim() != 3 or gt_boxes.shape[-1] != 4 or trk_boxes.dim() != 3 or trk_boxes.shape[-1] != 4:
+        raise MoEKernelError("mot_eval: gt_boxes must be [F, M, 4] and trk_boxes [F, K, 4]")
+    F, M, _ = (int(v) for v in gt_boxes.shape)
+    K = int(trk_boxes.shape[1])
+    shapes = {"gt_idx": (F, M), "gt_flag": (F, M), "n_gt": (F,), "trk_idx": (F, K), "n_trk": (F,),
+              "frame_slot": (F,), "frame_reset": (F,)}
+    if int(trk_boxes.shape[0]) != F or any(tuple(ints[k].shape) != v for k, v in shapes.items()):
+        raise MoEKernelError(f"mot_eval: expected {shapes} and trk_boxes [{F}, K, 4]")
+    S, NG, NT = state.S, state.NG, state.NT
+    st_shapes = ((S, NG), (S, NG), (S, NG, 3), (S, 8), (S,), (S, NG, NT), (S, NG), (S, NT), (1,))
+    st_dtypes = (torch.int32, torch.int32, torch.int32, torch.int64, torch.float64, torch.int32, torch.int32,
+                 torch.int32, torch.int32)
+    st = (*state.tensors(), state.status)
+    for t, s, d in zip(st, st_shapes, st_dtypes):
+        _need(t, d, "state")
+        if tuple(t.shape) != s:
+            raise MoEKernelError(f"mot_eval: a state tensor must be {s}, got {tuple(t.shape)}")
+    dev = gt_boxes.device
+    if any(t.device != dev for t in (trk_boxes, *ints.values(), *st)):
+        raise MoEKernelError("mot_eval: all tensors must be on one device")
+    rc = lib().rtdetr_mot_eval(_ptr(gt_boxes), _ptr(gt_idx), _ptr(gt_flag), _ptr(n_gt), _ptr(trk_boxes), _ptr(trk_idx),
+                               _ptr(n_trk), _ptr(frame_slot), _ptr(frame_reset), F, M, K, S, NG, NT, float(thr),
+                               *(_ptr(t) for t in st), _stream())
+    _check(rc, "rtdetr_mot_eval")
+    if F > 0:
+        _mot_eval_launches += 1
+
+
+def mot_eval_check(state) -> None:
+    """Raise if any launch on ``state`` set the status word (waits for them)."""
+    code = int(state.status.item())
+    if code:
+        raise MoEKernelError(f"rtdetr_mot_eval: status {code} (1 / 2: the solver refused a problem -- non-finite "
+                             "boxes --, 4: an index outside [0, NG) / [0, NT))")
 
 
 def frame_shift(state, images, out_hw, frame_slot, frame_reset, radius=48, gate=0.1, rows=(0.0, 1.0), out=None):

@@ -71,6 +71,8 @@ class PredictResults:
     speed: dict
     save_dir: Path | None
     model: ModelHandle | None
+    # track with gt=...: moteval.evaluate's {sequence file key: metrics, "COMBINED": metrics}; None otherwise
+    mot: dict | None = None
 
 
 def _image_id(path):
@@ -484,9 +486,28 @@ def _prediction(path, size, ctx, row, k=None, fused=False, **tracked) -> Predict
                       members=row[:, MEMBERS].to(torch.int64) if fused else None, **tracked)
 
 
-def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False):
-    """predictions.json, with a tracker tracks.json and mot/<sequence>.txt (with cmc camera_motion.json), and the
-    overlays."""
+def _score_tracks(preds, truth, eval_iou, dev) -> dict:
+    """moteval.evaluate of exactly the rows mot/<sequence>.txt holds: mot_lines' text, parsed back."""
+    from . import moteval
+
+    texts = {key.replace("/", "_"): text for key, text in mot_lines(preds).items()}
+    return moteval.evaluate({k: truth[k] for k in texts}, texts, thr=eval_iou, device=dev)
+
+
+def _load_truth(gt, seq_of, gt_classes, gt_ignore_classes) -> dict:
+    """The ground truth of the run's sequences (moteval.load_gt), by the key their mot/ files use."""
+    from . import moteval
+
+    keys = list(dict.fromkeys(key for key, _, _ in seq_of))
+    files = [k.replace("/", "_") for k in keys]
+    if len(set(files)) != len(files):
+        raise ValueError(f"two sequences share one file key once '/' is '_': {sorted(keys)}")
+    return moteval.load_gt(gt, files, gt_classes, gt_ignore_classes)
+
+
+def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False, mot=None):
+    """predictions.json, with a tracker tracks.json and mot/<sequence>.txt (with cmc camera_motion.json, with gt
+    mot_metrics.json), and the overlays."""
     save_dir.mkdir(parents=True, exist_ok=True)
     if save_json:
         (save_dir / "predictions.json").write_text(json.dumps(coco_results(preds)))
@@ -497,6 +518,8 @@ def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False):
             (save_dir / "mot" / (key.replace("/", "_") + ".txt")).write_text(text)
         if cmc:
             (save_dir / "camera_motion.json").write_text(json.dumps(camera_motion(preds)))
+        if mot is not None:
+            (save_dir / "mot_metrics.json").write_text(json.dumps(mot))
     if save_img:
         for p in preds:
             _save_overlay(p, save_dir / Path(p.path).name)
@@ -506,7 +529,7 @@ def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False):
 def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
             workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
             merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55, track=None,
-            sequence_of=None) -> PredictResults:
+            sequence_of=None, gt=None, gt_classes=None, gt_ignore_classes=(), eval_iou=0.5) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -593,11 +616,32 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     fusion are unaffected.  ``Prediction.camera_shift`` (dx, dy in source
     pixels) and ``.camera_status`` are set, and camera_motion.json ({sequence:
     [[frame, dx, dy, status], ...]}) is written beside tracks.json.  Without
-    ``cmc`` nothing of this runs."""
+    ``cmc`` nothing of this runs.
+    ``gt`` (with ``track``; without it a ValueError): a directory of
+    MOTChallenge ground truth, ``<gt>/<key>/gt/gt.txt`` or ``<gt>/<key>.txt``
+    per sequence, the key the one mot/<key>.txt uses (the sequence's with '/'
+    replaced by '_'); moteval.load_gt reads it before any frame is decoded, with
+    ``gt_classes`` (None: all) scored and ``gt_ignore_classes`` as ignore
+    regions.  After the run the tracks are scored against it (moteval.py's
+    rule: CLEAR-MOT and identity metrics at IoU ``eval_iou``): exactly the rows
+    of mot_lines(predictions), parsed back from their text, so that scoring the
+    written mot/ directory later (scripts/eval_tracks.py) gives the same
+    numbers.  On a GPU every chunk of at most 1024 frames is ONE HIP launch
+    (rtdetr_mot_eval); the CPU device or MOE_TRACK_EVAL=0 run
+    moteval.mot_reference and give the same result.  It goes into
+    ``PredictResults.mot`` ({key: metrics, "COMBINED": metrics}) and into
+    mot_metrics.json beside tracks.json.  Without ``gt`` nothing of this
+    runs."""
     # engine imports this module, and tests replace engine.EvalForward and preprocess.FrameSource: looked up per call
     from . import engine, preprocess
 
     targs, tiles, fuse = _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track)
+    if gt is not None:
+        from .moteval import check_thr
+
+        if targs is None:
+            raise ValueError("gt scores tracks: give track=... as well")
+        eval_iou = check_thr(eval_iou)
     devices = engine.parse_device(device)
     dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
     on_gpu = dev.type == "cuda"
@@ -621,6 +665,7 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     if targs is not None:  # on the device unless the merge left the candidates on the host
         tracker = _Tracker(targs, ds.paths, sequence_of, batch, max_det, dev,
                            predict_track_on_gpu(dev) and (tiles is None or gpu_merge), out_hw)
+    truth = _load_truth(gt, tracker.seq_of, gt_classes, gt_ignore_classes) if gt is not None else None
     gpu_track = tracker is not None and tracker.on_device
     cmc = tracker is not None and tracker.cmc
     if tiles is None:
@@ -674,10 +719,11 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     speed = {key: 1e3 * t / max(len(preds), 1) for key, t in clock.items()}
     if tiles is not None:
         speed["passes"] = 1 + n_tiles
+    mot = _score_tracks(preds, truth, eval_iou, dev) if truth is not None else None
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
-        _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc)
-    return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=engine.ModelHandle(model))
+        _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc, mot)
+    return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=engine.ModelHandle(model), mot=mot)
 
 
 def track(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.1, tracker=None, **kw) -> PredictResults:

@@ -3,7 +3,8 @@ that links a sequence's detections from frame to frame, stated once.
 
 * ``TrackArgs``: the tracker's arguments.  The defaults are ByteTrack's where it
   has them (track_high, track_low, new_thr, max_age) and are NOT tuned here:
-  this tree has no trained weights and no sequence ground truth.
+  this tree has no trained weights and no sequence ground truth (with ground
+  truth of your own, engine.track(..., gt=...) scores a run: moteval.py).
 * ``track_reference``: one frame of one sequence, plain numpy.  The HIP kernel
   rtdetr_track_update / rtdetr_track_update_shift (_lib.track_update) takes the
   same decisions and computes

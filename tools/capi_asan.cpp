@@ -176,6 +176,30 @@ int main() {
     std::printf("FAIL box_fuse B=0 must succeed\n");
     ++g_fail;
   }
+  auto* c64 = reinterpret_cast<int64_t*>(buf);
+  auto* d64 = reinterpret_cast<double*>(buf);
+  // F, M, K, S, NG, NT, thr, then one operand replaced
+  auto mot = [&](int F, int M, int K, int S, int NG, int NT, float thr, const float* gtb, int32_t* status) {
+    return rtdetr_mot_eval(gtb, i32, i32, i32, f32, i32, i32, i32, i32, F, M, K, S, NG, NT, thr, i32, i32, i32, c64, d64,
+                           i32, i32, i32, status, s);
+  };
+  expect_error("mot_eval K=1025", mot(1, 4, 1025, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("mot_eval M=257", mot(1, 257, 4, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("mot_eval M=0", mot(1, 0, 4, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("mot_eval NG=1025", mot(1, 4, 4, 1, 1025, 8, 0.5f, f32, i32));
+  expect_error("mot_eval NT=4097", mot(1, 4, 4, 1, 8, 4097, 0.5f, f32, i32));
+  expect_error("mot_eval F=1025", mot(1025, 4, 4, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("mot_eval S=0 with frames", mot(1, 4, 4, 0, 8, 8, 0.5f, f32, i32));
+  expect_error("mot_eval thr=0", mot(1, 4, 4, 1, 8, 8, 0.f, f32, i32));
+  expect_error("mot_eval thr=NaN", mot(1, 4, 4, 1, 8, 8, __builtin_nanf(""), f32, i32));
+  expect_error("mot_eval gt_boxes=NULL", mot(1, 4, 4, 1, 8, 8, 0.5f, nullptr, i32));
+  expect_error("mot_eval gt_boxes misaligned", mot(1, 4, 4, 1, 8, 8, 0.5f, f32 + 1, i32));
+  expect_error("mot_eval status=NULL", mot(1, 4, 4, 1, 8, 8, 0.5f, f32, nullptr));
+  ++g_n;
+  if (mot(0, 4, 4, 0, 8, 8, 0.5f, nullptr, nullptr) != 0) {  // F == 0: success, no launch
+    std::printf("FAIL mot_eval F=0 must succeed\n");
+    ++g_fail;
+  }
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
