@@ -1057,6 +1057,51 @@ int rtdetr_mot_eval(const float* gt_boxes, const int32_t* gt_idx, const int32_t*
                     int32_t* prev_step, int32_t* last_ever, int32_t* per_gt, int64_t* counts, double* motp_sum,
                     int32_t* pmc, int32_t* gt_count, int32_t* trk_count, int32_t* status, hipStream_t stream);
 
+/* HOTA (moteval.evaluate(..., hota=True)): hota.py's hota_pass_a / hota_gas /
+ * hota_pass_b on the host bit for bit (the rule: src/rtdetr_moe/hota.py).
+ * HOTA's matching of a frame depends on a score table global to the sequence,
+ * not on the frame before, so passes A and B run ONE 64-lane WORKGROUP PER
+ * FRAME (grid = F) over all frames of all sequences of the launch, in any
+ * order and split over any number of launches; frame_slot int32 [F] names the
+ * state slot of a frame (outside [0, S): the frame is skipped).  Every pass A
+ * launch of a slot must finish before rtdetr_hota_gas, and that before any pass
+ * B launch (stream order does it).  Inputs as rtdetr_mot_eval's (gt_boxes,
+ * gt_idx, gt_flag, n_gt, trk_boxes, trk_idx, n_trk).  State, owned by the
+ * caller (hota.HotaEvalState), zeroed before the first launch, updated in place
+ * with integer atomics only:
+ *   pot_q     int64 [S][NG][NT]     sum over frames of rint(sim_iou * 2^32)
+ *   gt_count  int32 [S][NG]         trk_count int32 [S][NT]   (pass A counts them itself)
+ *   gas       fp32  [S][NG][NT]     pot_q / (2^32 (gt_count + trk_count) - pot_q): fp64, rounded once
+ *   counts    int64 [S][3][19]      TP, FN, FP per threshold
+ *   mc        int32 [S][19][NG][NT] counted pairs per threshold
+ *   status    int32 [1]             as rtdetr_mot_eval's (4: an index outside its range, that frame is left out)
+ * Workspaces: keep uint8 [F][K], written by pass A (1: the tracker row remains
+ * after the ignore-region removal) and read by pass B of the same frames;
+ * loc_part fp64 [F][19], every element written by pass B: the frame's sum of
+ * its counted pairs' iou per threshold in ground-truth row order (0 for a
+ * skipped frame) -- the caller adds a sequence's partials in frame order; no
+ * floating-point atomic is used.  alpha: the 19 thresholds, fp64, device memory
+ * (np.arange(0.05, 0.99, 0.05) - eps, computed once on the host).
+ * Limits: 1 <= M <= 256, 1 <= K <= 1024, F <= 65536, S <= 1024, thr in (0, 1],
+ * and the table budget S * NG * NT <= 2^21 cells (mc 152 MiB, pot_q 16 MiB, gas
+ * 8 MiB at the bound): the caller processes sequences in groups under it and
+ * scores a single sequence over it on the host.  LDS at the largest: pass A
+ * 60.8 KiB, pass B 62.8 KiB.  A bad argument returns non-zero before any
+ * launch.  F == 0 (S == 0 for _gas) returns 0 without a launch.  Profiled and
+ * counted under MOE_PROF_EVAL. */
+int rtdetr_hota_pass_a(const float* gt_boxes, const int32_t* gt_idx, const int32_t* gt_flag, const int32_t* n_gt,
+                       const float* trk_boxes, const int32_t* trk_idx, const int32_t* n_trk,
+                       const int32_t* frame_slot, int F, int M, int K, int S, int NG, int NT, float thr,
+                       int64_t* pot_q, int32_t* gt_count, int32_t* trk_count, uint8_t* keep, int32_t* status,
+                       hipStream_t stream);
+int rtdetr_hota_gas(const int64_t* pot_q, const int32_t* gt_count, const int32_t* trk_count, int S, int NG, int NT,
+                    float* gas, hipStream_t stream);
+int rtdetr_hota_pass_b(const float* gt_boxes, const int32_t* gt_idx, const int32_t* gt_flag, const int32_t* n_gt,
+                       const float* trk_boxes, const int32_t* trk_idx, const int32_t* n_trk,
+                       const int32_t* frame_slot, const uint8_t* keep, int F, int M, int K, int S, int NG, int NT,
+                       const float* gas, const double* alpha, int64_t* counts, int32_t* mc, double* loc_part,
+                       int32_t* status, hipStream_t stream);
+
 /* RT-DETR set criterion fused (SetCriterion.loss_padded): S prediction sets,
  * B images, Q queries, C classes, M padded targets (first n_valid[b] real);
  * logits fp32 [S,B,Q,C], boxes fp32 [S,B,Q,4] cxcywh, tgt_boxes fp32 [B,M,4],
@@ -1423,7 +1468,7 @@ enum moe_prof_kind {
   MOE_PROF_CONV = 13,     /* implicit-GEMM convolutions (rtdetr_conv_*) */
   MOE_PROF_ROUTER_WGRAD = 14, /* router weight / context-bias gradients (moe_router_wgrad) */
   MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
-  MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match[_bands]), tracks scored (rtdetr_mot_eval) */
+  MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match[_bands]), tracks scored (rtdetr_mot_eval, rtdetr_hota_*) */
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
   MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */

@@ -34,7 +34,7 @@ enum ProfKind {
   PROF_CONV = 13,      // implicit-GEMM convolutions (rtdetr_conv_*)
   PROF_ROUTER_WGRAD = 14,  // router weight / context-bias gradients (moe_router_wgrad)
   PROF_AUGMENT = 15,       // training batch augmentation (train_augment_* / train_mosaic_*)
-  PROF_EVAL = 16,          // validation: detections matched to ground truth (rtdetr_eval_match[_bands]), tracks scored (rtdetr_mot_eval)
+  PROF_EVAL = 16,          // validation: detections matched to ground truth (rtdetr_eval_match[_bands]), tracks scored (rtdetr_mot_eval, rtdetr_hota_*)
   PROF_ROUTE_STATS = 17,   // validation: per-context routing statistics (moe_route_stats)
   PROF_RESIZE = 18,        // inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8)
   PROF_MERGE = 19,         // tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse)

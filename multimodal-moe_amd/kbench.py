@@ -16,6 +16,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
   python multimodal-moe_amd/kbench.py --frame-shift the camera-motion estimator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --mot-eval    the tracking evaluator against the host and a forward replay
+  python multimodal-moe_amd/kbench.py --hota        the frame-parallel HOTA kernels against the host and rtdetr_mot_eval
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
 """
 from __future__ import annotations
@@ -993,6 +994,41 @@ def mot_sequence(seed, F, n_gt, n_trk):
     return frames
 
 
+def pan_frames():
+    """The synthetic pedestrians of --track seen through the camera pan of
+    --frame-shift (every box of frame f moved by the pan's position; the
+    tracker's shift is the pan's step), tracked by track.track_reference with
+    cmc off and on -> {"cmc_off" / "cmc_on": [(truth boxes fp32, g, flags,
+    tracker boxes, t)]}, the evaluators' frames (NG 40, NT up to 4096)."""
+    import numpy as np
+
+    from src.rtdetr_moe.track import TrackArgs, new_state, track_reference
+
+    Fp, Kp, n_obj = 32, 300, 40
+    boxes, scores, labels, n_valid, _ = track_sequence(n_obj, Fp, Kp)
+    rng = np.random.default_rng(0)  # track_sequence's first draws: the objects' clean boxes
+    i = np.arange(n_obj)
+    w, h = rng.uniform(30, 50, n_obj), rng.uniform(80, 120, n_obj)
+    x0, y0 = 40.0 + (i % 10) * 110.0, 60.0 + (i // 10) * 150.0
+    vx, vy = rng.uniform(-0.8, 0.8, n_obj), rng.uniform(-0.3, 0.3, n_obj)
+    steps = np.random.default_rng(0).integers(-45, 46, (Fp, 2))
+    steps[::5] = 0
+    pos = np.clip(np.cumsum(steps, 0), -64, 64).astype(np.float32)
+    shift = np.diff(pos, axis=0, prepend=pos[:1])
+    out = {}
+    for cmc in (False, True):
+        st, frames = new_state(TrackArgs().max_tracks), []
+        for f in range(Fp):
+            move = np.tile(pos[f], 2)
+            oid, obox, _ = track_reference(st, boxes[f] + move, scores[f], labels[f], n_valid[f], TrackArgs(),
+                                           shift=shift[f] if cmc else None)
+            rows = np.nonzero(oid >= 0)[0]
+            truth = np.stack([x0 + vx * f, y0 + vy * f, x0 + vx * f + w, y0 + vy * f + h], 1) + move
+            frames.append((truth.astype(np.float32), i, np.ones(n_obj, np.int32), obox[rows], oid[rows] - 1))
+        out["cmc_on" if cmc else "cmc_off"] = frames
+    return out
+
+
 def mot_eval_leg(reps, rounds):
     """rtdetr_mot_eval at about MOT17's training split (8 sequences of 600
     frames, 30 truths and 35 tracker rows a frame) against moteval.mot_reference
@@ -1015,11 +1051,8 @@ def mot_eval_leg(reps, rounds):
     it."""
     import time
 
-    import numpy as np
-
     from src.rtdetr_moe import engine, moteval
     from src.rtdetr_moe.model import RTDETRMoE
-    from src.rtdetr_moe.track import TrackArgs, new_state, track_reference
 
     S, F, n_gt, n_trk, thr = 8, 600, 30, 35, 0.5
     seqs = [{"NG": n_gt, "NT": n_trk, "frames": mot_sequence(s, F, n_gt, n_trk)} for s in range(S)]
@@ -1050,32 +1083,14 @@ def mot_eval_leg(reps, rounds):
             raise SystemExit(f"mot_eval's state differs from mot_reference's (sequence {s})")
     combined = moteval.combine(device_path())
 
-    # the pan: --track's pedestrians through --frame-shift's camera
-    Fp, Kp, n_obj = 32, 300, 40
-    boxes, scores, labels, n_valid, _ = track_sequence(n_obj, Fp, Kp)
-    rng = np.random.default_rng(0)  # track_sequence's first draws: the objects' clean boxes
-    i = np.arange(n_obj)
-    w, h = rng.uniform(30, 50, n_obj), rng.uniform(80, 120, n_obj)
-    x0, y0 = 40.0 + (i % 10) * 110.0, 60.0 + (i // 10) * 150.0
-    vx, vy = rng.uniform(-0.8, 0.8, n_obj), rng.uniform(-0.3, 0.3, n_obj)
-    steps = np.random.default_rng(0).integers(-45, 46, (Fp, 2))
-    steps[::5] = 0
-    pos = np.clip(np.cumsum(steps, 0), -64, 64).astype(np.float32)
-    shift = np.diff(pos, axis=0, prepend=pos[:1])
     pan = {}
-    for cmc in (False, True):
-        st, ev = new_state(TrackArgs().max_tracks), moteval.new_state(n_obj, 4096)
-        for f in range(Fp):
-            move = np.tile(pos[f], 2)
-            oid, obox, _ = track_reference(st, boxes[f] + move, scores[f], labels[f], n_valid[f], TrackArgs(),
-                                           shift=shift[f] if cmc else None)
-            rows = np.nonzero(oid >= 0)[0]
-            truth = np.stack([x0 + vx * f, y0 + vy * f, x0 + vx * f + w, y0 + vy * f + h], 1) + move
-            moteval.mot_reference(ev, (truth.astype(np.float32), i, np.ones(n_obj, np.int32)),
-                                  (obox[rows], oid[rows] - 1), thr)
+    for cmc, frames in pan_frames().items():
+        ev = moteval.new_state(40, 4096)
+        for truth, i, flags, obox, oid in frames:
+            moteval.mot_reference(ev, (truth, i, flags), (obox, oid), thr)
         m = moteval.mot_metrics(ev)
-        pan["cmc_on" if cmc else "cmc_off"] = {"MOTA": round(m["MOTA"], 4), "IDF1": round(m["IDF1"], 4),
-                                               "IDSW": m["IDSW"], "FN": m["FN"], "FP": m["FP"]}
+        pan[cmc] = {"MOTA": round(m["MOTA"], 4), "IDF1": round(m["IDF1"], 4),
+                    "IDSW": m["IDSW"], "FN": m["FN"], "FP": m["FP"]}
 
     torch.manual_seed(0)
     model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
@@ -1122,6 +1137,116 @@ def mot_eval_leg(reps, rounds):
     line["host_over_kernel"] = round(1e3 * line["host_ms"] / line["kernel_us"], 1)
     line["host_over_device_path"] = round(line["host_ms"] / line["device_path_ms"], 1)
     line["kernel_over_forward"] = round(line["kernel_us"] / line["forward_replay_us"], 3)
+    print(json.dumps(line), flush=True)
+
+
+def hota_leg(reps, rounds):
+    """The frame-parallel HOTA kernels (rtdetr_hota_pass_a / _gas / _pass_b) at
+    --mot-eval's shape (8 sequences of 600 frames, 30 truths and 35 tracker rows
+    a frame) against hota.hota_reference on the host, same process, same rows:
+    every state array, gas and the loc partials checked equal first, bit for
+    bit.  The 4800 frames are one launch of 4800 workgroups per pass
+    (moteval.pack_chunks at hota.HOTA_MAX_F), against rtdetr_mot_eval's 5
+    launches of 8.  hota_kernels_us: pass A, gas and pass B, dispatch-stamped,
+    the rows on the device; mot_eval_kernel_us: rtdetr_mot_eval's 5 launches,
+    likewise; device_path_ms: hota.run_device_hota (pack, upload, new state, the
+    launches, the state and the partials copied back, the reduction in frame
+    order) and hota_metrics, wall clock; host_ms: hota.run_reference_hota and
+    hota_metrics, wall clock; forward_replay_us: one EvalForward graph replay at
+    batch 16.  Median, min and max over the rounds, the sides interleaved in
+    each round.  Also HOTA / DetA / AssA of the synthetic pan (pan_frames) with
+    cmc off and on: synthetic input, no accuracy claim beyond it."""
+    import time
+
+    from src.rtdetr_moe import engine, hota, moteval
+    from src.rtdetr_moe.model import RTDETRMoE
+
+    S, F, n_gt, n_trk, thr = 8, 600, 30, 35, 0.5
+    seqs = [{"NG": n_gt, "NT": n_trk, "frames": mot_sequence(s, F, n_gt, n_trk)} for s in range(S)]
+    chunks, M, K = moteval.pack_chunks(seqs, hota.HOTA_MAX_F)
+    dev_chunks = [{k: torch.from_numpy(v).cuda() for k, v in c.items() if k != "frame_reset"} for c in chunks]
+    keeps = [torch.empty(c["trk_idx"].shape, dtype=torch.uint8, device="cuda") for c in dev_chunks]
+    mot_chunks = [{k: torch.from_numpy(v).cuda() for k, v in c.items()} for c in moteval.pack_chunks(seqs)[0]]
+    order = ("gt_boxes", "gt_idx", "gt_flag", "n_gt", "trk_boxes", "trk_idx", "n_trk", "frame_slot", "frame_reset")
+
+    def kernels():
+        st = hota.HotaEvalState(S, n_gt, n_trk, "cuda")  # torch fills: not among the library's profiled launches
+        for c, keep in zip(dev_chunks, keeps):
+            L.hota_pass_a(st, c, keep, thr)
+        L.hota_gas(st)
+        for c, keep in zip(dev_chunks, keeps):
+            L.hota_pass_b(st, c, keep)
+
+    def mot_kernel():
+        st = moteval.MotEvalState(S, n_gt, n_trk, "cuda")
+        for c in mot_chunks:
+            L.mot_eval(st, *(c[k] for k in order), thr)
+
+    def device_path():
+        return [hota.hota_metrics(st) for st in hota.run_device_hota(seqs, thr, torch.device("cuda"))]
+
+    def host_path():
+        return [hota.hota_metrics(st) for st in hota.run_reference_hota(seqs, thr)]
+
+    want = hota.run_reference_hota(seqs, thr)
+    for s, (got, ref) in enumerate(zip(hota.run_device_hota(seqs, thr, torch.device("cuda")), want)):
+        if not hota.hota_states_equal(got, ref) or got["gas"].tobytes() != ref["gas"].tobytes() or \
+                got["loc_part"].tobytes() != ref["loc_part"].tobytes():
+            raise SystemExit(f"the HOTA kernels' state differs from hota_reference's (sequence {s})")
+    combined = hota.combine_hota(device_path())
+    if combined != hota.combine_hota([hota.hota_metrics(st) for st in want]):
+        raise SystemExit("the device path's combined HOTA differs from the host's")
+    pan = {}
+    for cmc, frames in pan_frames().items():
+        m = hota.hota_metrics(hota.hota_reference(frames, 40, 4096, thr))
+        pan[cmc] = {k: round(m[k], 4) for k in ("HOTA", "DetA", "AssA", "LocA")}
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    def wall(fn, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return statistics.median(ts)
+
+    res = {"hota_kernels_us": [], "mot_eval_kernel_us": [], "device_path_ms": [], "host_ms": [],
+           "forward_replay_us": []}
+    for _ in range(rounds):
+        res["hota_kernels_us"].append(timed(kernels, max(3, reps // 10)))
+        res["mot_eval_kernel_us"].append(timed(mot_kernel, max(3, reps // 10)))
+        res["device_path_ms"].append(wall(device_path, 3))
+        res["host_ms"].append(wall(host_path, 1))
+        res["forward_replay_us"].append(replay_us())
+    line = {"kernel": "rtdetr_hota", "shape": f"S{S} F{F} M{M} K{K} NG{n_gt} NT{n_trk}",
+            "launches": 2 * len(chunks) + 1, "workgroups_per_pass": S * F, "mot_eval_launches": len(mot_chunks),
+            "combined": {k: round(combined[k], 4) for k in ("HOTA", "DetA", "AssA", "LocA")}, "pan_32_frames": pan}
+    for k, v in res.items():
+        line[k] = round(statistics.median(v), 3)
+        line[k + "_min"] = round(min(v), 3)
+        line[k + "_max"] = round(max(v), 3)
+    line["mot_eval_over_hota_kernels"] = round(line["mot_eval_kernel_us"] / line["hota_kernels_us"], 2)
+    line["host_over_device_path"] = round(line["host_ms"] / line["device_path_ms"], 1)
+    line["hota_kernels_over_forward"] = round(line["hota_kernels_us"] / line["forward_replay_us"], 3)
     print(json.dumps(line), flush=True)
 
 
@@ -1195,6 +1320,10 @@ def main():
                     help="check rtdetr_mot_eval against moteval.mot_reference (8 sequences of 600 frames), time it "
                          "against the host reference and a forward replay, print MOTA / IDF1 / IDSW on the synthetic "
                          "pan with cmc off and on, and exit")
+    ap.add_argument("--hota", action="store_true",
+                    help="check the frame-parallel HOTA kernels against hota.hota_reference at --mot-eval's shape, "
+                         "time them against the host reference, rtdetr_mot_eval and a forward replay, print HOTA / "
+                         "DetA / AssA on the synthetic pan with cmc off and on, and exit")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--variants", default="0")
@@ -1246,6 +1375,9 @@ def main():
         return
     if a.mot_eval:
         mot_eval_leg(a.reps, a.rounds)
+        return
+    if a.hota:
+        hota_leg(a.reps, a.rounds)
         return
     if a.cold:
         global _FLUSH

@@ -70,9 +70,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--gt-ignore-classes", type=str, default="",
                     help="--gt: the classes that are ignore regions, e.g. 2,7,8,12")
     ap.add_argument("--eval-iou", type=float, default=0.5, help="--gt: the IoU a match needs")
+    ap.add_argument("--hota", action="store_true",
+                    help="--gt: also score HOTA (DetA, AssA, LocA over 19 IoU thresholds)")
     a = ap.parse_args(argv)
     if a.gt is not None and not a.track:
         ap.error("--gt needs --track")
+    if a.hota and a.gt is None:
+        ap.error("--hota needs --gt")
     if a.tracker is not None and not a.track:
         ap.error("--tracker needs --track")
     given = a.cmc_radius is not None or a.cmc_gate is not None or a.cmc_rows is not None
@@ -108,7 +112,8 @@ def gt_args(a) -> dict:
     if a.gt is None:
         return {}
     return dict(gt=a.gt, gt_classes=int_list(a.gt_classes) if a.gt_classes else None,
-                gt_ignore_classes=int_list(a.gt_ignore_classes), eval_iou=a.eval_iou)
+                gt_ignore_classes=int_list(a.gt_ignore_classes), eval_iou=a.eval_iou,
+                **({"hota": True} if a.hota else {}))
 
 
 def print_mot(mot) -> None:
@@ -116,7 +121,9 @@ def print_mot(mot) -> None:
     cols = ("MOTA", "MOTP", "IDF1", "IDP", "IDR", "Recall", "Precision")
     ints = ("TP", "FN", "FP", "IDSW", "Frag", "MT", "PT", "ML", "GT", "removed", "frames")
     for key, m in mot.items():
-        print(f"{key}: " + " ".join(f"{c} {m[c]:.4f}" for c in cols) + " " + " ".join(f"{c} {m[c]}" for c in ints))
+        hota = "".join(f" {c} {m['HOTA'][c]:.4f}" for c in ("HOTA", "DetA", "AssA", "LocA")) if "HOTA" in m else ""
+        print(f"{key}: " + " ".join(f"{c} {m[c]:.4f}" for c in cols) + " " + " ".join(f"{c} {m[c]}" for c in ints)
+              + hota)
 
 
 def main(argv=None) -> None:

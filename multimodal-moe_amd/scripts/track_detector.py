@@ -10,7 +10,8 @@ compensation and adds camera_motion.json.
 scores the tracks against MOTChallenge ground truth (DIR/<sequence>/gt/gt.txt or
 DIR/<sequence>.txt): MOTA, MOTP, IDF1 and the counts per sequence and combined,
 printed and written to mot_metrics.json; scripts/eval_tracks.py scores the
-written mot/ directory again later, without a model.
+written mot/ directory again later, without a model.  --hota (with --gt) adds
+HOTA, DetA, AssA and LocA to both.
 """
 from __future__ import annotations
 

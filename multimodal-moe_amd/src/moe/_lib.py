@@ -128,6 +128,10 @@ SIGNATURES = {
                                 _P]),
     "rtdetr_mot_eval": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P,
                              _P, _P, _P]),
+    "rtdetr_hota_pass_a": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "rtdetr_hota_gas": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "rtdetr_hota_pass_b": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P,
+                                _P]),
     "rtdetr_set_criterion_match": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rtdetr_set_criterion_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "rtdetr_set_criterion_loss_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -304,9 +308,10 @@ def launch_counts(reset=False) -> dict:
     (host-side counts, graph capture included: moe_launch_counts).
     "eval_match_bands" -- the launches of eval_match_bands(), which the library
     counts with eval_match's -- is reported apart and taken out of "eval_match";
-    likewise "mot_eval" (mot_eval()), also counted with eval_match's, and
-    "box_fuse" (box_fuse()), which the library counts under "merge"."""
-    global _eval_match_bands_launches, _box_fuse_launches, _mot_eval_launches
+    likewise "mot_eval" (mot_eval()) and "hota" (hota_pass_a / hota_gas /
+    hota_pass_b), also counted with eval_match's, and "box_fuse" (box_fuse()),
+    which the library counts under "merge"."""
+    global _eval_match_bands_launches, _box_fuse_launches, _mot_eval_launches, _hota_launches
     n = max(PROF_KINDS) + 1
     buf = (ctypes.c_longlong * n)()
     _check(lib().moe_launch_counts(ctypes.cast(buf, ctypes.c_void_p), n), "moe_launch_counts")
@@ -315,6 +320,8 @@ def launch_counts(reset=False) -> dict:
     out["eval_match"] -= out["eval_match_bands"]
     out["mot_eval"] = min(_mot_eval_launches, out["eval_match"])
     out["eval_match"] -= out["mot_eval"]
+    out["hota"] = min(_hota_launches, out["eval_match"])
+    out["eval_match"] -= out["hota"]
     out["box_fuse"] = min(_box_fuse_launches, out["merge"])
     out["merge"] -= out["box_fuse"]
     if reset:
@@ -322,6 +329,7 @@ def launch_counts(reset=False) -> dict:
         _eval_match_bands_launches = 0
         _box_fuse_launches = 0
         _mot_eval_launches = 0
+        _hota_launches = 0
     return {k: v for k, v in out.items() if v}
 
 
@@ -1215,6 +1223,96 @@ def mot_eval_check(state) -> None:
     code = int(state.status.item())
     if code:
         raise MoEKernelError(f"rtdetr_mot_eval: status {code} (1 / 2: the solver refused a problem -- non-finite "
+                             "boxes --, 4: an index outside [0, NG) / [0, NT))")
+
+
+# rtdetr_hota_*: as mot_eval, the library counts them with eval_match's and launch_counts() reports them as "hota"
+_hota_launches = 0
+_HOTA_INPUTS = ("gt_boxes", "gt_idx", "gt_flag", "n_gt", "trk_boxes", "trk_idx", "n_trk", "frame_slot")
+
+
+def _hota_inputs(frames, keep, what):
+    """Check a batch of frames {name: tensor} (mot_eval's inputs without frame_reset) and the keep workspace
+    uint8 [F, K] -> (their pointers in the C order, F, M, K)."""
+    _need(frames["gt_boxes"], torch.float32, "gt_boxes")
+    _need(frames["trk_boxes"], torch.float32, "trk_boxes")
+    for name in _HOTA_INPUTS:
+        if "boxes" not in name:
+            _need(frames[name], torch.int32, name)
+    _need(keep, torch.uint8, "keep")
+    gb, tb = frames["gt_boxes"], frames["trk_boxes"]
+    if gb.dim() != 3 or gb.shape[-1] != 4 or tb.dim() != 3 or tb.shape[-1] != 4:
+        raise MoEKernelError(f"{what}: gt_boxes must be [F, M, 4] and trk_boxes [F, K, 4]")
+    F, M, _ = (int(v) for v in gb.shape)
+    K = int(tb.shape[1])
+    shapes = {"gt_idx": (F, M), "gt_flag": (F, M), "n_gt": (F,), "trk_idx": (F, K), "n_trk": (F,), "frame_slot": (F,)}
+    if int(tb.shape[0]) != F or any(tuple(frames[k].shape) != v for k, v in shapes.items()) or \
+            tuple(keep.shape) != (F, K):
+        raise MoEKernelError(f"{what}: expected {shapes}, trk_boxes [{F}, K, 4] and keep [{F}, {K}]")
+    if any(frames[k].device != gb.device for k in _HOTA_INPUTS) or keep.device != gb.device:
+        raise MoEKernelError(f"{what}: all tensors must be on one device")
+    return [_ptr(frames[k]) for k in _HOTA_INPUTS], F, M, K
+
+
+def _hota_state(state, what):
+    S, NG, NT = state.S, state.NG, state.NT
+    spec = ((state.pot_q, (S, NG, NT), torch.int64), (state.gt_count, (S, NG), torch.int32),
+            (state.trk_count, (S, NT), torch.int32), (state.gas, (S, NG, NT), torch.float32),
+            (state.counts, (S, 3, 19), torch.int64), (state.mc, (S, 19, NG, NT), torch.int32),
+            (state.status, (1,), torch.int32), (state.alpha, (19,), torch.float64))
+    for t, shape, dtype in spec:
+        _need(t, dtype, "state")
+        if tuple(t.shape) != shape or t.device != state.pot_q.device:
+            raise MoEKernelError(f"{what}: a state tensor must be {shape} on the state's device, got {tuple(t.shape)}")
+    return S, NG, NT
+
+
+def hota_pass_a(state, frames, keep, thr=0.5):
+    """HOTA's pass A over a batch of frames, one workgroup per frame (rtdetr_hota_pass_a: hota.hota_pass_a per
+    frame, bit for bit).  ``state``: a hota.HotaEvalState; ``frames``: {name: tensor} of mot_eval's inputs
+    (frame_reset is not used: the frames are order-free); ``keep``: uint8 [F, K], written here for hota_pass_b
+    of the same frames.  Asynchronous; ``hota_check(state)`` after the last launch."""
+    global _hota_launches
+    ptrs, F, M, K = _hota_inputs(frames, keep, "hota_pass_a")
+    S, NG, NT = _hota_state(state, "hota_pass_a")
+    rc = lib().rtdetr_hota_pass_a(*ptrs, F, M, K, S, NG, NT, float(thr), _ptr(state.pot_q), _ptr(state.gt_count),
+                                  _ptr(state.trk_count), _ptr(keep), _ptr(state.status), _stream())
+    _check(rc, "rtdetr_hota_pass_a")
+    if F > 0:
+        _hota_launches += 1
+
+
+def hota_gas(state):
+    """state.gas from state.pot_q and the counts, after every pass A launch (rtdetr_hota_gas: hota.hota_gas)."""
+    global _hota_launches
+    S, NG, NT = _hota_state(state, "hota_gas")
+    rc = lib().rtdetr_hota_gas(_ptr(state.pot_q), _ptr(state.gt_count), _ptr(state.trk_count), S, NG, NT,
+                               _ptr(state.gas), _stream())
+    _check(rc, "rtdetr_hota_gas")
+    _hota_launches += 1
+
+
+def hota_pass_b(state, frames, keep):
+    """HOTA's pass B over a batch of frames, one workgroup per frame (rtdetr_hota_pass_b: hota.hota_pass_b per
+    frame, bit for bit), after hota_gas -> the frames' loc partials fp64 [F, 19] (hota.reduce_loc adds a
+    sequence's in frame order).  ``keep``: what hota_pass_a wrote for these frames."""
+    global _hota_launches
+    ptrs, F, M, K = _hota_inputs(frames, keep, "hota_pass_b")
+    S, NG, NT = _hota_state(state, "hota_pass_b")
+    loc = torch.empty((F, 19), dtype=torch.float64, device=keep.device)
+    rc = lib().rtdetr_hota_pass_b(*ptrs, _ptr(keep), F, M, K, S, NG, NT, _ptr(state.gas), _ptr(state.alpha),
+                                  _ptr(state.counts), _ptr(state.mc), _ptr(loc), _ptr(state.status), _stream())
+    _check(rc, "rtdetr_hota_pass_b")
+    if F > 0:
+        _hota_launches += 1
+    return loc
+
+
+def hota_check(state) -> None:
+    """Raise if any launch on ``state`` set the status word (waits for them)."""
+    code = int(state.status.item())
+    if code:
+        raise MoEKernelError(f"rtdetr_hota: status {code} (1 / 2: the solver refused a problem -- non-finite "
                              "boxes --, 4: an index outside [0, NG) / [0, NT))")
 
 

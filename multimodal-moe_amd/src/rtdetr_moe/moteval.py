@@ -10,6 +10,8 @@ MOTChallenge ground truth, the rule stated once.
   between launches, with an export to the reference's arrays.
 * ``mot_metrics``: the metrics of a finished state, on the host, for both paths.
 * ``load_gt`` / ``parse_mot`` / ``evaluate``: MOTChallenge files in, metrics out.
+  ``evaluate(..., hota=True)`` adds HOTA, whose rule, reference and device path
+  are hota.py's (it shares steps 1-2 and the dense indices below).
 
 The rule.  The host maps a sequence's raw ids to dense indices: ground truth g
 in [0, NG), tracker t in [0, NT).  A frame brings ground-truth rows (box xyxy
@@ -459,9 +461,9 @@ def run_reference(seqs, thr) -> list:
     return states
 
 
-def pack_chunks(seqs):
+def pack_chunks(seqs, max_frames=MOT_MAX_F):
     """The launches of ``seqs`` (at most MOT_MAX_S of them, slot j for sequence
-    j): host arrays per chunk of at most MOT_MAX_F frames.  A chunk
+    j): host arrays per chunk of at most ``max_frames`` frames.  A chunk
     holds the next frames of every sequence that has frames left, the same
     number of each, a sequence's frames in order, so that the launch's
     workgroups -- one per sequence -- all have work."""
@@ -473,7 +475,7 @@ def pack_chunks(seqs):
         live = [j for j, sq in enumerate(seqs) if done[j] < len(sq["frames"])]
         if not live:
             return chunks, M, K
-        per = max(1, MOT_MAX_F // len(live))
+        per = max(1, max_frames // len(live))
         picks = [(j, f) for j in live for f in range(done[j], min(done[j] + per, len(seqs[j]["frames"])))]
         F = len(picks)
         c = {"gt_boxes": np.zeros((F, M, 4), np.float32), "gt_idx": np.zeros((F, M), np.int32),
@@ -519,7 +521,7 @@ def run_device(seqs, thr, device) -> list:
     return states
 
 
-def evaluate(gt, results, thr=0.5, device=None) -> dict:
+def evaluate(gt, results, thr=0.5, device=None, hota=False) -> dict:
     """Score tracker output against ground truth.  ``gt``: load_gt's dict;
     ``results``: {key: MOT text} as predictor.mot_lines returns it, or a
     directory of <key>.txt files; every key of ``gt`` must have results.  The
@@ -529,7 +531,10 @@ def evaluate(gt, results, thr=0.5, device=None) -> dict:
     takes) all sequences are packed, padded to the largest M and K, and every
     chunk of at most 1024 frames is ONE HIP launch (rtdetr_mot_eval); with
     ``device`` None or the CPU, or MOE_TRACK_EVAL=0, mot_reference runs
-    instead and gives the same dict."""
+    instead and gives the same dict.  ``hota``: every sequence's dict and
+    COMBINED gain one key "HOTA" holding hota.hota_metrics' / combine_hota's
+    dict (hota.py: the frame-parallel kernels rtdetr_hota_* on a GPU device,
+    hota_reference otherwise, the same dict either way)."""
     thr = check_thr(thr)
     keys = list(gt)
     if "COMBINED" in keys:
@@ -547,4 +552,11 @@ def evaluate(gt, results, thr=0.5, device=None) -> dict:
     states = run_device(seqs, thr, dev) if eval_on_gpu(dev) and seqs else run_reference(seqs, thr)
     out = {k: mot_metrics(st) for k, st in zip(keys, states)}
     out["COMBINED"] = combine([out[k] for k in sorted(keys)])
+    if hota:
+        from . import hota as H
+
+        hs = H.run_device_hota(seqs, thr, dev) if eval_on_gpu(dev) and seqs else H.run_reference_hota(seqs, thr)
+        for k, st in zip(keys, hs):
+            out[k]["HOTA"] = H.hota_metrics(st)
+        out["COMBINED"]["HOTA"] = H.combine_hota([out[k]["HOTA"] for k in sorted(keys)])
     return out

@@ -72,6 +72,7 @@ class PredictResults:
     save_dir: Path | None
     model: ModelHandle | None
     # track with gt=...: moteval.evaluate's {sequence file key: metrics, "COMBINED": metrics}; None otherwise
+    # (with hota=True every metrics dict also has a "HOTA" entry)
     mot: dict | None = None
 
 
@@ -486,12 +487,12 @@ def _prediction(path, size, ctx, row, k=None, fused=False, **tracked) -> Predict
                       members=row[:, MEMBERS].to(torch.int64) if fused else None, **tracked)
 
 
-def _score_tracks(preds, truth, eval_iou, dev) -> dict:
+def _score_tracks(preds, truth, eval_iou, dev, hota=False) -> dict:
     """moteval.evaluate of exactly the rows mot/<sequence>.txt holds: mot_lines' text, parsed back."""
     from . import moteval
 
     texts = {key.replace("/", "_"): text for key, text in mot_lines(preds).items()}
-    return moteval.evaluate({k: truth[k] for k in texts}, texts, thr=eval_iou, device=dev)
+    return moteval.evaluate({k: truth[k] for k in texts}, texts, thr=eval_iou, device=dev, hota=hota)
 
 
 def _load_truth(gt, seq_of, gt_classes, gt_ignore_classes) -> dict:
@@ -529,7 +530,8 @@ def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False, mot=N
 def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25, max_det=300, contexts=None,
             workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
             merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55, track=None,
-            sequence_of=None, gt=None, gt_classes=None, gt_ignore_classes=(), eval_iou=0.5) -> PredictResults:
+            sequence_of=None, gt=None, gt_classes=None, gt_ignore_classes=(), eval_iou=0.5,
+            hota=False) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -631,7 +633,14 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     moteval.mot_reference and give the same result.  It goes into
     ``PredictResults.mot`` ({key: metrics, "COMBINED": metrics}) and into
     mot_metrics.json beside tracks.json.  Without ``gt`` nothing of this
-    runs."""
+    runs.
+    ``hota`` (with ``gt``; without it a ValueError): every entry of
+    ``PredictResults.mot`` and of mot_metrics.json gains the key "HOTA":
+    hota.hota_metrics' dict (HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA
+    over 19 localisation thresholds).  On a GPU every frame is scored in a
+    workgroup of its own (rtdetr_hota_*); the CPU device or MOE_TRACK_EVAL=0
+    run hota.hota_reference and give the same result.  Without ``hota`` the
+    entries are what they are without it."""
     # engine imports this module, and tests replace engine.EvalForward and preprocess.FrameSource: looked up per call
     from . import engine, preprocess
 
@@ -642,6 +651,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         if targs is None:
             raise ValueError("gt scores tracks: give track=... as well")
         eval_iou = check_thr(eval_iou)
+    elif hota:
+        raise ValueError("hota scores tracks against ground truth: give gt=... as well")
     devices = engine.parse_device(device)
     dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
     on_gpu = dev.type == "cuda"
@@ -719,7 +730,7 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     speed = {key: 1e3 * t / max(len(preds), 1) for key, t in clock.items()}
     if tiles is not None:
         speed["passes"] = 1 + n_tiles
-    mot = _score_tracks(preds, truth, eval_iou, dev) if truth is not None else None
+    mot = _score_tracks(preds, truth, eval_iou, dev, bool(hota)) if truth is not None else None
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
         _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc, mot)

@@ -200,6 +200,41 @@ int main() {
     std::printf("FAIL mot_eval F=0 must succeed\n");
     ++g_fail;
   }
+  // HOTA: F, M, K, S, NG, NT, thr, then one operand replaced
+  auto hota_a = [&](int F, int M, int K, int S, int NG, int NT, float thr, const float* gtb, int32_t* status) {
+    return rtdetr_hota_pass_a(gtb, i32, i32, i32, f32, i32, i32, i32, F, M, K, S, NG, NT, thr, c64, i32, i32, u8, status,
+                              s);
+  };
+  auto hota_b = [&](int F, int M, int K, int S, int NG, int NT, const float* gtb, const double* alpha) {
+    return rtdetr_hota_pass_b(gtb, i32, i32, i32, f32, i32, i32, i32, u8, F, M, K, S, NG, NT, f32, alpha, c64, i32, d64,
+                              i32, s);
+  };
+  expect_error("hota_pass_a K=1025", hota_a(1, 4, 1025, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("hota_pass_a M=257", hota_a(1, 257, 4, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("hota_pass_a F=65537", hota_a(65537, 4, 4, 1, 8, 8, 0.5f, f32, i32));
+  expect_error("hota_pass_a table over the budget", hota_a(1, 4, 4, 1, 1024, 2049, 0.5f, f32, i32));
+  expect_error("hota_pass_a S * NG * NT over the budget", hota_a(1, 4, 4, 3, 1024, 1024, 0.5f, f32, i32));
+  expect_error("hota_pass_a S=0 with frames", hota_a(1, 4, 4, 0, 8, 8, 0.5f, f32, i32));
+  expect_error("hota_pass_a thr=NaN", hota_a(1, 4, 4, 1, 8, 8, __builtin_nanf(""), f32, i32));
+  expect_error("hota_pass_a gt_boxes=NULL", hota_a(1, 4, 4, 1, 8, 8, 0.5f, nullptr, i32));
+  expect_error("hota_pass_a gt_boxes misaligned", hota_a(1, 4, 4, 1, 8, 8, 0.5f, f32 + 1, i32));
+  expect_error("hota_pass_a status=NULL", hota_a(1, 4, 4, 1, 8, 8, 0.5f, f32, nullptr));
+  expect_error("hota_pass_b K=1025", hota_b(1, 4, 1025, 1, 8, 8, f32, d64));
+  expect_error("hota_pass_b M=0", hota_b(1, 0, 4, 1, 8, 8, f32, d64));
+  expect_error("hota_pass_b table over the budget", hota_b(1, 4, 4, 1, 1024, 2049, f32, d64));
+  expect_error("hota_pass_b gt_boxes=NULL", hota_b(1, 4, 4, 1, 8, 8, nullptr, d64));
+  expect_error("hota_pass_b alpha=NULL", hota_b(1, 4, 4, 1, 8, 8, f32, nullptr));
+  expect_error("hota_pass_b alpha misaligned",
+               hota_b(1, 4, 4, 1, 8, 8, f32, reinterpret_cast<const double*>(buf + 4)));
+  expect_error("hota_gas table over the budget", rtdetr_hota_gas(c64, i32, i32, 1, 1024, 2049, f32, s));
+  expect_error("hota_gas NG=0", rtdetr_hota_gas(c64, i32, i32, 1, 0, 8, f32, s));
+  expect_error("hota_gas gas=NULL", rtdetr_hota_gas(c64, i32, i32, 1, 8, 8, nullptr, s));
+  g_n += 3;
+  if (hota_a(0, 4, 4, 0, 8, 8, 0.5f, nullptr, nullptr) != 0 || hota_b(0, 4, 4, 0, 8, 8, nullptr, nullptr) != 0 ||
+      rtdetr_hota_gas(nullptr, nullptr, nullptr, 0, 8, 8, nullptr, s) != 0) {  // F == 0 / S == 0: success, no launch
+    std::printf("FAIL hota F=0 / S=0 must succeed\n");
+    ++g_fail;
+  }
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
