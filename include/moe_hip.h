@@ -970,6 +970,37 @@ int rtdetr_track_update_shift(const float* boxes, const float* scores, const int
                               float* trk_score, int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id,
                               float* out_boxes, int32_t* count, const float* frame_shift, hipStream_t stream);
 
+/* The tracker's parameter sweep (tune.sweep, scripts/tune_tracker.py): G
+ * configurations of rtdetr_track_update_shift's rule over the same inputs in
+ * one launch on a (S, G) grid: workgroup (s, g) is rtdetr_track_update_shift's
+ * workgroup s -- the same device function, the same decisions and boxes bit for
+ * bit -- under configuration g.  Inputs (boxes ... frame_reset, frame_shift or
+ * NULL) as above, read-only and shared by every configuration.  The
+ * configurations are two device tables, so that one launch serves any G:
+ *   params_f fp32  [G][7]  track_high, track_low, new_thr, match_iou, second_iou, alpha, beta
+ *   params_i int32 [G][3]  max_age, min_hits, class_agnostic
+ * The entry cannot see their values: the caller guarantees what
+ * rtdetr_track_update checks (no NaN, max_age in [0, 2^30], min_hits in [1,
+ * 2^30]); _lib.track_sweep builds them from validated TrackArgs only.
+ * State: the four buffers above with a leading G: trk_box [G][S][T][8],
+ * trk_score [G][S][T], trk_meta [G][S][T][4], seq_meta [G][S][2]
+ * (track.SweepState).
+ * Outputs, the compact report, every element written: a track slot is reported
+ * by at most one row per frame, so a frame reports count <= T rows, and the
+ * j-th reported row in row order stands at position j:
+ *   count     int32 [G][F]
+ *   out_id    int32 [G][F][T]     the slot's id, -1 past count
+ *   out_boxes fp32  [G][F][T][4]  its filtered box, zeros past count (16-byte aligned)
+ *   out_row   int32 [G][F][T]     the row d that reported it, -1 past count
+ * A frame whose slot is outside [0, S) gets count 0 and the padding for every
+ * g.  Limits and refusals as rtdetr_track_update's, and 1 <= G <= 1024, no NULL
+ * table; profiler kind MOE_PROF_TRACK_SWEEP.  F == 0 returns 0 without a launch. */
+int rtdetr_track_sweep(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                       const int32_t* frame_slot, const int32_t* frame_reset, int F, int K, int S, int T, int G,
+                       const float* params_f, const int32_t* params_i, float* trk_box, float* trk_score,
+                       int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* out_row,
+                       int32_t* count, const float* frame_shift, hipStream_t stream);
+
 /* Camera-motion compensation for the tracker (TrackArgs.cmc): the global shift
  * of each frame against its predecessor, motion.sequence_shifts on the host bit
  * for bit (the rule: src/rtdetr_moe/motion.py).  It measures on the model's
@@ -1448,7 +1479,8 @@ int train_mosaic_boxes(const float* boxes, const int64_t* labels, const int32_t*
  * 12 self-attention, 13 implicit-GEMM convolutions, 14 router weight /
  * context-bias gradients, 15 training batch augmentation, 16 validation
  * matching, 17 routing statistics, 18 inference preprocessing (resize),
- * 19 tiled prediction's merge, 20 tracking, 21 camera-motion estimation.
+ * 19 tiled prediction's merge, 20 tracking, 21 camera-motion estimation,
+ * 22 the tracker's parameter sweep.
  * Not thread-safe, not for graph capture.  enable(0|1) also clears; get()
  * waits for the record. */
 enum moe_prof_kind {
@@ -1473,7 +1505,8 @@ enum moe_prof_kind {
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
   MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
   MOE_PROF_TRACK = 20,     /* tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift]) */
-  MOE_PROF_MOTION = 21     /* tracking: a frame's global shift against its predecessor (rtdetr_frame_shift) */
+  MOE_PROF_MOTION = 21,    /* tracking: a frame's global shift against its predecessor (rtdetr_frame_shift) */
+  MOE_PROF_TRACK_SWEEP = 22 /* tracker tuning: every configuration of a parameter grid in one launch (rtdetr_track_sweep) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

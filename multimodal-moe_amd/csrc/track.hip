@@ -35,6 +35,12 @@
 // rounded on its own, no FMA contraction (pragma below), one correctly rounded
 // division.
 //
+// rtdetr_track_sweep (tune.py) runs G configurations of the same rule in one launch: workgroup (s, g) of a (S, G)
+// grid is the workgroup above under the g-th row of two device tables, on the same read-only inputs, with state
+// [G][S] and, in place of step 5, the compact report: the j-th reported row in row order at position j of out_id
+// [G][F][T], out_boxes [G][F][T][4] and out_row [G][F][T] (a slot is taken by one row a frame, so count <= T),
+// ranked by trk_block_rank as the births are; -1 / zeros / -1 past count.
+//
 // LDS (dynamic, every offset a multiple of 16): rows 28 K bytes, tracks 52 T
 // bytes, the free list 4 T, 192 bytes of keys and counters: 41.2 KiB at the
 // limits K = 1024, T = 256.
@@ -47,6 +53,7 @@ namespace moe {
 
 constexpr int kTrkMaxK = 1024, kTrkMaxT = 256, kTrkMaxF = 1024, kTrkMaxS = 1024, kTrkMaxWaves = 4;
 constexpr int kTrkHitsCap = 1 << 30;
+constexpr int kTrkMaxG = 1024, kTrkSweepF = 7, kTrkSweepI = 3;  // rtdetr_track_sweep: configurations, table widths
 constexpr int kRowOut = -3, kRowLow = -2, kRowHigh = -1;  // rstate: not taking part / free low / free high; >= 0: its slot
 
 __host__ __device__ constexpr size_t trk_up16(size_t n) { return (n + 15) & ~(size_t)15; }
@@ -114,13 +121,19 @@ __device__ __forceinline__ int trk_block_rank(bool flag, int32_t* wcnt, int lane
   return base + __popcll(bal & below);
 }
 
-__global__ __launch_bounds__(256) void track_update_kernel(
+// The frames of state slot ``s`` for one configuration ``p``: the whole rule, shared by track_update_kernel and
+// track_sweep_kernel.  gbox / gscore / gmeta / gseq are the state slot's own buffers; out_id, out_boxes, out_row and
+// count are the launch's (the configuration's, in a sweep).  kCompact chooses the form of step 5: false, out_id [F][K]
+// and out_boxes [F][K][4] per row (out_row unused); true, the reported rows alone, in row order, in out_id [F][T],
+// out_boxes [F][T][4] and out_row [F][T], padded with -1 / zeros / -1.
+template <bool kCompact>
+__device__ __forceinline__ void trk_run(
     const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
     const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
-    TrkParams p, float* __restrict__ trk_box,
-    float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
-    int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ count) {
+    const int s, const TrkParams& p, float4* __restrict__ gbox, float* __restrict__ gscore,
+    int4* __restrict__ gmeta, int32_t* __restrict__ gseq, int32_t* __restrict__ out_id,
+    float* __restrict__ out_boxes, int32_t* __restrict__ out_row, int32_t* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const TrkLds o(K, T);
   float4* rbox = reinterpret_cast<float4*>(smem + o.rbox);
@@ -136,24 +149,25 @@ __global__ __launch_bounds__(256) void track_update_kernel(
   int32_t* wcnt = reinterpret_cast<int32_t*>(smem + o.wcnt);
   int32_t* ctl = reinterpret_cast<int32_t*>(smem + o.ctl);
 
-  const int s = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+  const int tid = threadIdx.x, nthr = blockDim.x;
   const int lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
   const bool mine = tid < T;  // this thread owns track slot tid
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4* gbox = reinterpret_cast<float4*>(trk_box) + (size_t)s * T * 2;
-  int4* gmeta = reinterpret_cast<int4*>(trk_meta) + (size_t)s * T;
+  const int W = kCompact ? T : K;  // the outputs' row length
   bool loaded = false;  // block-uniform: the sequence's tracks stand in LDS
   int parity = 0;       // which half of wkey the next round writes
 
   for (int f = 0; f < F; ++f) {
     const int fs = frame_slot[f];  // block-uniform
-    float4* ob = reinterpret_cast<float4*>(out_boxes) + (size_t)f * K;
-    int32_t* oi = out_id + (size_t)f * K;
+    float4* ob = reinterpret_cast<float4*>(out_boxes) + (size_t)f * W;
+    int32_t* oi = out_id + (size_t)f * W;
+    int32_t* orow = kCompact ? out_row + (size_t)f * W : nullptr;
     if (fs != s) {
       if ((fs < 0 || fs >= S) && f % S == s) {  // nobody's frame: the empty outputs
-        for (int d = tid; d < K; d += nthr) {
+        for (int d = tid; d < W; d += nthr) {
           oi[d] = -1;
           ob[d] = zero4;
+          if (kCompact) orow[d] = -1;
         }
         if (tid == 0) count[f] = 0;
       }
@@ -176,12 +190,12 @@ __global__ __launch_bounds__(256) void track_update_kernel(
         if (mine) {
           tbox[tid] = gbox[2 * tid];
           tvel[tid] = gbox[2 * tid + 1];
-          tscore[tid] = trk_score[(size_t)s * T + tid];
+          tscore[tid] = gscore[tid];
           tmeta[tid] = gmeta[tid];
         }
         if (tid == 0) {
-          ctl[0] = seq_meta[2 * s];
-          ctl[1] = seq_meta[2 * s + 1];
+          ctl[0] = gseq[0];
+          ctl[1] = gseq[1];
         }
       }
       loaded = true;
@@ -319,22 +333,57 @@ __global__ __launch_bounds__(256) void track_update_kernel(
     }
 
     // 5. report
-    for (int base = 0; base < K; base += nthr) {
-      const int d = base + tid;
-      bool rep = false;
-      if (d < K) {
-        const int t = rstate[d];
-        int4 tm = make_int4(0, 0, 0, 0);
-        if (t >= 0) tm = tmeta[t];
-        rep = t >= 0 && tm.w >= p.min_hits;
-        oi[d] = rep ? tm.y : -1;
-        ob[d] = rep ? tbox[t] : zero4;
+    if (kCompact) {
+      // the j-th reported row, in row order, goes to position j; a slot is taken by one row, so at most T of them
+      int reported = 0;  // block-uniform: the reported rows so far
+      for (int base = 0; base < K; base += nthr) {
+        const int d = base + tid;
+        bool rep = false;
+        int rid = -1;
+        float4 rb = zero4;
+        if (d < K) {
+          const int t = rstate[d];
+          if (t >= 0) {
+            const int4 tm = tmeta[t];
+            rep = tm.w >= p.min_hits;
+            rid = tm.y;
+            rb = tbox[t];
+          }
+        }
+        int nr = 0;
+        const int j = reported + trk_block_rank(rep, wcnt, lane, wave, nwaves, &nr);
+        if (rep && j < T) {
+          oi[j] = rid;
+          ob[j] = rb;
+          orow[j] = d;
+        }
+        reported += nr;
       }
-      const unsigned long long bal = __ballot(rep);
-      if (lane == 0 && bal != 0ull) atomicAdd(&ctl[2], __popcll(bal));
+      reported = min(reported, T);
+      for (int j = reported + tid; j < T; j += nthr) {
+        oi[j] = -1;
+        ob[j] = zero4;
+        orow[j] = -1;
+      }
+      if (tid == 0) count[f] = reported;
+    } else {
+      for (int base = 0; base < K; base += nthr) {
+        const int d = base + tid;
+        bool rep = false;
+        if (d < K) {
+          const int t = rstate[d];
+          int4 tm = make_int4(0, 0, 0, 0);
+          if (t >= 0) tm = tmeta[t];
+          rep = t >= 0 && tm.w >= p.min_hits;
+          oi[d] = rep ? tm.y : -1;
+          ob[d] = rep ? tbox[t] : zero4;
+        }
+        const unsigned long long bal = __ballot(rep);
+        if (lane == 0 && bal != 0ull) atomicAdd(&ctl[2], __popcll(bal));
+      }
+      __syncthreads();
+      if (tid == 0) count[f] = ctl[2];
     }
-    __syncthreads();
-    if (tid == 0) count[f] = ctl[2];
     __syncthreads();  // before the next frame overwrites the rows and ctl[2]
   }
 
@@ -342,14 +391,59 @@ __global__ __launch_bounds__(256) void track_update_kernel(
     if (mine) {
       gbox[2 * tid] = tbox[tid];
       gbox[2 * tid + 1] = tvel[tid];
-      trk_score[(size_t)s * T + tid] = tscore[tid];
+      gscore[tid] = tscore[tid];
       gmeta[tid] = tmeta[tid];
     }
     if (tid == 0) {
-      seq_meta[2 * s] = ctl[0];
-      seq_meta[2 * s + 1] = ctl[1];
+      gseq[0] = ctl[0];
+      gseq[1] = ctl[1];
     }
   }
+}
+
+__global__ __launch_bounds__(256) void track_update_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
+    const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
+    TrkParams p, float* __restrict__ trk_box,
+    float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
+    int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ count) {
+  const int s = blockIdx.x;
+  trk_run<false>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p,
+                 reinterpret_cast<float4*>(trk_box) + (size_t)s * T * 2, trk_score + (size_t)s * T,
+                 reinterpret_cast<int4*>(trk_meta) + (size_t)s * T, seq_meta + 2 * (size_t)s, out_id, out_boxes,
+                 nullptr, count);
+}
+
+// The parameter sweep (tune.py): workgroup (s, g) runs state slot s under configuration g of the two tables, on the
+// same read-only inputs; the state is [G][S] slots, the outputs [G][F] frames in the compact form.
+__global__ __launch_bounds__(256) void track_sweep_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
+    const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
+    const float* __restrict__ params_f, const int32_t* __restrict__ params_i, float* __restrict__ trk_box,
+    float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
+    int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ out_row,
+    int32_t* __restrict__ count) {
+  const int s = blockIdx.x, g = blockIdx.y;
+  const float* pf = params_f + (size_t)g * kTrkSweepF;
+  const int32_t* pi = params_i + (size_t)g * kTrkSweepI;
+  TrkParams p;
+  p.track_high = pf[0];
+  p.track_low = pf[1];
+  p.new_thr = pf[2];
+  p.match_iou = pf[3];
+  p.second_iou = pf[4];
+  p.alpha = pf[5];
+  p.beta = pf[6];
+  p.max_age = pi[0];
+  p.min_hits = pi[1];
+  p.class_agnostic = pi[2] != 0 ? 1 : 0;
+  const size_t gs = (size_t)g * S + s, gf = (size_t)g * F;
+  trk_run<true>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p,
+                reinterpret_cast<float4*>(trk_box) + gs * T * 2, trk_score + gs * T,
+                reinterpret_cast<int4*>(trk_meta) + gs * T, seq_meta + 2 * gs, out_id + gf * T, out_boxes + gf * T * 4,
+                out_row + gf * T, count + gf);
 }
 
 }  // namespace moe
@@ -425,4 +519,39 @@ extern "C" int rtdetr_track_update_shift(const float* boxes, const float* scores
                       frame_shift, F, K, S, T, track_high, track_low, new_thr, match_iou, second_iou, max_age,
                       min_hits, alpha, beta, class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes,
                       count, stream);
+}
+
+extern "C" int rtdetr_track_sweep(const float* boxes, const float* scores, const int32_t* labels,
+                                  const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
+                                  int F, int K, int S, int T, int G, const float* params_f, const int32_t* params_i,
+                                  float* trk_box, float* trk_score, int32_t* trk_meta, int32_t* seq_meta,
+                                  int32_t* out_id, float* out_boxes, int32_t* out_row, int32_t* count,
+                                  const float* frame_shift, hipStream_t stream) {
+  const std::string what = "rtdetr_track_sweep";
+  if (F < 0 || K < 0 || S < 0 || F > kTrkMaxF || K > kTrkMaxK || S > kTrkMaxS || T < 1 || T > kTrkMaxT)
+    return fail(what + ": need 0 <= F <= 1024, 0 <= K <= 1024, 0 <= S <= 1024, 1 <= T <= 256");
+  if (G < 1 || G > kTrkMaxG) return fail(what + ": need 1 <= G <= 1024 configurations");
+  if (!params_f || !params_i) return fail(what + ": NULL parameter table");
+  if (F == 0) return 0;
+  if (S < 1) return fail(what + ": need S >= 1 state slots with F > 0");
+  if (!frame_slot || !frame_reset) return fail(what + ": NULL frame table");
+  if (!trk_box || !trk_score || !trk_meta || !seq_meta) return fail(what + ": NULL state pointer");
+  if (!count || !out_id || !out_boxes || !out_row) return fail(what + ": NULL output pointer");
+  if (K > 0 && (!boxes || !scores || !labels)) return fail(what + ": NULL input pointer");
+  if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_boxes) |
+       reinterpret_cast<uintptr_t>(trk_box) | reinterpret_cast<uintptr_t>(trk_meta)) & 15)
+    return fail(what + ": boxes, out_boxes, trk_box and trk_meta must be 16-byte aligned");
+  const size_t shmem = TrkLds(K, T).total;
+  if (shmem > 64 * 1024) return fail(what + ": K / T too large for LDS");
+  const int threads = (T + 63) / 64 * 64;
+  // the inputs once (every configuration's workgroups read the same lines), the tables, and per configuration the
+  // state read and written and the compact outputs
+  ProfScope prof(stream, PROF_TRACK_SWEEP,
+                 (double)F * (K * 24.0 + (n_valid ? 4.0 : 0.0) + (frame_shift ? 8.0 : 0.0) + 8.0) +
+                     (double)G * ((kTrkSweepF + kTrkSweepI) * 4.0 + (double)S * (T * 104.0 + 16.0) +
+                                  (double)F * (T * 24.0 + 4.0)));
+  MOE_LAUNCH(prof, track_sweep_kernel, dim3(S, G), dim3(threads), shmem, stream, boxes, scores, labels, n_valid,
+             frame_slot, frame_reset, frame_shift, F, K, S, T, params_f, params_i, trk_box, trk_score, trk_meta,
+             seq_meta, out_id, out_boxes, out_row, count);
+  return check_launch(what.c_str());
 }

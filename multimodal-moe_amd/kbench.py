@@ -14,6 +14,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
   python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
   python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
+  python multimodal-moe_amd/kbench.py --track-sweep the parameter sweep's kernel against G launches of the tracker's
   python multimodal-moe_amd/kbench.py --frame-shift the camera-motion estimator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --mot-eval    the tracking evaluator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --hota        the frame-parallel HOTA kernels against the host and rtdetr_mot_eval
@@ -858,6 +859,143 @@ def track_leg(reps, rounds):
     print(json.dumps(line), flush=True)
 
 
+def track_sweep_leg(reps, rounds):
+    """rtdetr_track_sweep at about MOT17's training split (8 sequences of 600
+    frames, --track's 300 candidate rows a frame of 40 objects, T 64) with G =
+    1, 16 and 64 configurations, one JSON line per G.  First the kernel's
+    compact report and states at G 16, all 4800 frames, are checked equal to
+    tune.track_sweep_reference's, bit for bit.  sweep_kernel_us: the launches of
+    one sweep (tune.launch_chunks: 1024 frames each), dispatch-stamped, summed;
+    update_x_g_kernel_us: rtdetr_track_update launched G times over the same
+    chunks, one configuration each -- what there was before -- likewise;
+    host_reference_ms: tune.track_sweep_reference for ONE configuration, wall
+    clock (G of them cost G times that: a loop); forward_replay_us: one
+    EvalForward graph replay at batch 16 (rtdetr-r50-moe8-top2, 704 x 1248);
+    sweep_wall_ms: tune.sweep(hota=True) on the GPU, wall clock, split into
+    tracking (packing the detections, the launches, the copies back), packing
+    (the G x 8 dense sequences on the host) and scoring (rtdetr_mot_eval and
+    rtdetr_hota_*, their own host packing included).  Median, min and max over
+    the rounds."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import engine, tune
+    from src.rtdetr_moe.model import RTDETRMoE
+    from src.rtdetr_moe.track import SweepState, TrackArgs, TrackState, states_equal
+
+    S, F, K, T, n_obj = 8, 600, 300, 64, 40
+    grids = {1: {}, 16: {"match_iou": [0.2, 0.3, 0.4, 0.5], "max_age": [5, 15, 30, 60]},
+             64: {"match_iou": [0.2, 0.3, 0.4, 0.5], "max_age": [5, 15, 30, 60], "min_hits": [1, 2],
+                  "track_high": [0.5, 0.6]}}
+    dets, gt = {}, {}
+    for q in range(S):
+        boxes, scores, labels, _, _ = track_sequence(n_obj, F, K, seed=q)
+        key = f"seq{q}"
+        dets[key] = {f + 1: (boxes[f], scores[f], labels[f]) for f in range(F)}
+        rng = np.random.default_rng(q)  # track_sequence's first draws: the objects' clean boxes
+        i = np.arange(n_obj)
+        w, h = rng.uniform(30, 50, n_obj), rng.uniform(80, 120, n_obj)
+        x0, y0 = 40.0 + (i % 10) * 110.0, 60.0 + (i // 10) * 150.0
+        vx, vy = rng.uniform(-0.8, 0.8, n_obj), rng.uniform(-0.3, 0.3, n_obj)
+        gt[key] = {f + 1: (np.stack([x0 + vx * f, y0 + vy * f, x0 + vx * f + w, y0 + vy * f + h], 1).astype(np.float32),
+                           i + 1, np.ones(n_obj, np.int32)) for f in range(F)}
+    seqs, _ = tune.pack_sequences(dets)
+    base = TrackArgs(max_tracks=T)
+    dev = torch.device("cuda")
+
+    cfg16 = tune.expand_grid(grids[16], base)
+    t0 = time.perf_counter()
+    want = tune.track_sweep_reference(dets, cfg16, T)
+    ref_s = time.perf_counter() - t0
+    got = tune.sweep_tracks(dets, cfg16, T, dev)
+    for g in range(16):
+        for key in dets:
+            a, b = got[g][key], want[g][key]
+            if not (np.array_equal(a["count"], b["count"]) and np.array_equal(a["ids"], b["ids"])
+                    and np.array_equal(a["rows"], b["rows"]) and a["boxes"].tobytes() == b["boxes"].tobytes()
+                    and states_equal(a["state"], b["state"])):
+                raise SystemExit(f"track_sweep differs from track_sweep_reference (configuration {g}, {key})")
+    reported = [int(sum(want[g][k]["count"].sum() for k in dets)) for g in range(16)]
+
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()  # noqa: E731
+    for G, grid in grids.items():
+        configs = tune.expand_grid(grid, base)
+        chunks = []
+        for picks in tune.launch_chunks(seqs, G, T):
+            cat = lambda key: up(np.concatenate([seqs[j][key][a:b] for j, a, b in picks]))  # noqa: E731
+            slot = np.concatenate([np.full(b - a, j, np.int32) for j, a, b in picks])
+            reset = np.concatenate([(np.arange(a, b) == 0).astype(np.int32) for j, a, b in picks])
+            chunks.append((cat("boxes"), cat("scores"), cat("labels"), cat("n_valid"), up(slot), up(reset)))
+        sweep_state, one_state = SweepState(G, S, T, dev), TrackState(S, T, dev)
+        outs = [tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in
+                      (((G, len(c[4]), T), torch.int32), ((G, len(c[4]), T, 4), torch.float32),
+                       ((G, len(c[4]), T), torch.int32), ((G, len(c[4])), torch.int32))) for c in chunks]
+
+        def sweep_kernel():
+            for c, o in zip(chunks, outs):
+                L.track_sweep(sweep_state, *c, configs, out=o)
+
+        def update_x_g():
+            for cfg in configs:
+                for c in chunks:
+                    L.track_update(one_state, *c, cfg)
+
+        def host_one():
+            tune.track_sweep_reference(dets, configs[:1], T)
+
+        res = {"sweep_kernel_us": [], "update_x_g_kernel_us": [], "host_reference_ms": [], "forward_replay_us": [],
+               "sweep_wall_ms": [], "tracking_ms": [], "packing_ms": [], "scoring_ms": []}
+        best = None
+        for r in range(rounds):
+            res["sweep_kernel_us"].append(timed(sweep_kernel, max(2, reps // 10)))
+            res["update_x_g_kernel_us"].append(timed(update_x_g, 1 if G > 1 else max(2, reps // 10)))
+            res["forward_replay_us"].append(replay_us())
+            if G == 1:
+                t0 = time.perf_counter()
+                host_one()
+                res["host_reference_ms"].append(1e3 * (time.perf_counter() - t0))
+            if G < 64 or r < 3:  # the largest sweep's wall clock: three rounds
+                tm = {}
+                t0 = time.perf_counter()
+                out = tune.sweep(dets, gt, configs, hota=True, device=dev, timing=tm)
+                res["sweep_wall_ms"].append(1e3 * (time.perf_counter() - t0))
+                for k in ("tracking", "packing", "scoring"):
+                    res[k + "_ms"].append(1e3 * tm[k])
+                best = (out["best"], round(out["metrics"][out["best"]]["COMBINED"]["HOTA"]["HOTA"], 4), tm["launches"])
+        line = {"kernel": "rtdetr_track_sweep", "shape": f"S{S} F{F} K{K} T{T} G{G} objects{n_obj}",
+                "launches": len(chunks), "workgroups": S * G, "update_launches": G * len(chunks),
+                "checked_bit_for_bit_at": "G16, 4800 frames", "reference_g16_s": round(ref_s, 1),
+                "reported_rows_g16_min_max": [min(reported), max(reported)],
+                "best_config_hota_launches": best, "wall_rounds": len(res["sweep_wall_ms"])}
+        for k, v in res.items():
+            if v:
+                line[k] = round(statistics.median(v), 3)
+                line[k + "_min"] = round(min(v), 3)
+                line[k + "_max"] = round(max(v), 3)
+        line["update_x_g_over_sweep"] = round(line["update_x_g_kernel_us"] / line["sweep_kernel_us"], 2)
+        line["sweep_kernel_over_forward"] = round(line["sweep_kernel_us"] / line["forward_replay_us"], 3)
+        print(json.dumps(line), flush=True)
+
+
 def frame_shift_leg(reps, rounds):
     """rtdetr_frame_shift at predict's shape (F 16 frames of one sequence, 704 x
     1248, the defaults of track.TrackArgs: radius 48, gate 0.1) against
@@ -1313,6 +1451,10 @@ def main():
     ap.add_argument("--track", action="store_true",
                     help="time rtdetr_track_update (16 frames of one sequence, K 300, about 40 live tracks) against "
                          "track_reference on the host and one forward replay, and exit")
+    ap.add_argument("--track-sweep", action="store_true",
+                    help="check rtdetr_track_sweep against tune.track_sweep_reference (8 sequences of 600 frames, K "
+                         "300), time it at G 1 / 16 / 64 against rtdetr_track_update launched G times, the host "
+                         "reference and one forward replay, time tune.sweep's stages, and exit")
     ap.add_argument("--frame-shift", action="store_true",
                     help="check rtdetr_frame_shift against motion.sequence_shifts, then time it against the host and "
                          "a forward replay, and exit")
@@ -1366,6 +1508,9 @@ def main():
         return
     if a.track:
         track_leg(a.reps, a.rounds)
+        return
+    if a.track_sweep:
+        track_sweep_leg(a.reps, a.rounds)
         return
     if a.box_fuse:
         box_fuse_leg(a.reps, a.rounds)

@@ -7,7 +7,9 @@ one image file or a dataset yaml; frames may have any size.  --tiles 2x2 adds
 sliced inference: every frame is also detected on a grid of crops and the passes
 are merged (engine.predict).  --track links the detections of consecutive frames
 (a sequence: the images of one directory) by track id and also writes tracks.json
-and mot/<sequence>.txt; scripts/track_detector.py is the same thing.
+and mot/<sequence>.txt; scripts/track_detector.py is the same thing.  --save-det
+(without --track) also writes det/<sequence>.txt, the detections as MOTChallenge
+text: the input of scripts/tune_tracker.py.
 """
 from __future__ import annotations
 
@@ -72,7 +74,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--eval-iou", type=float, default=0.5, help="--gt: the IoU a match needs")
     ap.add_argument("--hota", action="store_true",
                     help="--gt: also score HOTA (DetA, AssA, LocA over 19 IoU thresholds)")
+    ap.add_argument("--save-det", action="store_true",
+                    help="also write det/<sequence>.txt, the detections as MOTChallenge text for "
+                         "scripts/tune_tracker.py (not with --track)")
     a = ap.parse_args(argv)
+    if a.save_det and a.track:
+        ap.error("--save-det writes an untracked run's detections: not with --track")
     if a.gt is not None and not a.track:
         ap.error("--gt needs --track")
     if a.hota and a.gt is None:
@@ -135,7 +142,7 @@ def main(argv=None) -> None:
                          name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
                          tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
                          class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou,
-                         track=tracker_args(a), **gt_args(a))
+                         track=tracker_args(a), **gt_args(a), **({"save_det": True} if a.save_det else {}))
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
     if a.track:
@@ -149,6 +156,8 @@ def main(argv=None) -> None:
             print(f"Saved tracking metrics -> {res.save_dir / 'mot_metrics.json'}")
     print("speed ms/img: " + ", ".join(f"{k} {v:.3f}" for k, v in res.speed.items()))
     print(f"Saved predictions -> {res.save_dir / 'predictions.json'}")
+    if a.save_det:
+        print(f"Saved detections -> {res.save_dir / 'det'}")
 
 
 if __name__ == "__main__":

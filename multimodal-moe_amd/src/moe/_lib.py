@@ -124,6 +124,8 @@ SIGNATURES = {
                                  _P, _P, _P, _P, _P]),
     "rtdetr_track_update_shift": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _F, _F, _I,
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rtdetr_track_sweep": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                _P]),
     "rtdetr_frame_shift": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P,
                                 _P]),
     "rtdetr_mot_eval": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P,
@@ -225,7 +227,8 @@ def lib() -> ctypes.CDLL:
 PROF_KINDS = {0: "grouped_gemm", 1: "dispatch", 2: "router", 3: "route_scan", 4: "token_bwd", 5: "msda",
               6: "mx_quant", 7: "conv_epilogue", 8: "optimizer", 9: "matcher", 10: "grouped_gemm_fp8",
               11: "linear_wgrad", 12: "attention", 13: "conv", 14: "router_wgrad", 15: "augment",
-              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge", 20: "track", 21: "motion"}
+              16: "eval_match", 17: "route_stats", 18: "resize", 19: "merge", 20: "track", 21: "motion",
+              22: "track_sweep"}
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0   # MI355X dense fp8 / MXFP8 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
@@ -1164,6 +1167,87 @@ def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset,
         _check(lib().rtdetr_track_update(*common, _stream()), "rtdetr_track_update")
     else:
         _check(lib().rtdetr_track_update_shift(*common, _ptr(shift), _stream()), "rtdetr_track_update_shift")
+    return out
+
+
+TRACK_MAX_G = 1024  # rtdetr_track_sweep's limit on the configurations of one launch
+SWEEP_F = ("track_high", "track_low", "new_thr", "match_iou", "second_iou", "alpha", "beta")  # params_f's columns
+SWEEP_I = ("max_age", "min_hits", "class_agnostic")                                           # params_i's columns
+
+
+def track_sweep(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, configs, out=None, shift=None):
+    """The tracker under G configurations, one launch for the batch
+    (rtdetr_track_sweep: track.track_reference per frame and configuration, bit
+    for bit).  ``state``: a track.SweepState (G x S state slots of T tracks,
+    updated in place); the inputs as track_update's, shared by all
+    configurations; ``configs``: G track.TrackArgs (validated by their own
+    constructor, which is what keeps NaN and bad counts out of the device
+    tables); ``shift`` fp32 [F, 2] or None.  -> (out_id int32 [G, F, T],
+    out_boxes fp32 [G, F, T, 4], out_row int32 [G, F, T], count int32 [G, F]),
+    the compact report, every element written.  ``out``: that tuple to write
+    into instead of new tensors."""
+    from ..rtdetr_moe.track import TrackArgs
+
+    _need(boxes, torch.float32, "boxes")
+    _need(scores, torch.float32, "scores")
+    _need(labels, torch.int32, "labels")
+    _need(frame_slot, torch.int32, "frame_slot")
+    _need(frame_reset, torch.int32, "frame_reset")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4:
+        raise MoEKernelError("track_sweep: boxes must be [F, K, 4]")
+    F, K, _ = (int(v) for v in boxes.shape)
+    if tuple(scores.shape) != (F, K) or tuple(labels.shape) != (F, K):
+        raise MoEKernelError("track_sweep: scores / labels must be [F, K]")
+    if tuple(frame_slot.shape) != (F,) or tuple(frame_reset.shape) != (F,):
+        raise MoEKernelError("track_sweep: frame_slot / frame_reset must be [F]")
+    if n_valid is not None:
+        _need(n_valid, torch.int32, "n_valid")
+        if tuple(n_valid.shape) != (F,):
+            raise MoEKernelError("track_sweep: n_valid must be [F]")
+    configs = list(configs)
+    G, S, T = state.G, state.S, state.T
+    if len(configs) != G or not all(isinstance(c, TrackArgs) for c in configs):
+        raise MoEKernelError(f"track_sweep: configs must be {G} TrackArgs (the state's G)")
+    st_shapes = ((G, S, T, 8), (G, S, T), (G, S, T, 4), (G, S, 2))
+    st_dtypes = (torch.float32, torch.float32, torch.int32, torch.int32)
+    for t, s, d, name in zip(state.tensors(), st_shapes, st_dtypes, ("state.box", "state.score", "state.meta",
+                                                                    "state.seq")):
+        _need(t, d, name)
+        if tuple(t.shape) != s or not t.is_contiguous():
+            raise MoEKernelError(f"track_sweep: {name} must be contiguous {s}, got {tuple(t.shape)}")
+    dev = boxes.device
+    shapes = ((G, F, T), (G, F, T, 4), (G, F, T), (G, F))
+    dtypes = (torch.int32, torch.float32, torch.int32, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    else:
+        if len(out) != 4:
+            raise MoEKernelError("track_sweep: out must be (out_id, out_boxes, out_row, count)")
+        for t, s, d, name in zip(out, shapes, dtypes, ("out_id", "out_boxes", "out_row", "count")):
+            _need(t, d, name)
+            if tuple(t.shape) != s or not t.is_contiguous():
+                raise MoEKernelError(f"track_sweep: {name} must be contiguous {s}, got {tuple(t.shape)}")
+    for t, name in ((boxes, "boxes"), (scores, "scores"), (labels, "labels")):
+        if not t.is_contiguous():
+            raise MoEKernelError(f"track_sweep: {name} must be contiguous")
+    pf = torch.tensor([[float(getattr(c, k)) for k in SWEEP_F] for c in configs], dtype=torch.float32).reshape(G, 7)
+    pi = torch.tensor([[int(getattr(c, k)) for k in SWEEP_I] for c in configs], dtype=torch.int32).reshape(G, 3)
+    if bool(torch.isnan(pf).any()) or bool((pi[:, 0] < 0).any()) or bool((pi[:, 1] < 1).any()):
+        raise MoEKernelError("track_sweep: a configuration holds a NaN, max_age < 0 or min_hits < 1")
+    pf, pi = pf.to(dev), pi.to(dev)
+    tensors = [boxes, scores, labels, frame_slot, frame_reset, *state.tensors(), *out]
+    tensors += [n_valid] if n_valid is not None else []
+    if shift is not None:
+        _need(shift, torch.float32, "shift")
+        if tuple(shift.shape) != (F, 2) or not shift.is_contiguous():
+            raise MoEKernelError("track_sweep: shift must be contiguous [F, 2]")
+        tensors.append(shift)
+    if any(t.device != dev for t in tensors):
+        raise MoEKernelError("track_sweep: all tensors must be on one device")
+    rc = lib().rtdetr_track_sweep(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), _ptr(frame_slot),
+                                  _ptr(frame_reset), F, K, S, T, G, _ptr(pf), _ptr(pi),
+                                  *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out), _ptr(shift), _stream())
+    _check(rc, "rtdetr_track_sweep")
     return out
 
 

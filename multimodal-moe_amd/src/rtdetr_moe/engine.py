@@ -827,3 +827,38 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
     return DetMetrics(results_dict=_results_dict(box), box=box, speed=speed, model=ModelHandle(model),
                       save_dir=save_dir, moe=_moe_stats(model), context=report, size=sizes)
 
+
+
+# ---------------------------------------------------------------------------
+# tracker tuning
+# ---------------------------------------------------------------------------
+def tune_tracker(det, gt, grid, device="0", gt_classes=None, gt_ignore_classes=(), out=None, **kw) -> dict:
+    """Sweep a grid of tracker arguments over detection files and score every
+    configuration against ground truth (tune.sweep).  ``det``: a directory of
+    ``<key>/det/det.txt`` or ``<key>.txt`` files (tune.load_det;
+    predict(save_det=True) writes them, MOTChallenge's public detections read
+    the same way); ``gt``: MOTChallenge ground truth for the same keys
+    (moteval.load_gt with ``gt_classes`` / ``gt_ignore_classes``); ``grid``:
+    {field: [values]} over tune.SWEEPABLE, or a list of configurations.  On a
+    GPU ``device`` all configurations are tracked in ONE HIP launch per chunk of
+    frames (rtdetr_track_sweep) and scored by the evaluators' kernels; "cpu"
+    runs the references and gives the same dict.  ``out``: a directory that
+    receives tracker_sweep.json.  Every other argument is tune.sweep's (base,
+    eval_iou, hota, metric, shifts)."""
+    from . import moteval, tune
+
+    devices = parse_device(device)
+    dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
+    if dev.type == "cuda":
+        torch.cuda.set_device(dev)
+        from ..moe import _lib
+
+        _lib.lib()
+    keys = tune.sequence_keys(det)
+    dets = tune.load_det(det, keys)
+    truth = moteval.load_gt(gt, keys, gt_classes, gt_ignore_classes)
+    res = tune.sweep(dets, truth, grid, device=dev, **kw)
+    if out is not None:
+        Path(out).mkdir(parents=True, exist_ok=True)
+        (Path(out) / "tracker_sweep.json").write_text(json.dumps(res))
+    return res

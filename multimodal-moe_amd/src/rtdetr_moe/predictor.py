@@ -506,12 +506,27 @@ def _load_truth(gt, seq_of, gt_classes, gt_ignore_classes) -> dict:
     return moteval.load_gt(gt, files, gt_classes, gt_ignore_classes)
 
 
-def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False, mot=None):
+def det_files(preds, seq_of) -> dict:
+    """{sequence file key: detection text} of an untracked run (tune.det_lines: frame,-1,x,y,w,h,score,class,-1,-1,
+    every fp32 value with its bits): the input of engine.tune_tracker.  ``seq_of``: frame_sequences' list."""
+    from .tune import det_lines
+
+    frames = {}
+    for p, (key, _, f) in zip(preds, seq_of):
+        frames.setdefault(key.replace("/", "_"), {})[f] = (p.boxes.numpy(), p.scores.numpy(), p.labels.numpy())
+    return {key: det_lines(fr) for key, fr in frames.items()}
+
+
+def _write_files(save_dir, preds, save_json, tracked, save_img, cmc=False, mot=None, det=None):
     """predictions.json, with a tracker tracks.json and mot/<sequence>.txt (with cmc camera_motion.json, with gt
-    mot_metrics.json), and the overlays."""
+    mot_metrics.json), with save_det det/<sequence>.txt, and the overlays."""
     save_dir.mkdir(parents=True, exist_ok=True)
     if save_json:
         (save_dir / "predictions.json").write_text(json.dumps(coco_results(preds)))
+    if det is not None:
+        (save_dir / "det").mkdir(exist_ok=True)
+        for key, text in det_files(preds, det).items():
+            (save_dir / "det" / (key + ".txt")).write_text(text)
     if tracked:
         (save_dir / "tracks.json").write_text(json.dumps(track_results(preds)))
         (save_dir / "mot").mkdir(exist_ok=True)
@@ -531,7 +546,7 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
             workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
             merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55, track=None,
             sequence_of=None, gt=None, gt_classes=None, gt_ignore_classes=(), eval_iou=0.5,
-            hota=False) -> PredictResults:
+            hota=False, save_det=False) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -640,11 +655,19 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     over 19 localisation thresholds).  On a GPU every frame is scored in a
     workgroup of its own (rtdetr_hota_*); the CPU device or MOE_TRACK_EVAL=0
     run hota.hota_reference and give the same result.  Without ``hota`` the
-    entries are what they are without it."""
+    entries are what they are without it.
+    ``save_det`` (off by default; with ``track`` a ValueError, because a tracked
+    frame holds only the reported rows): det/<sequence>.txt beside
+    predictions.json, the run's rows as MOTChallenge detection text
+    (tune.det_lines: frame,-1,x,y,w,h,score,class,-1,-1, every fp32 value with
+    its bits), sequences and frame numbers from frame_sequences as for
+    tracking -- the input of engine.tune_tracker / scripts/tune_tracker.py."""
     # engine imports this module, and tests replace engine.EvalForward and preprocess.FrameSource: looked up per call
     from . import engine, preprocess
 
     targs, tiles, fuse = _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track)
+    if save_det and targs is not None:
+        raise ValueError("save_det writes an untracked run's detections: a tracked frame holds only the reported rows")
     if gt is not None:
         from .moteval import check_thr
 
@@ -733,7 +756,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     mot = _score_tracks(preds, truth, eval_iou, dev, bool(hota)) if truth is not None else None
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
-        _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc, mot)
+        det = frame_sequences(ds.paths, sequence_of) if save_det else None
+        _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc, mot, det)
     return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=engine.ModelHandle(model), mot=mot)
 
 

@@ -12,6 +12,8 @@ that links a sequence's detections from frame to frame, stated once.
   the tracker of the CPU device and of MOE_PREDICT_TRACK=0.
 * ``TrackState``: the device buffers the kernel keeps its tracks in between
   launches, with an export to (and an import from) the reference's arrays.
+* ``SweepState``: the same for G configurations at once (tune.py's parameter
+  sweep, rtdetr_track_sweep).
 
 The rule.  A sequence owns T track slots: box (xyxy), vel (one fp32 per side),
 score, label, id, age, hits (0: the slot is free), and per sequence next_id
@@ -55,6 +57,7 @@ from dataclasses import asdict, dataclass, fields
 import numpy as np
 
 TRACK_MAX_K, TRACK_MAX_T, TRACK_MAX_F, TRACK_MAX_S = 1024, 256, 1024, 1024  # rtdetr_track_update's limits
+TRACK_MAX_G = 1024  # rtdetr_track_sweep: configurations per launch
 HITS_CAP = 1 << 30
 STATE_FIELDS = ("box", "vel", "score", "label", "id", "age", "hits")
 EVENTS = ("stage1", "stage2", "refound", "tentative_freed", "expired", "births", "dropped", "ties", "reported")
@@ -329,3 +332,47 @@ class TrackState:
         self.score[s].copy_(torch.from_numpy(np.asarray(state["score"], np.float32)))
         self.meta[s].copy_(torch.from_numpy(meta))
         self.seq[s].copy_(torch.tensor([int(state["next_id"]), int(state["dropped"])], dtype=torch.int32))
+
+
+class SweepState(TrackState):
+    """G configurations' TrackStates in one set of buffers, between launches of
+    rtdetr_track_sweep (tune.py): TrackState's layout per (g, s),
+      box fp32 [G, S, T, 8]   score fp32 [G, S, T]   meta int32 [G, S, T, 4]   seq int32 [G, S, 2]
+    """
+
+    def __init__(self, G: int, S: int, T: int, device):
+        import torch
+
+        self.G, self.S, self.T = int(G), int(S), int(T)
+        if not 1 <= self.G <= TRACK_MAX_G or not 1 <= self.S <= TRACK_MAX_S or not 1 <= self.T <= TRACK_MAX_T:
+            raise ValueError(f"SweepState: need 1 <= G <= {TRACK_MAX_G}, 1 <= S <= {TRACK_MAX_S} and "
+                             f"1 <= T <= {TRACK_MAX_T}")
+        G, S, T = self.G, self.S, self.T
+        self.box = torch.zeros((G, S, T, 8), dtype=torch.float32, device=device)
+        self.score = torch.zeros((G, S, T), dtype=torch.float32, device=device)
+        self.meta = torch.zeros((G, S, T, 4), dtype=torch.int32, device=device)
+        self.seq = torch.zeros((G, S, 2), dtype=torch.int32, device=device)
+        self.seq[..., 0] = 1
+
+    def _slot(self, g: int, s: int) -> TrackState:
+        """Configuration g's slots as a TrackState over the same memory."""
+        view = TrackState.__new__(TrackState)
+        view.S, view.T = self.S, self.T
+        view.box, view.score, view.meta, view.seq = (t[g] for t in self.tensors())
+        return view
+
+    def export(self, g: int, s: int) -> dict:
+        """Slot s of configuration g as the reference's named arrays."""
+        return self._slot(g, s).export(s)
+
+    def export_all(self) -> list:
+        """[g][s] -> the reference's named arrays, with one copy per buffer."""
+        box, score, meta, seq = (t.cpu().numpy() for t in self.tensors())
+        return [[{"box": box[g, s, :, :4].copy(), "vel": box[g, s, :, 4:].copy(), "score": score[g, s].copy(),
+                  "label": meta[g, s, :, 0].copy(), "id": meta[g, s, :, 1].copy(), "age": meta[g, s, :, 2].copy(),
+                  "hits": meta[g, s, :, 3].copy(), "next_id": int(seq[g, s, 0]), "dropped": int(seq[g, s, 1])}
+                 for s in range(self.S)] for g in range(self.G)]
+
+    def load(self, g: int, s: int, state: dict):
+        """Slot s of configuration g from the reference's named arrays."""
+        self._slot(g, s).load(s, state)

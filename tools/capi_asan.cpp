@@ -235,6 +235,29 @@ int main() {
     std::printf("FAIL hota F=0 / S=0 must succeed\n");
     ++g_fail;
   }
+  // the tracker's parameter sweep: F, K, S, T, G, then one operand replaced
+  auto sweep = [&](int F, int K, int S, int T, int G, const float* pf, const int32_t* pi, float* obox, float* tbox,
+                   int32_t* orow) {
+    return rtdetr_track_sweep(f32, f32, i32, nullptr, i32, i32, F, K, S, T, G, pf, pi, tbox, f32, i32, i32, i32, obox,
+                              orow, i32, nullptr, s);
+  };
+  expect_error("track_sweep G=0", sweep(1, 8, 1, 4, 0, f32, i32, f32, f32, i32));
+  expect_error("track_sweep G=1025", sweep(1, 8, 1, 4, 1025, f32, i32, f32, f32, i32));
+  expect_error("track_sweep T=257", sweep(1, 8, 1, 257, 2, f32, i32, f32, f32, i32));
+  expect_error("track_sweep T=0", sweep(1, 8, 1, 0, 2, f32, i32, f32, f32, i32));
+  expect_error("track_sweep K=1025", sweep(1, 1025, 1, 4, 2, f32, i32, f32, f32, i32));
+  expect_error("track_sweep F=1025", sweep(1025, 8, 1, 4, 2, f32, i32, f32, f32, i32));
+  expect_error("track_sweep S=0 with frames", sweep(1, 8, 0, 4, 2, f32, i32, f32, f32, i32));
+  expect_error("track_sweep params_f=NULL", sweep(1, 8, 1, 4, 2, nullptr, i32, f32, f32, i32));
+  expect_error("track_sweep params_i=NULL", sweep(1, 8, 1, 4, 2, f32, nullptr, f32, f32, i32));
+  expect_error("track_sweep out_row=NULL", sweep(1, 8, 1, 4, 2, f32, i32, f32, f32, nullptr));
+  expect_error("track_sweep out_boxes misaligned", sweep(1, 8, 1, 4, 2, f32, i32, f32 + 1, f32, i32));
+  expect_error("track_sweep trk_box misaligned", sweep(1, 8, 1, 4, 2, f32, i32, f32, f32 + 1, i32));
+  ++g_n;
+  if (sweep(0, 8, 0, 4, 2, f32, i32, nullptr, nullptr, nullptr) != 0) {  // F == 0: success, no launch
+    std::printf("FAIL track_sweep F=0 must succeed\n");
+    ++g_fail;
+  }
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
