@@ -1001,6 +1001,41 @@ int rtdetr_track_sweep(const float* boxes, const float* scores, const int32_t* l
                        int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* out_row,
                        int32_t* count, const float* frame_shift, hipStream_t stream);
 
+/* The tracker with a choice of association (TrackArgs.assoc, the rule:
+ * src/rtdetr_moe/track.py, step 4): rtdetr_track_update_shift's arguments plus
+ * ``assoc`` after frame_shift (which may be NULL): 0 greedy -- the decisions and
+ * boxes of rtdetr_track_update_shift bit for bit -- or 1 lsap; any other value
+ * is refused.  With lsap each stage's admissible pairs are pruned to the slots
+ * and rows that have one, and the one-to-one matching with the largest total
+ * IoU is found by the library's linear_sum_assignment solver inside the
+ * tracker's workgroup (tracks in LDS, the cost computed from the boxes, no cost
+ * matrix in memory); a returned pair is a match only if it is admissible.  The
+ * kernel is an instantiation of its own: the three entries above run the code
+ * they ran before.  It needs up to 85.4 KiB of LDS (K = 1024, T = 256) and
+ * raises its dynamic-LDS limit itself.  Operands, limits, refusals and the
+ * profiler kind as rtdetr_track_update's. */
+int rtdetr_track_update_assoc(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                              const int32_t* frame_slot, const int32_t* frame_reset, int F, int K, int S, int T,
+                              float track_high, float track_low, float new_thr, float match_iou, float second_iou,
+                              int max_age, int min_hits, float alpha, float beta, int class_agnostic, float* trk_box,
+                              float* trk_score, int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id,
+                              float* out_boxes, int32_t* count, const float* frame_shift, int assoc,
+                              hipStream_t stream);
+
+/* rtdetr_track_sweep with the association as a swept parameter: its arguments
+ * plus params_assoc int32 [G] after frame_shift, configuration g's ``assoc`` (0
+ * greedy, 1 lsap; the caller guarantees the values, any other is taken as
+ * lsap); params_i stays [G][3].  Workgroup (s, g) branches on its
+ * configuration's value, so one launch mixes both.  All-greedy tables give
+ * rtdetr_track_sweep's outputs and state bit for bit.  NULL params_assoc is
+ * refused; everything else as rtdetr_track_sweep's. */
+int rtdetr_track_sweep_assoc(const float* boxes, const float* scores, const int32_t* labels, const int32_t* n_valid,
+                             const int32_t* frame_slot, const int32_t* frame_reset, int F, int K, int S, int T, int G,
+                             const float* params_f, const int32_t* params_i, float* trk_box, float* trk_score,
+                             int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* out_row,
+                             int32_t* count, const float* frame_shift, const int32_t* params_assoc,
+                             hipStream_t stream);
+
 /* Camera-motion compensation for the tracker (TrackArgs.cmc): the global shift
  * of each frame against its predecessor, motion.sequence_shifts on the host bit
  * for bit (the rule: src/rtdetr_moe/motion.py).  It measures on the model's
@@ -1504,9 +1539,9 @@ enum moe_prof_kind {
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
   MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
   MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
-  MOE_PROF_TRACK = 20,     /* tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift]) */
+  MOE_PROF_TRACK = 20,     /* tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift|_assoc]) */
   MOE_PROF_MOTION = 21,    /* tracking: a frame's global shift against its predecessor (rtdetr_frame_shift) */
-  MOE_PROF_TRACK_SWEEP = 22 /* tracker tuning: every configuration of a parameter grid in one launch (rtdetr_track_sweep) */
+  MOE_PROF_TRACK_SWEEP = 22 /* tracker tuning: every configuration of a parameter grid in one launch (rtdetr_track_sweep[_assoc]) */
 };
 int moe_profile_enable(int on);
 int moe_profile_count(void);

@@ -14,6 +14,15 @@
 // m, -1 for m >= n.  smem: M * 8 + 2 * Q * 8 + 3 * Q * 4 + M * 4 + M + Q bytes,
 // 8-byte aligned.  Consecutive solves of one workgroup reuse smem and the static
 // shared scalars below: put a __syncthreads() between them.
+//
+// lsap_solve<true> is the same solver inside a wider workgroup (the tracker's,
+// up to 256 threads): threads 0..63 are the solver, threads 64 and up do no work
+// and take the same barriers.  Every branch that lies between two barriers is
+// then decided by a block-uniform value: the arguments n, Q, M; the loop counters
+// cur and nrem; and s_sink and s_minval, read from LDS after the barrier that
+// follows lane 0's write and before the barrier that precedes its next write
+// (s_minval is L, which only the solver's wave holds in a register).  With
+// kWide == false nothing changes: the code is the one-wave form.
 #pragma once
 
 #include "moe_common.h"
@@ -43,7 +52,7 @@ struct MatrixCost {
   __device__ __forceinline__ float operator()(int q, int m) const { return C[(size_t)q * M + m]; }
 };
 
-template <class CostFn>
+template <bool kWide = false, class CostFn>
 __device__ void lsap_solve(const CostFn& cost_qm, int n, int Q, int M, int32_t* __restrict__ out,
                            int32_t* __restrict__ status, char* smem) {
   double* u = reinterpret_cast<double*>(smem);  // [M]
@@ -58,7 +67,9 @@ __device__ void lsap_solve(const CostFn& cost_qm, int n, int Q, int M, int32_t* 
   __shared__ int s_i, s_sink, s_index;
   __shared__ double s_minval;
 
-  const int lane = threadIdx.x;
+  // an idle thread of the wide form: a lane past every bound, so every "lane, lane + 64, ..." loop below is empty
+  // for it and it is never lane 0
+  const int lane = (!kWide || threadIdx.x < 64) ? (int)threadIdx.x : 0x40000000;
   for (int m = lane; m < M; m += 64) out[m] = -1;
   if (n <= 0) return;
   if (n > Q || n > M) {
@@ -137,7 +148,9 @@ __device__ void lsap_solve(const CostFn& cost_qm, int n, int Q, int M, int32_t* 
       }
       --nrem;
       __syncthreads();
-      if (s_sink != -1 || L == INFINITY || nrem == 0) break;  // nrem == 0 only if infeasible
+      // wide: lane 0 stored L in s_minval before the barrier above and writes it next after the next one
+      const double Lb = kWide ? s_minval : L;
+      if (s_sink != -1 || Lb == INFINITY || nrem == 0) break;  // nrem == 0 only if infeasible
     }
     const double minval = s_minval;
     if (s_sink == -1) {  // infeasible (non-finite costs)

@@ -38,9 +38,9 @@ enum ProfKind {
   PROF_ROUTE_STATS = 17,   // validation: per-context routing statistics (moe_route_stats)
   PROF_RESIZE = 18,        // inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8)
   PROF_MERGE = 19,         // tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse)
-  PROF_TRACK = 20,         // tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift])
+  PROF_TRACK = 20,         // tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift|_assoc])
   PROF_MOTION = 21,        // tracking: a frame's global shift against its predecessor (rtdetr_frame_shift)
-  PROF_TRACK_SWEEP = 22    // tracker tuning: every configuration of a parameter grid in one launch (rtdetr_track_sweep)
+  PROF_TRACK_SWEEP = 22    // tracker tuning: every configuration of a parameter grid in one launch (rtdetr_track_sweep[_assoc])
 };
 
 class ProfScope {

@@ -44,7 +44,23 @@
 // LDS (dynamic, every offset a multiple of 16): rows 28 K bytes, tracks 52 T
 // bytes, the free list 4 T, 192 bytes of keys and counters: 41.2 KiB at the
 // limits K = 1024, T = 256.
+//
+// rtdetr_track_update_assoc / rtdetr_track_sweep_assoc (TrackArgs.assoc) are trk_run<.., kAssoc = true>: a second
+// pair of kernels, so that the three entries above keep the code they had (kAssoc = false compiles none of what
+// follows).  With assoc != 0 (block-uniform: a launch's argument, or the configuration's table entry) step 2 of a
+// stage is track.py's step 4 "lsap" instead of the greedy rounds:
+//   a. every eligible track scans the stage's rows as the greedy scan does, notes whether it has an admissible row
+//      and marks those rows in an LDS flag array (plain stores of 1; several tracks may mark one row);
+//   b. the tracks with a row and the marked rows are compacted into two ascending index lists (trk_block_rank);
+//   c. lsap_solve<true> (lsap.h: threads 0..63 solve, the other waves take the same barriers) on the pruned problem,
+//      the larger side as the queries (equal: the tracks), cost -(iou if admissible else 0) computed by TrkCost from
+//      the boxes in LDS through the two lists -- the predicted boxes are stored to tbox before the stage for this;
+//   d. a returned pair that is admissible sets rstate[row] and the track's matched row.
+// Its LDS is TrkLds plus TrkAssocLds: the lists 4 T + 4 K, the flags 4 K, the matched rows 4 T, the solver's out 4 M
+// and scratch 12 M + 29 Q + M bytes at Q = max(T, K), M = min(T, K): 85.4 KiB at the limits, raised past the 64 KiB
+// default with allow_dyn_lds.
 #include "moe_common.h"
+#include "lsap.h"
 #include "prof.h"
 
 #pragma clang fp contract(off)
@@ -77,6 +93,22 @@ struct TrkLds {
   }
 };
 
+// what kAssoc adds after TrkLds's bytes
+constexpr size_t kTrkStaticLds = 32;  // lsap_solve's shared scalars
+struct TrkAssocLds {
+  size_t slist, rlist, aflag, smatch, aout, solver, total;
+  __host__ __device__ TrkAssocLds(int K, int T) {
+    const size_t Q = K > T ? K : T, M = K > T ? T : K;
+    slist = TrkLds(K, T).total;                          // int32 [T]: the tracks with an admissible row, ascending
+    rlist = slist + trk_up16((size_t)T * 4);             // int32 [K]: the rows with an admissible track, ascending
+    aflag = rlist + trk_up16((size_t)K * 4);             // int32 [K]: row d is marked
+    smatch = aflag + trk_up16((size_t)K * 4);            // int32 [T]: the row the solve gave track t, -1
+    aout = smatch + trk_up16((size_t)T * 4);             // int32 [M]: lsap_solve's out
+    solver = aout + trk_up16(M * 4);                     // lsap_solve's scratch
+    total = solver + trk_up16(M * 8 + 2 * Q * 8 + 3 * Q * 4 + M * 4 + M + Q);
+  }
+};
+
 struct TrkParams {
   float track_high, track_low, new_thr, match_iou, second_iou, alpha, beta;
   int max_age, min_hits, class_agnostic;
@@ -92,6 +124,36 @@ __device__ __forceinline__ float trk_iou(float4 t, float ta, float4 d) {
   const float den = (ta + trk_area(d)) - inter;
   return den > 0.f ? __fdiv_rn(inter, den) : 0.f;
 }
+
+// the admissibility of (track, row) under the stage's threshold, and the pair's iou: the one statement of it for the
+// lsap stage's scan, its cost and its matches, so that the three agree to the bit
+__device__ __forceinline__ bool trk_adm(float4 t, float ta, int tlabel, float4 d, int dlabel, float thr,
+                                        int agnostic, float* iou) {
+  *iou = 0.f;
+  if (!agnostic && dlabel != tlabel) return false;
+  *iou = trk_iou(t, ta, d);
+  return *iou > thr;  // false for NaN
+}
+
+// lsap_solve's cost of (query, target) through the two index lists: -(iou if admissible else 0)
+struct TrkCost {
+  const float4* tbox;
+  const int4* tmeta;
+  const float4* rbox;
+  const int32_t* rlabel;
+  const int32_t* slist;
+  const int32_t* rlist;
+  float thr;
+  int agnostic;
+  bool sq;  // the tracks are the queries
+  __device__ __forceinline__ float operator()(int q, int m) const {
+    const int t = slist[sq ? q : m], d = rlist[sq ? m : q];
+    const float4 tb = tbox[t];
+    float iou;
+    const bool adm = trk_adm(tb, trk_area(tb), tmeta[t].x, rbox[d], rlabel[d], thr, agnostic, &iou);
+    return -(adm ? iou : 0.f);
+  }
+};
 
 __device__ __forceinline__ unsigned long long trk_wave_max(unsigned long long v) {
   for (int off = 32; off > 0; off >>= 1) {
@@ -125,13 +187,14 @@ __device__ __forceinline__ int trk_block_rank(bool flag, int32_t* wcnt, int lane
 // track_sweep_kernel.  gbox / gscore / gmeta / gseq are the state slot's own buffers; out_id, out_boxes, out_row and
 // count are the launch's (the configuration's, in a sweep).  kCompact chooses the form of step 5: false, out_id [F][K]
 // and out_boxes [F][K][4] per row (out_row unused); true, the reported rows alone, in row order, in out_id [F][T],
-// out_boxes [F][T][4] and out_row [F][T], padded with -1 / zeros / -1.
-template <bool kCompact>
+// out_boxes [F][T][4] and out_row [F][T], padded with -1 / zeros / -1.  kAssoc: the kernels that take ``assoc`` (0
+// greedy, else lsap; block-uniform); with kAssoc false ``assoc`` is not read and none of the lsap stage is compiled.
+template <bool kCompact, bool kAssoc>
 __device__ __forceinline__ void trk_run(
     const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
     const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
-    const int s, const TrkParams& p, float4* __restrict__ gbox, float* __restrict__ gscore,
+    const int s, const TrkParams& p, const int assoc, float4* __restrict__ gbox, float* __restrict__ gscore,
     int4* __restrict__ gmeta, int32_t* __restrict__ gseq, int32_t* __restrict__ out_id,
     float* __restrict__ out_boxes, int32_t* __restrict__ out_row, int32_t* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -148,6 +211,12 @@ __device__ __forceinline__ void trk_run(
   unsigned long long* wkey = reinterpret_cast<unsigned long long*>(smem + o.wkey);
   int32_t* wcnt = reinterpret_cast<int32_t*>(smem + o.wcnt);
   int32_t* ctl = reinterpret_cast<int32_t*>(smem + o.ctl);
+  const TrkAssocLds oa(K, T);  // used with kAssoc only
+  int32_t* slist = reinterpret_cast<int32_t*>(smem + oa.slist);
+  int32_t* rlist = reinterpret_cast<int32_t*>(smem + oa.rlist);
+  int32_t* aflag = reinterpret_cast<int32_t*>(smem + oa.aflag);
+  int32_t* smatch = reinterpret_cast<int32_t*>(smem + oa.smatch);
+  int32_t* aout = reinterpret_cast<int32_t*>(smem + oa.aout);
 
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
@@ -223,6 +292,7 @@ __device__ __forceinline__ void trk_run(
           const float sx = frame_shift[2 * f], sy = frame_shift[2 * f + 1];
           tb = make_float4(tb.x + sx, tb.y + sy, tb.z + sx, tb.w + sy);
         }
+        if (kAssoc) tbox[tid] = tb;  // TrkCost reads other tracks' predicted boxes; step 3 stores every live box again
       }
     }
     if (tid == 0) ctl[2] = 0;
@@ -235,6 +305,54 @@ __device__ __forceinline__ void trk_run(
       const int want = stage == 0 ? kRowHigh : kRowLow;
       const float thr = stage == 0 ? p.match_iou : p.second_iou;
       const bool eligible = mine && m.w > 0 && matched < 0 && (stage == 0 || (m.z == 0 && m.w >= p.min_hits));
+      if (kAssoc && assoc != 0) {  // block-uniform: the lsap stage (the file's head, a-d)
+        for (int d = tid; d < K; d += nthr) aflag[d] = 0;
+        if (mine) smatch[tid] = -1;
+        __syncthreads();
+        bool has = false;  // a. this track has an admissible row
+        if (eligible) {
+          for (int d = 0; d < K; ++d) {
+            if (rstate[d] != want) continue;  // wave-uniform
+            float iou;
+            if (!trk_adm(tb, ta, m.x, rbox[d], rlabel[d], thr, p.class_agnostic, &iou)) continue;
+            has = true;
+            aflag[d] = 1;
+          }
+        }
+        __syncthreads();
+        int ns = 0, nr = 0;  // b. block-uniform: the tracks and the rows that are kept
+        const int srank = trk_block_rank(has, wcnt, lane, wave, nwaves, &ns);
+        if (has) slist[srank] = tid;
+        for (int base = 0; base < K; base += nthr) {
+          const int d = base + tid;
+          const bool marked = d < K && aflag[d] != 0;
+          int nc = 0;
+          const int j = nr + trk_block_rank(marked, wcnt, lane, wave, nwaves, &nc);
+          if (marked) rlist[j] = d;
+          nr += nc;
+        }
+        __syncthreads();
+        if (ns > 0) {  // block-uniform; a kept track has a kept row, so nr > 0 too
+          const bool sq = ns >= nr;
+          const int n = sq ? nr : ns;
+          lsap_solve<true>(TrkCost{tbox, tmeta, rbox, rlabel, slist, rlist, thr, p.class_agnostic, sq}, n,
+                           sq ? ns : nr, n, aout, &ctl[3], smem + oa.solver);  // c.
+          __syncthreads();
+          for (int mm = tid; mm < n; mm += nthr) {  // d.
+            const int q = aout[mm];
+            if (q < 0) continue;
+            const int t = slist[sq ? q : mm], d = rlist[sq ? mm : q];
+            const float4 b = tbox[t];
+            float iou;
+            if (!trk_adm(b, trk_area(b), tmeta[t].x, rbox[d], rlabel[d], thr, p.class_agnostic, &iou)) continue;
+            rstate[d] = t;
+            smatch[t] = d;
+          }
+          __syncthreads();  // rstate and smatch, before the next stage and the steps below read them
+          if (has && smatch[tid] >= 0) matched = smatch[tid];
+        }
+        continue;
+      }
       unsigned long long key = 0ull;
       bool scan = eligible;
       int taken = -1;  // the row the last round matched: taken, whether or not its rstate write has landed
@@ -409,10 +527,62 @@ __global__ __launch_bounds__(256) void track_update_kernel(
     float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
     int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ count) {
   const int s = blockIdx.x;
-  trk_run<false>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p,
+  trk_run<false, false>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p, 0,
                  reinterpret_cast<float4*>(trk_box) + (size_t)s * T * 2, trk_score + (size_t)s * T,
                  reinterpret_cast<int4*>(trk_meta) + (size_t)s * T, seq_meta + 2 * (size_t)s, out_id, out_boxes,
                  nullptr, count);
+}
+
+// track_update_kernel with the association chosen by ``assoc`` (rtdetr_track_update_assoc)
+__global__ __launch_bounds__(256) void track_update_assoc_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
+    const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
+    TrkParams p, int assoc, float* __restrict__ trk_box,
+    float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
+    int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ count) {
+  const int s = blockIdx.x;
+  trk_run<false, true>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p, assoc,
+                       reinterpret_cast<float4*>(trk_box) + (size_t)s * T * 2, trk_score + (size_t)s * T,
+                       reinterpret_cast<int4*>(trk_meta) + (size_t)s * T, seq_meta + 2 * (size_t)s, out_id, out_boxes,
+                       nullptr, count);
+}
+
+__device__ __forceinline__ TrkParams trk_table_params(const float* __restrict__ params_f,
+                                                      const int32_t* __restrict__ params_i, int g) {
+  const float* pf = params_f + (size_t)g * kTrkSweepF;
+  const int32_t* pi = params_i + (size_t)g * kTrkSweepI;
+  TrkParams p;
+  p.track_high = pf[0];
+  p.track_low = pf[1];
+  p.new_thr = pf[2];
+  p.match_iou = pf[3];
+  p.second_iou = pf[4];
+  p.alpha = pf[5];
+  p.beta = pf[6];
+  p.max_age = pi[0];
+  p.min_hits = pi[1];
+  p.class_agnostic = pi[2] != 0 ? 1 : 0;
+  return p;
+}
+
+// track_sweep_kernel with configuration g's association in params_assoc[g] (rtdetr_track_sweep_assoc)
+__global__ __launch_bounds__(256) void track_sweep_assoc_kernel(
+    const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ n_valid, const int32_t* __restrict__ frame_slot,
+    const int32_t* __restrict__ frame_reset, const float* __restrict__ frame_shift, int F, int K, int S, int T,
+    const float* __restrict__ params_f, const int32_t* __restrict__ params_i,
+    const int32_t* __restrict__ params_assoc, float* __restrict__ trk_box,
+    float* __restrict__ trk_score, int32_t* __restrict__ trk_meta, int32_t* __restrict__ seq_meta,
+    int32_t* __restrict__ out_id, float* __restrict__ out_boxes, int32_t* __restrict__ out_row,
+    int32_t* __restrict__ count) {
+  const int s = blockIdx.x, g = blockIdx.y;
+  const TrkParams p = trk_table_params(params_f, params_i, g);
+  const size_t gs = (size_t)g * S + s, gf = (size_t)g * F;
+  trk_run<true, true>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p,
+                      params_assoc[g], reinterpret_cast<float4*>(trk_box) + gs * T * 2, trk_score + gs * T,
+                      reinterpret_cast<int4*>(trk_meta) + gs * T, seq_meta + 2 * gs, out_id + gf * T,
+                      out_boxes + gf * T * 4, out_row + gf * T, count + gf);
 }
 
 // The parameter sweep (tune.py): workgroup (s, g) runs state slot s under configuration g of the two tables, on the
@@ -440,7 +610,7 @@ __global__ __launch_bounds__(256) void track_sweep_kernel(
   p.min_hits = pi[1];
   p.class_agnostic = pi[2] != 0 ? 1 : 0;
   const size_t gs = (size_t)g * S + s, gf = (size_t)g * F;
-  trk_run<true>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p,
+  trk_run<true, false>(boxes, scores, labels, n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, s, p, 0,
                 reinterpret_cast<float4*>(trk_box) + gs * T * 2, trk_score + gs * T,
                 reinterpret_cast<int4*>(trk_meta) + gs * T, seq_meta + 2 * gs, out_id + gf * T, out_boxes + gf * T * 4,
                 out_row + gf * T, count + gf);
@@ -450,12 +620,25 @@ __global__ __launch_bounds__(256) void track_sweep_kernel(
 
 using namespace moe;
 
+// the dynamic LDS of the kAssoc kernels at (K, T), raised past the 64 KiB default once per device; only a shape
+// past the CU's 160 KiB is refused (none within the limits is: 85.4 KiB at K = 1024, T = 256)
+static int track_assoc_lds(const std::string& what, const void* kernel, unsigned long long* done, int K, int T,
+                           size_t* shmem) {
+  *shmem = TrkAssocLds(K, T).total;
+  if (*shmem + kTrkStaticLds > 160 * 1024) return fail(what + ": K / T too large for the 160 KiB of LDS");
+  if (*shmem + kTrkStaticLds <= 64 * 1024) return 0;
+  return allow_dyn_lds(kernel, (int)TrkAssocLds(kTrkMaxK, kTrkMaxT).total, done, (what + ": LDS attribute").c_str());
+}
+
+// assoc < 0: the entries without the argument (track_update_kernel); 0 / 1: rtdetr_track_update_assoc
 static int track_update(const std::string& what, const float* boxes, const float* scores, const int32_t* labels,
                         const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
                         const float* frame_shift, int F, int K, int S, int T, float track_high, float track_low,
                         float new_thr, float match_iou, float second_iou, int max_age, int min_hits, float alpha,
                         float beta, int class_agnostic, float* trk_box, float* trk_score, int32_t* trk_meta,
-                        int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* count, hipStream_t stream) {
+                        int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* count, int assoc,
+                        hipStream_t stream) {
+  if (assoc > 1) return fail(what + ": assoc must be 0 (greedy) or 1 (lsap)");
   if (F < 0 || K < 0 || S < 0 || F > kTrkMaxF || K > kTrkMaxK || S > kTrkMaxS || T < 1 || T > kTrkMaxT)
     return fail(what + ": need 0 <= F <= 1024, 0 <= K <= 1024, 0 <= S <= 1024, 1 <= T <= 256");
   if (track_high != track_high || track_low != track_low || new_thr != new_thr || match_iou != match_iou ||
@@ -472,8 +655,13 @@ static int track_update(const std::string& what, const float* boxes, const float
   if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_boxes) |
        reinterpret_cast<uintptr_t>(trk_box) | reinterpret_cast<uintptr_t>(trk_meta)) & 15)
     return fail(what + ": boxes, out_boxes, trk_box and trk_meta must be 16-byte aligned");
-  const size_t shmem = TrkLds(K, T).total;
+  size_t shmem = TrkLds(K, T).total;
   if (shmem > 64 * 1024) return fail(what + ": K / T too large for LDS");
+  if (assoc >= 0) {
+    static unsigned long long done = 0;  // per-device bitmask
+    if (int rc = track_assoc_lds(what, reinterpret_cast<const void*>(track_update_assoc_kernel), &done, K, T, &shmem))
+      return rc;
+  }
   const int threads = (T + 63) / 64 * 64;
   TrkParams p;
   p.track_high = track_high;
@@ -489,6 +677,12 @@ static int track_update(const std::string& what, const float* boxes, const float
   ProfScope prof(stream, PROF_TRACK,
                  (double)F * (K * 44.0 + (n_valid ? 4.0 : 0.0) + (frame_shift ? 8.0 : 0.0) + 12.0) +
                      (double)S * (T * 104.0 + 16.0));
+  if (assoc >= 0) {
+    MOE_LAUNCH(prof, track_update_assoc_kernel, dim3(S), dim3(threads), shmem, stream, boxes, scores, labels, n_valid,
+               frame_slot, frame_reset, frame_shift, F, K, S, T, p, assoc, trk_box, trk_score, trk_meta, seq_meta,
+               out_id, out_boxes, count);
+    return check_launch(what.c_str());
+  }
   MOE_LAUNCH(prof, track_update_kernel, dim3(S), dim3(threads), shmem, stream, boxes, scores, labels, n_valid,
              frame_slot, frame_reset, frame_shift, F, K, S, T, p, trk_box, trk_score, trk_meta, seq_meta, out_id,
              out_boxes, count);
@@ -504,7 +698,7 @@ extern "C" int rtdetr_track_update(const float* boxes, const float* scores, cons
                                    int32_t* count, hipStream_t stream) {
   return track_update("rtdetr_track_update", boxes, scores, labels, n_valid, frame_slot, frame_reset, nullptr, F, K,
                       S, T, track_high, track_low, new_thr, match_iou, second_iou, max_age, min_hits, alpha, beta,
-                      class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes, count, stream);
+                      class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes, count, -1, stream);
 }
 
 extern "C" int rtdetr_track_update_shift(const float* boxes, const float* scores, const int32_t* labels,
@@ -518,20 +712,35 @@ extern "C" int rtdetr_track_update_shift(const float* boxes, const float* scores
   return track_update("rtdetr_track_update_shift", boxes, scores, labels, n_valid, frame_slot, frame_reset,
                       frame_shift, F, K, S, T, track_high, track_low, new_thr, match_iou, second_iou, max_age,
                       min_hits, alpha, beta, class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes,
-                      count, stream);
+                      count, -1, stream);
 }
 
-extern "C" int rtdetr_track_sweep(const float* boxes, const float* scores, const int32_t* labels,
-                                  const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
-                                  int F, int K, int S, int T, int G, const float* params_f, const int32_t* params_i,
-                                  float* trk_box, float* trk_score, int32_t* trk_meta, int32_t* seq_meta,
-                                  int32_t* out_id, float* out_boxes, int32_t* out_row, int32_t* count,
-                                  const float* frame_shift, hipStream_t stream) {
-  const std::string what = "rtdetr_track_sweep";
+extern "C" int rtdetr_track_update_assoc(const float* boxes, const float* scores, const int32_t* labels,
+                                         const int32_t* n_valid, const int32_t* frame_slot,
+                                         const int32_t* frame_reset, int F, int K, int S, int T, float track_high,
+                                         float track_low, float new_thr, float match_iou, float second_iou,
+                                         int max_age, int min_hits, float alpha, float beta, int class_agnostic,
+                                         float* trk_box, float* trk_score, int32_t* trk_meta, int32_t* seq_meta,
+                                         int32_t* out_id, float* out_boxes, int32_t* count, const float* frame_shift,
+                                         int assoc, hipStream_t stream) {
+  if (assoc < 0) return fail("rtdetr_track_update_assoc: assoc must be 0 (greedy) or 1 (lsap)");
+  return track_update("rtdetr_track_update_assoc", boxes, scores, labels, n_valid, frame_slot, frame_reset,
+                      frame_shift, F, K, S, T, track_high, track_low, new_thr, match_iou, second_iou, max_age,
+                      min_hits, alpha, beta, class_agnostic, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes,
+                      count, assoc, stream);
+}
+
+// with_assoc: rtdetr_track_sweep_assoc (track_sweep_assoc_kernel, params_assoc required); else params_assoc is unused
+static int track_sweep(const std::string& what, bool with_assoc, const float* boxes, const float* scores,
+                       const int32_t* labels, const int32_t* n_valid, const int32_t* frame_slot,
+                       const int32_t* frame_reset, int F, int K, int S, int T, int G, const float* params_f,
+                       const int32_t* params_i, const int32_t* params_assoc, float* trk_box, float* trk_score,
+                       int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id, float* out_boxes, int32_t* out_row,
+                       int32_t* count, const float* frame_shift, hipStream_t stream) {
   if (F < 0 || K < 0 || S < 0 || F > kTrkMaxF || K > kTrkMaxK || S > kTrkMaxS || T < 1 || T > kTrkMaxT)
     return fail(what + ": need 0 <= F <= 1024, 0 <= K <= 1024, 0 <= S <= 1024, 1 <= T <= 256");
   if (G < 1 || G > kTrkMaxG) return fail(what + ": need 1 <= G <= 1024 configurations");
-  if (!params_f || !params_i) return fail(what + ": NULL parameter table");
+  if (!params_f || !params_i || (with_assoc && !params_assoc)) return fail(what + ": NULL parameter table");
   if (F == 0) return 0;
   if (S < 1) return fail(what + ": need S >= 1 state slots with F > 0");
   if (!frame_slot || !frame_reset) return fail(what + ": NULL frame table");
@@ -541,17 +750,51 @@ extern "C" int rtdetr_track_sweep(const float* boxes, const float* scores, const
   if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_boxes) |
        reinterpret_cast<uintptr_t>(trk_box) | reinterpret_cast<uintptr_t>(trk_meta)) & 15)
     return fail(what + ": boxes, out_boxes, trk_box and trk_meta must be 16-byte aligned");
-  const size_t shmem = TrkLds(K, T).total;
+  size_t shmem = TrkLds(K, T).total;
   if (shmem > 64 * 1024) return fail(what + ": K / T too large for LDS");
+  if (with_assoc) {
+    static unsigned long long done = 0;  // per-device bitmask
+    if (int rc = track_assoc_lds(what, reinterpret_cast<const void*>(track_sweep_assoc_kernel), &done, K, T, &shmem))
+      return rc;
+  }
   const int threads = (T + 63) / 64 * 64;
   // the inputs once (every configuration's workgroups read the same lines), the tables, and per configuration the
   // state read and written and the compact outputs
   ProfScope prof(stream, PROF_TRACK_SWEEP,
                  (double)F * (K * 24.0 + (n_valid ? 4.0 : 0.0) + (frame_shift ? 8.0 : 0.0) + 8.0) +
-                     (double)G * ((kTrkSweepF + kTrkSweepI) * 4.0 + (double)S * (T * 104.0 + 16.0) +
-                                  (double)F * (T * 24.0 + 4.0)));
+                     (double)G * ((kTrkSweepF + kTrkSweepI + (with_assoc ? 1 : 0)) * 4.0 +
+                                  (double)S * (T * 104.0 + 16.0) + (double)F * (T * 24.0 + 4.0)));
+  if (with_assoc) {
+    MOE_LAUNCH(prof, track_sweep_assoc_kernel, dim3(S, G), dim3(threads), shmem, stream, boxes, scores, labels,
+               n_valid, frame_slot, frame_reset, frame_shift, F, K, S, T, params_f, params_i, params_assoc, trk_box,
+               trk_score, trk_meta, seq_meta, out_id, out_boxes, out_row, count);
+    return check_launch(what.c_str());
+  }
   MOE_LAUNCH(prof, track_sweep_kernel, dim3(S, G), dim3(threads), shmem, stream, boxes, scores, labels, n_valid,
              frame_slot, frame_reset, frame_shift, F, K, S, T, params_f, params_i, trk_box, trk_score, trk_meta,
              seq_meta, out_id, out_boxes, out_row, count);
   return check_launch(what.c_str());
+}
+
+extern "C" int rtdetr_track_sweep(const float* boxes, const float* scores, const int32_t* labels,
+                                  const int32_t* n_valid, const int32_t* frame_slot, const int32_t* frame_reset,
+                                  int F, int K, int S, int T, int G, const float* params_f, const int32_t* params_i,
+                                  float* trk_box, float* trk_score, int32_t* trk_meta, int32_t* seq_meta,
+                                  int32_t* out_id, float* out_boxes, int32_t* out_row, int32_t* count,
+                                  const float* frame_shift, hipStream_t stream) {
+  return track_sweep("rtdetr_track_sweep", false, boxes, scores, labels, n_valid, frame_slot, frame_reset, F, K, S, T,
+                     G, params_f, params_i, nullptr, trk_box, trk_score, trk_meta, seq_meta, out_id, out_boxes,
+                     out_row, count, frame_shift, stream);
+}
+
+extern "C" int rtdetr_track_sweep_assoc(const float* boxes, const float* scores, const int32_t* labels,
+                                        const int32_t* n_valid, const int32_t* frame_slot,
+                                        const int32_t* frame_reset, int F, int K, int S, int T, int G,
+                                        const float* params_f, const int32_t* params_i, float* trk_box,
+                                        float* trk_score, int32_t* trk_meta, int32_t* seq_meta, int32_t* out_id,
+                                        float* out_boxes, int32_t* out_row, int32_t* count, const float* frame_shift,
+                                        const int32_t* params_assoc, hipStream_t stream) {
+  return track_sweep("rtdetr_track_sweep_assoc", true, boxes, scores, labels, n_valid, frame_slot, frame_reset, F, K,
+                     S, T, G, params_f, params_i, params_assoc, trk_box, trk_score, trk_meta, seq_meta, out_id,
+                     out_boxes, out_row, count, frame_shift, stream);
 }

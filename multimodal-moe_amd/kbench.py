@@ -15,6 +15,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
   python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
   python multimodal-moe_amd/kbench.py --track-sweep the parameter sweep's kernel against G launches of the tracker's
+  python multimodal-moe_amd/kbench.py --track-lsap  assoc = lsap against the greedy kernel, the host and a forward replay
   python multimodal-moe_amd/kbench.py --frame-shift the camera-motion estimator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --mot-eval    the tracking evaluator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --hota        the frame-parallel HOTA kernels against the host and rtdetr_mot_eval
@@ -996,6 +997,169 @@ def track_sweep_leg(reps, rounds):
         print(json.dumps(line), flush=True)
 
 
+def crowd_sequence(n_obj, F, K, seed=0, spacing=18.0, speed=3.0):
+    """track_sequence for a crowd: 40 x 100 px pedestrians ``spacing`` px apart
+    (closer than their width: neighbours overlap at an IoU of about 0.38) in
+    rows 120 px apart, walking at up to ``speed`` px a frame in alternating
+    directions, so that neighbours cross; 1.5 px of jitter per side, 10 %
+    missed, 20 % scored low, 2 false positives.  -> track_sequence's tuple and
+    clean fp32 [F, n_obj, 4], the objects' true boxes (the ground truth)."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    per_row = int(1148 // spacing)
+    i = np.arange(n_obj)
+    x0, y0 = 30.0 + spacing * (i % per_row), 20.0 + 120.0 * (i // per_row)
+    vx = np.where(i % 2 == 0, speed, -speed) * rng.uniform(0.6, 1.0, n_obj)
+    boxes, scores = np.zeros((F, K, 4), np.float32), np.zeros((F, K), np.float32)
+    n_valid, truth = np.zeros(F, np.int32), np.full((F, K), -1, np.int64)
+    clean = np.zeros((F, n_obj, 4), np.float32)
+    for f in range(F):
+        x = x0 + vx * f
+        clean[f] = np.stack([x, y0, x + 40.0, y0 + 100.0], 1)
+        rows = []
+        for o in range(n_obj):
+            if f > 0 and rng.random() < 0.1:
+                continue
+            sc = rng.uniform(0.15, 0.45) if f > 1 and rng.random() < 0.2 else rng.uniform(0.65, 0.95)
+            rows.append((sc, clean[f, o].astype(np.float64) + rng.normal(0, 1.5, 4), o))
+        for _ in range(2):
+            fx, fy = rng.uniform(0, 1188), rng.uniform(0, 574)
+            rows.append((rng.uniform(0.1, 0.9), np.array([fx, fy, fx + 40.0, fy + 100.0]), -1))
+        rows.sort(key=lambda r: -r[0])
+        rows = rows[:K]
+        n = len(rows)
+        for d, (sc, b, o) in enumerate(rows):
+            boxes[f, d], scores[f, d], truth[f, d] = b, sc, o
+        fx, fy = rng.uniform(0, 1188, K - n), rng.uniform(0, 574, K - n)
+        boxes[f, n:] = np.stack([fx, fy, fx + 40, fy + 100], 1)
+        scores[f, n:] = np.sort(rng.uniform(0.001, 0.05, K - n))[::-1]
+        n_valid[f] = n
+    return boxes, scores, np.zeros((F, K), np.int32), n_valid, truth, clean
+
+
+def track_lsap_leg(reps, rounds):
+    """TrackArgs.assoc: rtdetr_track_update_assoc with assoc = lsap against the
+    greedy kernel, one JSON line per shape: --track's (F 16, K 300, 40 objects, T
+    64) and a crowd (F 16, K 300, 200 overlapping objects that cross, T 256: the
+    solved problems are as large as the crowd).  Per shape and mode the kernel's
+    outputs and state over frames 16..31 are first checked equal to
+    track.track_reference's, bit for bit (the state before them is the one 16
+    earlier frames leave).  kernel_us: dispatch-stamped execution time of one
+    launch; host_reference_ms: the reference loop over the 16 frames, wall
+    clock; forward_replay_us: one EvalForward graph replay at batch 16
+    (rtdetr-r50-moe8-top2, 704 x 1248); solves / solve_n_max / solve_q_max: the
+    reference's events over the 16 timed frames.  Median, min and max over the
+    rounds, the modes interleaved in each round.  Then the accuracy line: 4
+    crowd sequences of 200 frames (60 objects) scored against the objects' clean
+    boxes by tune.sweep(hota=True) over {"assoc": ["greedy", "lsap"]} in one
+    launch per chunk: HOTA, IDF1, IDSW per mode.  Synthetic numbers only: no
+    claim is made beyond them."""
+    import time
+
+    import numpy as np
+
+    from src.rtdetr_moe import engine, tune
+    from src.rtdetr_moe.model import RTDETRMoE
+    from src.rtdetr_moe.track import TrackArgs, TrackState, copy_state, new_state, states_equal, track_reference
+
+    F, K = 16, 300
+    torch.manual_seed(0)
+    model = RTDETRMoE("rtdetr-r50-moe8-top2").cuda().to(memory_format=torch.channels_last).eval()
+    fwd = engine.EvalForward(model)
+    x = torch.rand((16, 3, 704, 1248), device="cuda").contiguous(memory_format=torch.channels_last)
+    ctx = torch.zeros(16, dtype=torch.int32, device="cuda")
+    fwd.prepare(x, ctx)
+
+    def replay_us(n=10):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fwd(x, ctx)
+            e1.record()
+            e1.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    dev = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
+    zeros = torch.zeros(F, dtype=torch.int32, device="cuda")
+    shapes = {"track": (track_sequence(40, 2 * F, K)[:4], 64, 40), "crowd": (crowd_sequence(200, 2 * F, K)[:4], 256, 200)}
+    for name, ((boxes, scores, labels, n_valid), T, n_obj) in shapes.items():
+        db, ds, dl, dn = dev(boxes[F:]), dev(scores[F:]), dev(labels[F:]), dev(n_valid[F:])
+        modes = {}
+        for assoc in ("greedy", "lsap"):
+            args = TrackArgs(max_tracks=T, assoc=assoc)
+            ref, events, want = new_state(T), {}, []
+            for f in range(2 * F):
+                if f == F:
+                    warm, events = copy_state(ref), {}
+                want.append(track_reference(ref, boxes[f], scores[f], labels[f], n_valid[f], args, events))
+            state = TrackState(1, T, "cuda")
+            state.load(0, warm)
+            snap = state.snapshot()
+            out = tuple(t.cpu().numpy() for t in L.track_update(state, db, ds, dl, dn, zeros, zeros, args))
+            for f in range(F):
+                oid, obox, cnt = want[F + f]
+                if (int(out[2][f]) != cnt or not np.array_equal(out[0][f], oid)
+                        or not np.array_equal(out[1][f].view(np.int32), obox.view(np.int32))):
+                    raise SystemExit(f"track_update ({assoc}, {name}) differs from track_reference (frame {F + f})")
+            if not states_equal(state.export(0), ref):
+                raise SystemExit(f"track_update's state ({assoc}, {name}) differs from track_reference's")
+            modes[assoc] = dict(args=args, state=state, snap=snap, warm=warm, events=events,
+                                live=int((warm["hits"] > 0).sum()), reported=int(out[2].sum()))
+
+        def kernel(m):
+            m["state"].restore(m["snap"])
+            return L.track_update(m["state"], db, ds, dl, dn, zeros, zeros, m["args"])
+
+        def host(m):
+            st = copy_state(m["warm"])
+            t0 = time.perf_counter()
+            for f in range(F):
+                track_reference(st, boxes[F + f], scores[F + f], labels[F + f], n_valid[F + f], m["args"])
+            return 1e3 * (time.perf_counter() - t0)
+
+        res = {f"{k}_{a}": [] for k in ("kernel_us", "host_reference_ms") for a in modes}
+        res["forward_replay_us"] = []
+        for _ in range(rounds):
+            for a, m in modes.items():
+                res[f"kernel_us_{a}"].append(timed(lambda: kernel(m), reps))
+                res[f"host_reference_ms_{a}"].append(host(m))
+            res["forward_replay_us"].append(replay_us())
+        e = modes["lsap"]["events"]
+        line = {"kernel": "rtdetr_track_update_assoc", "shape": f"{name}: F{F} K{K} T{T} S1 objects{n_obj}",
+                "live_tracks": modes["lsap"]["live"], "reported_greedy": modes["greedy"]["reported"],
+                "reported_lsap": modes["lsap"]["reported"], "solves": e["solves"], "solve_n_max": e["solve_n_max"],
+                "solve_q_max": e["solve_q_max"], "checked_bit_for_bit": "both modes, frames 16..31"}
+        for k, v in res.items():
+            line[k] = round(statistics.median(v), 3)
+            line[k + "_min"] = round(min(v), 3)
+            line[k + "_max"] = round(max(v), 3)
+        line["lsap_over_greedy"] = round(line["kernel_us_lsap"] / line["kernel_us_greedy"], 2)
+        line["host_over_kernel_lsap"] = round(1e3 * line["host_reference_ms_lsap"] / line["kernel_us_lsap"], 1)
+        line["lsap_share_of_forward"] = round(line["kernel_us_lsap"] / line["forward_replay_us"], 4)
+        print(json.dumps(line), flush=True)
+
+    S, FA, n_obj = 4, 200, 60
+    dets, gt = {}, {}
+    for q in range(S):
+        boxes, scores, labels, _, _, clean = crowd_sequence(n_obj, FA, K, seed=100 + q)
+        key = f"crowd{q}"
+        dets[key] = {f + 1: (boxes[f], scores[f], labels[f]) for f in range(FA)}
+        gt[key] = {f + 1: (clean[f], np.arange(n_obj) + 1, np.ones(n_obj, np.int32)) for f in range(FA)}
+    tm = {}
+    out = tune.sweep(dets, gt, {"assoc": ["greedy", "lsap"]}, base=TrackArgs(max_tracks=128), hota=True,
+                     device=torch.device("cuda"), timing=tm)
+    line = {"kernel": "rtdetr_track_sweep_assoc", "shape": f"S{S} F{FA} K{K} T128 G2 objects{n_obj} (crowd, synthetic)",
+            "launches": tm["launches"], "tracking_ms": round(1e3 * tm["tracking"], 1)}
+    for cfg, m in zip(out["configs"], out["metrics"]):
+        c = m["COMBINED"]
+        line[cfg["assoc"]] = {"HOTA": round(c["HOTA"]["HOTA"], 4), "AssA": round(c["HOTA"]["AssA"], 4),
+                              "IDF1": round(c["IDF1"], 4), "MOTA": round(c["MOTA"], 4), "IDSW": int(c["IDSW"])}
+    print(json.dumps(line), flush=True)
+
+
 def frame_shift_leg(reps, rounds):
     """rtdetr_frame_shift at predict's shape (F 16 frames of one sequence, 704 x
     1248, the defaults of track.TrackArgs: radius 48, gate 0.1) against
@@ -1455,6 +1619,10 @@ def main():
                     help="check rtdetr_track_sweep against tune.track_sweep_reference (8 sequences of 600 frames, K "
                          "300), time it at G 1 / 16 / 64 against rtdetr_track_update launched G times, the host "
                          "reference and one forward replay, time tune.sweep's stages, and exit")
+    ap.add_argument("--track-lsap", action="store_true",
+                    help="check rtdetr_track_update_assoc (assoc = lsap) against track_reference, time it against the "
+                         "greedy kernel at --track's shape and at a crowd shape, the host reference and one forward "
+                         "replay, print HOTA / IDF1 / IDSW of both modes on synthetic crowds, and exit")
     ap.add_argument("--frame-shift", action="store_true",
                     help="check rtdetr_frame_shift against motion.sequence_shifts, then time it against the host and "
                          "a forward replay, and exit")
@@ -1511,6 +1679,9 @@ def main():
         return
     if a.track_sweep:
         track_sweep_leg(a.reps, a.rounds)
+        return
+    if a.track_lsap:
+        track_lsap_leg(a.reps, a.rounds)
         return
     if a.box_fuse:
         box_fuse_leg(a.reps, a.rounds)

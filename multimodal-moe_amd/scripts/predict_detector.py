@@ -54,6 +54,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="link the detections across the frames of a sequence (one directory): tracks.json, mot/*.txt")
     ap.add_argument("--tracker", type=str, default=None,
                     help="--track: JSON of track.TrackArgs fields, e.g. '{\"max_age\": 15}' (default: ByteTrack's)")
+    ap.add_argument("--assoc", type=str, default=None, choices=("greedy", "lsap"),
+                    help="--track: the association of tracks and detections: greedy by IoU (the default), or lsap, the "
+                         "one-to-one matching with the largest total IoU, solved in the tracker's kernel")
     ap.add_argument("--cmc", action="store_true",
                     help="--track: camera-motion compensation, the tracks move by each frame's global shift "
                          "(camera_motion.json)")
@@ -86,6 +89,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error("--hota needs --gt")
     if a.tracker is not None and not a.track:
         ap.error("--tracker needs --track")
+    if a.assoc is not None and not a.track:
+        ap.error("--assoc needs --track")
     given = a.cmc_radius is not None or a.cmc_gate is not None or a.cmc_rows is not None
     if (a.cmc or given) and not a.track:
         ap.error("--cmc needs --track")
@@ -95,10 +100,12 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def tracker_args(a):
-    """engine.predict's ``track`` from the command line: --tracker's JSON, the --cmc options over it."""
+    """engine.predict's ``track`` from the command line: --tracker's JSON, --assoc and the --cmc options over it."""
     if not a.track:
         return None
     t = json.loads(a.tracker) if a.tracker else {}
+    if a.assoc is not None:
+        t["assoc"] = a.assoc
     if a.cmc:
         t["cmc"] = True
         if a.cmc_radius is not None:

@@ -6,6 +6,8 @@ tracks.json (the COCO rows plus track_id and sequence) and mot/<sequence>.txt
 (frame,id,x,y,w,h,score,-1,-1,-1) under RUNS_DIR/rtdetr/<run-name>_predict.
 --cmc (with --cmc-radius, --cmc-gate, --cmc-rows T,B) turns on camera-motion
 compensation and adds camera_motion.json.
+--assoc lsap (or --tracker '{"assoc": "lsap"}') associates by the one-to-one
+matching with the largest total IoU instead of greedily (track.py, step 4).
 --gt DIR (with --gt-classes 1 --gt-ignore-classes 2,7,8,12 --eval-iou 0.5)
 scores the tracks against MOTChallenge ground truth (DIR/<sequence>/gt/gt.txt or
 DIR/<sequence>.txt): MOTA, MOTP, IDF1 and the counts per sequence and combined,

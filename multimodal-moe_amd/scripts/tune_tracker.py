@@ -6,8 +6,9 @@ detection files and score every configuration against MOTChallenge ground truth
 w,h,score,class,-1,-1: what scripts/predict_detector.py --save-det writes and
 what MOTChallenge ships as public detections); --gt holds <sequence>/gt/gt.txt
 or <sequence>.txt.  --grid is a JSON object of lists over the sweepable fields,
-e.g. '{"match_iou":[0.2,0.3,0.5],"max_age":[15,30,60]}'; --tracker a JSON object
-of the fields every configuration shares.  On a GPU (--device 0, the default
+e.g. '{"match_iou":[0.2,0.3,0.5],"max_age":[15,30,60]}' or, to compare the two
+associations, '{"assoc":["greedy","lsap"]}'; --tracker a JSON object of the
+fields every configuration shares ("assoc" among them).  On a GPU (--device 0, the default
 when there is one) all configurations are tracked in one HIP launch per chunk of
 frames and scored by the evaluators' kernels; --device cpu runs the references
 and gives the same numbers.  Prints one line per configuration, best first, then
@@ -87,7 +88,7 @@ def main(argv=None) -> dict:
               f"FP {m['FP']} FN {m['FN']} | " + " ".join(f"{k}={res['configs'][g][k]}" for k in varied))
     best = res["configs"][res["best"]]
     print(f"best by {res['metric']}: --tracker '" +
-          json.dumps({k: best[k] for k in (*tune.SWEEPABLE, "max_tracks")}) + "'")
+          json.dumps({k: best[k] for k in (*tune.SWEEPABLE, *tune.SWEEPABLE_MODES, "max_tracks")}) + "'")
     if a.out:
         print(f"Saved the sweep -> {Path(a.out) / 'tracker_sweep.json'}")
     if a.write_best:

@@ -126,6 +126,10 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rtdetr_track_sweep": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _P]),
+    "rtdetr_track_update_assoc": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _F, _F, _I,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "rtdetr_track_sweep_assoc": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                      _P, _P, _P, _P]),
     "rtdetr_frame_shift": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P,
                                 _P]),
     "rtdetr_mot_eval": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P,
@@ -1102,6 +1106,16 @@ def box_fuse(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=30
 TRACK_MAX_K, TRACK_MAX_T, TRACK_MAX_F, TRACK_MAX_S = 1024, 256, 1024, 1024  # rtdetr_track_update's limits
 
 
+TRACK_ASSOC = ("greedy", "lsap")  # TrackArgs.assoc -> the ``assoc`` argument of the *_assoc entries
+
+
+def _assoc_code(args, what) -> int:
+    name = getattr(args, "assoc", "greedy")
+    if name not in TRACK_ASSOC:
+        raise MoEKernelError(f'{what}: assoc must be "greedy" or "lsap", got {name!r}')
+    return TRACK_ASSOC.index(name)
+
+
 def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, args, out=None, shift=None):
     """The tracker, one launch for the batch (rtdetr_track_update:
     track.track_reference per frame, bit for bit).  ``state``: a
@@ -1110,6 +1124,8 @@ def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset,
     None (= K), frame_slot / frame_reset int32 [F]; ``args``: a track.TrackArgs.
     ``shift``: fp32 [F, 2], every frame's camera shift in the boxes' pixels
     (rtdetr_track_update_shift: the predicted boxes move by it), or None.
+    With args.assoc == "lsap" the launch is rtdetr_track_update_assoc's (the
+    association solved in the kernel); "greedy" runs the entries above.
     -> (out_id int32 [F, K], out_boxes fp32 [F, K, 4], count int32 [F]), every
     element written.  ``out``: that tuple of tensors to write into instead of
     new ones."""
@@ -1163,7 +1179,10 @@ def track_update(state, boxes, scores, labels, n_valid, frame_slot, frame_reset,
               float(a.track_high), float(a.track_low), float(a.new_thr), float(a.match_iou), float(a.second_iou),
               int(a.max_age), int(a.min_hits), float(a.alpha), float(a.beta), int(bool(a.class_agnostic)),
               *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out))
-    if shift is None:
+    assoc = _assoc_code(a, "track_update")
+    if assoc != 0:
+        _check(lib().rtdetr_track_update_assoc(*common, _ptr(shift), assoc, _stream()), "rtdetr_track_update_assoc")
+    elif shift is None:
         _check(lib().rtdetr_track_update(*common, _stream()), "rtdetr_track_update")
     else:
         _check(lib().rtdetr_track_update_shift(*common, _ptr(shift), _stream()), "rtdetr_track_update_shift")
@@ -1180,7 +1199,9 @@ def track_sweep(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, 
     (rtdetr_track_sweep: track.track_reference per frame and configuration, bit
     for bit).  ``state``: a track.SweepState (G x S state slots of T tracks,
     updated in place); the inputs as track_update's, shared by all
-    configurations; ``configs``: G track.TrackArgs (validated by their own
+    configurations (rtdetr_track_sweep_assoc, with the configurations' assoc
+    as a third table, as soon as one of them asks for "lsap"); ``configs``: G
+    track.TrackArgs (validated by their own
     constructor, which is what keeps NaN and bad counts out of the device
     tables); ``shift`` fp32 [F, 2] or None.  -> (out_id int32 [G, F, T],
     out_boxes fp32 [G, F, T, 4], out_row int32 [G, F, T], count int32 [G, F]),
@@ -1244,10 +1265,14 @@ def track_sweep(state, boxes, scores, labels, n_valid, frame_slot, frame_reset, 
         tensors.append(shift)
     if any(t.device != dev for t in tensors):
         raise MoEKernelError("track_sweep: all tensors must be on one device")
-    rc = lib().rtdetr_track_sweep(_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), _ptr(frame_slot),
-                                  _ptr(frame_reset), F, K, S, T, G, _ptr(pf), _ptr(pi),
-                                  *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out), _ptr(shift), _stream())
-    _check(rc, "rtdetr_track_sweep")
+    head = (_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(n_valid), _ptr(frame_slot), _ptr(frame_reset), F, K, S, T, G,
+            _ptr(pf), _ptr(pi), *(_ptr(t) for t in state.tensors()), *(_ptr(t) for t in out), _ptr(shift))
+    codes = [_assoc_code(c, "track_sweep") for c in configs]
+    if any(codes):
+        pa = torch.tensor(codes, dtype=torch.int32).to(dev)
+        _check(lib().rtdetr_track_sweep_assoc(*head, _ptr(pa), _stream()), "rtdetr_track_sweep_assoc")
+    else:
+        _check(lib().rtdetr_track_sweep(*head, _stream()), "rtdetr_track_sweep")
     return out
 
 

@@ -839,7 +839,8 @@ def tune_tracker(det, gt, grid, device="0", gt_classes=None, gt_ignore_classes=(
     predict(save_det=True) writes them, MOTChallenge's public detections read
     the same way); ``gt``: MOTChallenge ground truth for the same keys
     (moteval.load_gt with ``gt_classes`` / ``gt_ignore_classes``); ``grid``:
-    {field: [values]} over tune.SWEEPABLE, or a list of configurations.  On a
+    {field: [values]} over tune.SWEEPABLE and tune.SWEEPABLE_MODES ("assoc":
+    ["greedy", "lsap"]), or a list of configurations.  On a
     GPU ``device`` all configurations are tracked in ONE HIP launch per chunk of
     frames (rtdetr_track_sweep) and scored by the evaluators' kernels; "cpu"
     runs the references and gives the same dict.  ``out``: a directory that

@@ -74,6 +74,8 @@ class PredictResults:
     # track with gt=...: moteval.evaluate's {sequence file key: metrics, "COMBINED": metrics}; None otherwise
     # (with hota=True every metrics dict also has a "HOTA" entry)
     mot: dict | None = None
+    # with track: the tracker's arguments as the run used them (TrackArgs.as_dict(): assoc among them); None otherwise
+    tracker: dict | None = None
 
 
 def _image_id(path):
@@ -758,7 +760,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     if save_dir is not None:
         det = frame_sequences(ds.paths, sequence_of) if save_det else None
         _write_files(save_dir, preds, save_json, tracker is not None, save_img, cmc, mot, det)
-    return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=engine.ModelHandle(model), mot=mot)
+    return PredictResults(predictions=preds, speed=speed, save_dir=save_dir, model=engine.ModelHandle(model), mot=mot,
+                          tracker=None if targs is None else targs.as_dict())
 
 
 def track(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.1, tracker=None, **kw) -> PredictResults:

@@ -35,7 +35,8 @@ is sorted.  All arithmetic is fp32, every operation rounded on its own, no FMA.
  4. Greedy association of a set of slots with a set of rows: repeatedly match
     the admissible pair of a still-unmatched slot and row with the largest iou
     (equal iou: the lower row, then the lower slot) until none is left.  A
-    deliberate simplification of ByteTrack's linear assignment.
+    deliberate simplification of ByteTrack's linear assignment.  This is
+    assoc = "greedy", the default; assoc = "lsap" replaces the step (below).
  5. Stage 1: all live slots against the high rows, thr = match_iou.
  6. Stage 2 (BYTE): the slots still unmatched with age == 0 and hits >=
     min_hits against the low rows, thr = second_iou.
@@ -49,6 +50,27 @@ is sorted.  All arithmetic is fp32, every operation rounded on its own, no FMA.
 10. Report: out_id[d] is the id of the slot that row d updated or founded if
     that slot now has hits >= min_hits, else -1; out_box[d] is that slot's box
     after the update, else zeros.
+
+Step 4 with assoc = "lsap", for one stage's slots and rows (both in ascending
+index order); steps 1-3 and 5-10 are as above.
+ 4a. Admissible pairs: adm[t, d] as in step 3 (labels equal or class_agnostic,
+     fp32 iou > thr); score[t, d] is the fp32 iou where admissible, else 0.
+ 4b. Pruning (part of the rule): only the slots with at least one admissible
+     row and the rows with at least one admissible slot are kept.  If either
+     side is then empty the stage matches nothing and no problem is solved.
+     This keeps filler rows and false positives out of the problem and bounds
+     the solver's work by the real candidates, not by K.
+ 4c. Solve scipy.optimize.linear_sum_assignment on cost = -(float64) score of
+     the pruned sets, in moteval._assign's orientation: the side with more
+     members is the matrix's rows (equal sizes: the slots).  The costs lie in
+     [-1, 0] and are finite: a NaN iou is simply inadmissible.
+ 4d. A returned pair is a match if and only if it is admissible.
+It maximises the total IoU over the one-to-one admissible matchings.  It is NOT
+ByteTrack's lapjv with cost_limit: that prices leaving a pair unmatched and can
+prefer fewer matches; here a match is never traded away for a price.  Events:
+"ties" is a greedy notion and is not counted; solves (problems solved),
+solve_n_max (the largest smaller side) and solve_q_max (the largest larger side)
+are added instead (LSAP_EVENTS), under "lsap" only.
 """
 from __future__ import annotations
 
@@ -61,6 +83,8 @@ TRACK_MAX_G = 1024  # rtdetr_track_sweep: configurations per launch
 HITS_CAP = 1 << 30
 STATE_FIELDS = ("box", "vel", "score", "label", "id", "age", "hits")
 EVENTS = ("stage1", "stage2", "refound", "tentative_freed", "expired", "births", "dropped", "ties", "reported")
+LSAP_EVENTS = ("solves", "solve_n_max", "solve_q_max")  # added to the events under assoc = "lsap" only
+ASSOC = ("greedy", "lsap")  # TrackArgs.assoc; the index is the kernel's ``assoc`` argument
 
 
 @dataclass
@@ -81,10 +105,13 @@ class TrackArgs:
     cmc_radius: int = 48        # search radius in pixels of the model's input, a multiple of 4 in [4, 64]; not tuned
     cmc_gate: float = 0.1       # a non-zero shift must beat SAD(0, 0) by this share; not tuned
     cmc_rows: tuple = (0.0, 1.0)  # the (top, bottom) fractions of the height the estimator looks at
+    assoc: str = "greedy"       # step 4: "greedy", or "lsap" (the assignment with the largest total IoU)
 
     def __post_init__(self):
         from .motion import check_rows, check_search
 
+        if not isinstance(self.assoc, str) or self.assoc not in ASSOC:
+            raise ValueError(f'TrackArgs.assoc must be "greedy" or "lsap", got {self.assoc!r}')
         if not isinstance(self.cmc, (bool, np.bool_)):
             raise ValueError(f"TrackArgs.cmc must be a bool, got {self.cmc!r}")
         self.cmc = bool(self.cmc)
@@ -182,12 +209,42 @@ def _associate(slots, rows, box, label, b, lab, thr, agnostic, events):
     return out
 
 
+def _associate_lsap(slots, rows, box, label, b, lab, thr, agnostic, events):
+    """Step 4 with assoc = "lsap" (4a-4d) over the given slot and row indices -> [(slot, row)]."""
+    if len(slots) == 0 or len(rows) == 0:
+        return []
+    from scipy.optimize import linear_sum_assignment
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        iou = _iou(box[slots], b[rows])
+        adm = iou > np.float32(thr)
+    if not agnostic:
+        adm &= label[slots][:, None] == lab[rows][None, :]
+    ks, kr = np.nonzero(adm.any(1))[0], np.nonzero(adm.any(0))[0]
+    if len(ks) == 0:
+        return []
+    adm = adm[np.ix_(ks, kr)]
+    score = np.where(adm, iou[np.ix_(ks, kr)], np.float32(0)).astype(np.float32)
+    cost = -score.astype(np.float64)
+    if len(ks) >= len(kr):  # the larger side is the matrix's rows; equal: the slots
+        ts, ds = linear_sum_assignment(cost)
+    else:
+        ds, ts = linear_sum_assignment(np.ascontiguousarray(cost.T))
+    if events is not None:
+        events["solves"] += 1
+        events["solve_n_max"] = max(events["solve_n_max"], min(len(ks), len(kr)))
+        events["solve_q_max"] = max(events["solve_q_max"], max(len(ks), len(kr)))
+        if "solve_shapes" in events:  # a list the caller put there: every problem's (slots, rows)
+            events["solve_shapes"].append((len(ks), len(kr)))
+    return [(int(slots[ks[t]]), int(rows[kr[d]])) for t, d in zip(ts, ds) if adm[t, d]]
+
+
 def track_reference(state, boxes, scores, labels, n_valid, args, events=None, shift=None):
     """One frame of one sequence: boxes fp32 [K, 4] xyxy, scores fp32 [K], labels
     [K] (tensors or arrays), ``n_valid`` None (= K) or the number of leading
     rows that count.  Updates ``state`` (new_state) in place -> (out_id int32
     [K], out_box fp32 [K, 4], count: the reported rows).  ``events``: a dict the
-    frame's event counts (EVENTS) are added to.  ``shift``: the frame's camera
+    frame's event counts (EVENTS; with assoc = "lsap" LSAP_EVENTS too) are added to.  ``shift``: the frame's camera
     shift (sx, sy) in the boxes' pixels, or None: nothing is added."""
     a = TrackArgs.parse(args)
     f32 = np.float32
@@ -199,8 +256,9 @@ def track_reference(state, boxes, scores, labels, n_valid, args, events=None, sh
     box, vel, hits, age = state["box"], state["vel"], state["hits"], state["age"]
     T = hits.shape[0]
     if events is not None:
-        for k in EVENTS:
+        for k in EVENTS + (LSAP_EVENTS if a.assoc == "lsap" else ()):
             events.setdefault(k, 0)
+    associate = _associate_lsap if a.assoc == "lsap" else _associate
     # 1. predict
     live = hits > 0
     box[live] = box[live] + vel[live]
@@ -215,12 +273,12 @@ def track_reference(state, boxes, scores, labels, n_valid, args, events=None, sh
     # 5. stage 1, 6. stage 2
     row_slot = np.full(K, -1, dtype=np.int64)
     slot_row = np.full(T, -1, dtype=np.int64)
-    m1 = _associate(np.nonzero(live)[0], np.nonzero(high)[0], box, state["label"], b, lab, a.match_iou,
+    m1 = associate(np.nonzero(live)[0], np.nonzero(high)[0], box, state["label"], b, lab, a.match_iou,
                     a.class_agnostic, events)
     for t, d in m1:
         slot_row[t], row_slot[d] = d, t
     second = live & (slot_row < 0) & (age == 0) & (hits >= a.min_hits)
-    m2 = _associate(np.nonzero(second)[0], np.nonzero(low)[0], box, state["label"], b, lab, a.second_iou,
+    m2 = associate(np.nonzero(second)[0], np.nonzero(low)[0], box, state["label"], b, lab, a.second_iou,
                     a.class_agnostic, events)
     for t, d in m2:
         slot_row[t], row_slot[d] = d, t

@@ -2,8 +2,10 @@
 TrackArgs run over the same detections and scored against ground truth, the
 rule stated once.
 
-* ``SWEEPABLE`` / ``expand_grid``: the fields a sweep may vary -- the ones the
-  tracker's kernel takes as parameters -- and the grid's configurations.
+* ``SWEEPABLE`` / ``SWEEPABLE_MODES`` / ``expand_grid``: the fields a sweep may
+  vary -- the numbers the tracker's kernel takes as parameters, and the modes it
+  branches on per configuration (``assoc``: "greedy" / "lsap") -- and the grid's
+  configurations.
   ``max_tracks`` is the state's layout and ``cmc*`` an input (``shifts``).
 * ``load_det`` / ``det_lines``: detections as MOTChallenge ``det.txt`` text
   (frame,-1,x,y,w,h,score,class,-1,-1) and back, every fp32 value with the same
@@ -44,6 +46,7 @@ from .track import (TRACK_MAX_F, TRACK_MAX_G, TRACK_MAX_K, TRACK_MAX_S, TrackArg
 
 SWEEPABLE = ("track_high", "track_low", "new_thr", "match_iou", "second_iou", "max_age", "min_hits", "alpha", "beta",
              "class_agnostic")
+SWEEPABLE_MODES = ("assoc",)  # chosen per configuration inside the launch (rtdetr_track_sweep_assoc)
 MAX_CONFIGS = TRACK_MAX_G
 MAX_OUT_BYTES = 256 << 20  # one launch's compact outputs: G * F * T * 24 bytes stay under this
 METRICS = ("HOTA", "MOTA", "IDF1")
@@ -53,7 +56,7 @@ def expand_grid(grid: dict, base=None) -> list:
     """The cartesian product of ``grid`` {field: [values]} over the keys in
     sorted order, the last key fastest; every other field from ``base`` (a
     TrackArgs or a dict of its fields; None: the defaults).  A ValueError for an
-    unknown key, a key outside SWEEPABLE, an empty list, or more than 1024
+    unknown key, a key outside SWEEPABLE and SWEEPABLE_MODES, an empty list, or more than 1024
     configurations; TrackArgs' own checks run per configuration."""
     base = TrackArgs() if base is None else TrackArgs.parse(base)
     if not isinstance(grid, dict):
@@ -63,8 +66,9 @@ def expand_grid(grid: dict, base=None) -> list:
     for k in keys:
         if k not in known:
             raise ValueError(f"unknown tracker argument {k!r} in the grid")
-        if k not in SWEEPABLE:
-            raise ValueError(f"{k!r} cannot be swept (the sweepable fields are {', '.join(SWEEPABLE)})")
+        if k not in SWEEPABLE and k not in SWEEPABLE_MODES:
+            raise ValueError(f"{k!r} cannot be swept (the sweepable fields are "
+                             f"{', '.join(SWEEPABLE + SWEEPABLE_MODES)})")
         if isinstance(grid[k], (str, bytes)) or not hasattr(grid[k], "__len__") or len(grid[k]) == 0:
             raise ValueError(f"the grid's {k!r} must be a non-empty list of values")
     n = 1
@@ -383,7 +387,8 @@ def sweep(dets, gt, grid_or_configs, base=None, eval_iou=0.5, hota=False, metric
     expand_grid (with ``base``) or a list of TrackArgs / dicts sharing
     max_tracks; ``shifts``: {key: fp32 [n, 2]} camera shifts per frame or None.
     Tracking: on a GPU ``device`` ONE HIP launch per chunk of frames for all
-    configurations (rtdetr_track_sweep) unless MOE_TRACK_SWEEP=0; otherwise
+    configurations (rtdetr_track_sweep; rtdetr_track_sweep_assoc when one of
+    them has assoc = "lsap") unless MOE_TRACK_SWEEP=0; otherwise
     track_sweep_reference.  A sequence's frames are 1 .. the last frame either
     side has.  Scoring: every (configuration, key) pair is one
     moteval.dense_sequence (tracker ids to dense indices in ascending order)

@@ -258,6 +258,22 @@ int main() {
     std::printf("FAIL track_sweep F=0 must succeed\n");
     ++g_fail;
   }
+  // the entries that take the association: assoc outside {0, 1}, the third table, the shared limits
+  auto upd = [&](int K, int T, int assoc) {
+    return rtdetr_track_update_assoc(f32, f32, i32, nullptr, i32, i32, 1, K, 1, T, 0.5f, 0.1f, 0.6f, 0.2f, 0.5f, 30, 2,
+                                     0.5f, 0.25f, 0, f32, f32, i32, i32, i32, f32, i32, nullptr, assoc, s);
+  };
+  expect_error("track_update_assoc assoc=2", upd(8, 4, 2));
+  expect_error("track_update_assoc assoc=-1", upd(8, 4, -1));
+  expect_error("track_update_assoc K=1025", upd(1025, 4, 1));
+  expect_error("track_update_assoc T=257", upd(8, 257, 1));
+  auto sweep_a = [&](int K, int G, const int32_t* pa) {
+    return rtdetr_track_sweep_assoc(f32, f32, i32, nullptr, i32, i32, 1, K, 1, 4, G, f32, i32, f32, f32, i32, i32, i32,
+                                    f32, i32, i32, nullptr, pa, s);
+  };
+  expect_error("track_sweep_assoc params_assoc=NULL", sweep_a(8, 2, nullptr));
+  expect_error("track_sweep_assoc G=0", sweep_a(8, 0, i32));
+  expect_error("track_sweep_assoc K=1025", sweep_a(1025, 2, i32));
   std::printf("%d checks, %d failed\n", g_n, g_fail);
   return g_fail == 0 ? 0 : 1;
 }
