@@ -63,6 +63,37 @@ int moe_router_topk_fwd(const void* x, const float* wg, const float* ctx_bias,
                         int32_t* local_rank, int32_t* block_counts,
                         float* aux_partials, hipStream_t stream);
 
+/* The router with a selection bias (loss-free load balancing, Wang et al.
+ * 2024): moe_router_topk_fwd, except that the k experts are those with the
+ * largest key[t,e] = fl32(logits[t,e] + sel_bias[e]) (one fp32 add after the
+ * context bias; descending key, ties -> lower index).  probs, lse, the gates
+ * topk_w (the selected experts' UNBIASED probabilities), the aux partials and
+ * every backward are those of the unbiased logits.  sel_bias: fp32 [E], read
+ * by address at run time (a captured launch routes with the current values);
+ * NULL calls moe_router_topk_fwd. */
+int moe_router_topk_fwd_sel(const void* x, const float* wg, const float* ctx_bias,
+                            const int32_t* ctx_img, int n_ctx, int tokens_per_image,
+                            int T, int d, int E, int k, int normalize, const float* sel_bias,
+                            int32_t* topk_idx, float* topk_w, float* probs, float* lse,
+                            int32_t* local_rank, int32_t* block_counts,
+                            float* aux_partials, hipStream_t stream);
+
+/* The selection biases' update, ONE launch for all L MoE layers of a model.
+ * table: device array of L records {const int32_t* hist (or NULL); float*
+ * bias} (16 B each); load: int64 [L, E]; maxvio: fp32 [L] or NULL.
+ *   load[l,e] += hist[l,e]                       (hist non-NULL)
+ * and, when apply != 0, per layer:
+ *   total = sum_e load[l,e]                      (0: bias unchanged, maxvio 0)
+ *   bias[l,e] = fl32(bias[l,e] + sign(total - E load[l,e]) * rate), then minus
+ *               min_e of the new bias (the smallest becomes 0)
+ *   maxvio[l] = float((double)(E max_e load[l,e] - total) / (double)total)
+ *   load[l,:] = 0
+ * No atomics: bit for bit src/moe/balance.py::balance_reference.  apply with
+ * NULL hist pointers applies a load summed elsewhere (over ranks).  E in
+ * 1..64, L >= 0 (L == 0: nothing is launched). */
+int moe_balance_step(const void* table, int L, int E, long long* load, float rate, int apply,
+                     float* maxvio, hipStream_t stream);
+
 /* a4, index half: exclusive scans of the block counts.
  * Assignment (t,j) to expert e has rank r = slot_base[j,e] + sum_{b'<b}
  * block_counts[b',j,e] + local_rank[t,j] (slot-major, then token order; this

@@ -7,7 +7,10 @@
 //                    for E > 32);
 //                    16 lanes per token, each lane owning d/16 channels read as
 //                    16-B chunks (a token row is read by 16 lanes, 4 tokens per
-//                    wave-instruction).
+//                    wave-instruction).  The kSel instantiation (moe_router_
+//                    topk_fwd_sel) ranks the experts by logit + sel_bias[e]
+//                    (loss-free load balancing); everything else, the gates
+//                    included, still comes from the unbiased logits.
 //  route_scan      : one workgroup; each (slot, expert) column split into
 //                    1024/(k*E) block segments (coalesced row reads), segment
 //                    sums -> exclusive prefixes, then hist / kept offsets
@@ -47,8 +50,16 @@ __device__ __forceinline__ void argmax_stage(float& bv, int& best) {
   const int oi = row_xor_i<H>(best);
   if (ov > bv || (ov == bv && oi < best)) { bv = ov; best = oi; }
 }
+// The same on selection keys, the winner's unbiased logit moved beside its key.
+template <int H>
+__device__ __forceinline__ void argmax_stage_sel(float& bv, float& bl, int& best) {
+  const float ov = row_xor<H>(bv);
+  const float ol = row_xor<H>(bl);
+  const int oi = row_xor_i<H>(best);
+  if (ov > bv || (ov == bv && oi < best)) { bv = ov; bl = ol; best = oi; }
+}
 
-template <int EMAX, int NW, int TPB>
+template <int EMAX, int NW, int TPB, bool kSel>
 __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     const uint16_t* __restrict__ x, const float* __restrict__ wg,
     const float* __restrict__ ctx_bias, const int32_t* __restrict__ ctx_img, int n_ctx,
@@ -56,7 +67,7 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     int32_t* __restrict__ topk_idx, float* __restrict__ topk_w,
     float* __restrict__ probs_out, float* __restrict__ lse_out,
     int32_t* __restrict__ local_rank, int32_t* __restrict__ block_counts,
-    float* __restrict__ aux_partials) {
+    float* __restrict__ aux_partials, const float* __restrict__ sel_bias) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s_wg = reinterpret_cast<float*>(smem);               // [E][d]
   int32_t* s_idx = reinterpret_cast<int32_t*>(s_wg + E * d);  // [TPB][8]
@@ -104,6 +115,9 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
   }
   if (has_ctx)
     for (int i = tid; i < n_ctx * E; i += NT) s_cb[i] = ctx_bias[i];
+  float* s_sb = s_cb + (has_ctx ? n_ctx * E : 0);  // [E] the selection bias (kSel only)
+  if constexpr (kSel)
+    for (int i = tid; i < E; i += NT) s_sb[i] = sel_bias[i];
   for (int i = tid; i < TPB * 8; i += NT) s_idx[i] = -1;
   __syncthreads();
 
@@ -182,7 +196,14 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     for (int q = 0; q < Q; ++q) p[q] *= inv;
     const float lse = m + logf(ssm);
 
-    // top-k on logits (monotone in probs); ties -> lower expert id
+    // kSel: the selection key fl(logit + sel_bias[e]), one add after the context bias
+    float key[Q];
+    if constexpr (kSel) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) key[q] = own[q] ? logit[q] + s_sb[16 * q + sub] : 0.f;
+    }
+
+    // top-k on logits (monotone in probs), kSel: on the keys; ties -> lower expert id
     uint32_t taken = 0;  // bit q: owned expert 16q+sub already selected
     int sel[8];
     float selp[8];
@@ -190,16 +211,32 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     _Pragma("unroll") for (int j = 0; j < 8; ++j) if (j < k) {
       int best = 0x7fffffff;
       float bv = -INFINITY;
+      if constexpr (kSel) {
+        float bl = 0.f;  // the unbiased logit of the expert whose key is bv
 #pragma unroll
-      for (int q = 0; q < Q; ++q)
-        if (own[q] && !((taken >> q) & 1u) && (best == 0x7fffffff || logit[q] > bv)) {
-          bv = logit[q];
-          best = 16 * q + sub;
-        }
-      argmax_stage<8>(bv, best);
-      argmax_stage<4>(bv, best);
-      argmax_stage<2>(bv, best);
-      argmax_stage<1>(bv, best);
+        for (int q = 0; q < Q; ++q)
+          if (own[q] && !((taken >> q) & 1u) && (best == 0x7fffffff || key[q] > bv)) {
+            bv = key[q];
+            bl = logit[q];
+            best = 16 * q + sub;
+          }
+        argmax_stage_sel<8>(bv, bl, best);
+        argmax_stage_sel<4>(bv, bl, best);
+        argmax_stage_sel<2>(bv, bl, best);
+        argmax_stage_sel<1>(bv, bl, best);
+        bv = bl;  // the gate below is the winner's unbiased probability
+      } else {
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+          if (own[q] && !((taken >> q) & 1u) && (best == 0x7fffffff || logit[q] > bv)) {
+            bv = logit[q];
+            best = 16 * q + sub;
+          }
+        argmax_stage<8>(bv, best);
+        argmax_stage<4>(bv, best);
+        argmax_stage<2>(bv, best);
+        argmax_stage<1>(bv, best);
+      }
       if ((best & 15) == sub) taken |= 1u << (best >> 4);
       sel[j] = best;
       selp[j] = expf(bv - m) * inv;  // bit-identical to the owner's p
@@ -891,12 +928,12 @@ static void allow_lds(size_t bytes) {
 
 static int emax_for(int E) { return E <= 8 ? 8 : E <= 16 ? 16 : E <= 32 ? 32 : 64; }
 
-extern "C" int moe_router_topk_fwd(const void* x, const float* wg, const float* ctx_bias,
-                                   const int32_t* ctx_img, int n_ctx, int tokens_per_image, int T,
-                                   int d, int E, int k, int normalize, int32_t* topk_idx,
-                                   float* topk_w, float* probs, float* lse,
-                                   int32_t* local_rank, int32_t* block_counts,
-                                   float* aux_partials, hipStream_t stream) {
+// Both router entries: sel_bias NULL launches the plain instantiations, else the kSel ones.
+static int router_topk_fwd_impl(const void* x, const float* wg, const float* ctx_bias, const int32_t* ctx_img,
+                                int n_ctx, int tokens_per_image, int T, int d, int E, int k, int normalize,
+                                const float* sel_bias, int32_t* topk_idx, float* topk_w, float* probs, float* lse,
+                                int32_t* local_rank, int32_t* block_counts, float* aux_partials,
+                                hipStream_t stream) {
   if (T < 0 || d <= 0 || d % 128 != 0 || d > 1024) return fail("router: d must be a multiple of 128 in [128,1024]");
   if (E < 1 || E > 64 || k < 1 || k > 8 || k > E) return fail("router: need 1<=E<=64, 1<=k<=min(8,E)");
   if ((size_t)E * d * 4 > 64 * 1024) return fail("router: E*d*4 must fit 64 KiB of LDS");
@@ -910,24 +947,54 @@ extern "C" int moe_router_topk_fwd(const void* x, const float* wg, const float* 
   constexpr int TPB = kRouterBlockTokens;
   const int nw = em <= 32 ? TPB / 4 : 4;
   const size_t shmem = (size_t)E * d * 4 + TPB * 8 * 4 + nw * (em + 1) * 4 +
-                       (ctx_bias != nullptr ? (size_t)n_ctx * E * 4 : 0);
+                       (ctx_bias != nullptr ? (size_t)n_ctx * E * 4 : 0) + (sel_bias != nullptr ? (size_t)E * 4 : 0);
   const uint16_t* xb = static_cast<const uint16_t*>(x);
   // bytes: x, Wg once, per-token outputs (idx, w, probs, lse, local rank), per-block partials
   ProfScope prof(stream, PROF_ROUTER,
                  2.0 * T * d + 4.0 * E * d + 12.0 * T * k + 4.0 * T * (E + 1) + 4.0 * nblk * (k * E + E + 1));
-#define LAUNCH_R(EM, NW)                                                                                    \
-  allow_lds<router_topk_fwd_kernel<EM, NW, TPB>>(shmem);                                                     \
-  MOE_LAUNCH(prof, (router_topk_fwd_kernel<EM, NW, TPB>), dim3(nblk), dim3(NW * 64), shmem, stream, xb, wg,  \
-             ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, topk_idx, topk_w, probs, lse, \
-             local_rank, block_counts, aux_partials)
-  switch (em) {
-    case 8: LAUNCH_R(8, TPB / 4); break;
-    case 16: LAUNCH_R(16, TPB / 4); break;
-    case 32: LAUNCH_R(32, TPB / 4); break;
-    default: LAUNCH_R(64, TPB / 16); break;
+#define LAUNCH_R(EM, NW, SEL)                                                                                    \
+  allow_lds<router_topk_fwd_kernel<EM, NW, TPB, SEL>>(shmem);                                                     \
+  MOE_LAUNCH(prof, (router_topk_fwd_kernel<EM, NW, TPB, SEL>), dim3(nblk), dim3(NW * 64), shmem, stream, xb, wg,  \
+             ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, topk_idx, topk_w, probs, lse,     \
+             local_rank, block_counts, aux_partials, sel_bias)
+#define LAUNCH_RS(EM, NW)         \
+  if (sel_bias != nullptr) {      \
+    LAUNCH_R(EM, NW, true);       \
+  } else {                        \
+    LAUNCH_R(EM, NW, false);      \
   }
+  switch (em) {
+    case 8: LAUNCH_RS(8, TPB / 4); break;
+    case 16: LAUNCH_RS(16, TPB / 4); break;
+    case 32: LAUNCH_RS(32, TPB / 4); break;
+    default: LAUNCH_RS(64, TPB / 16); break;
+  }
+#undef LAUNCH_RS
 #undef LAUNCH_R
-  return check_launch("moe_router_topk_fwd");
+  return check_launch(sel_bias != nullptr ? "moe_router_topk_fwd_sel" : "moe_router_topk_fwd");
+}
+
+extern "C" int moe_router_topk_fwd(const void* x, const float* wg, const float* ctx_bias,
+                                   const int32_t* ctx_img, int n_ctx, int tokens_per_image, int T,
+                                   int d, int E, int k, int normalize, int32_t* topk_idx,
+                                   float* topk_w, float* probs, float* lse,
+                                   int32_t* local_rank, int32_t* block_counts,
+                                   float* aux_partials, hipStream_t stream) {
+  return router_topk_fwd_impl(x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, nullptr,
+                              topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
+}
+
+extern "C" int moe_router_topk_fwd_sel(const void* x, const float* wg, const float* ctx_bias,
+                                       const int32_t* ctx_img, int n_ctx, int tokens_per_image, int T,
+                                       int d, int E, int k, int normalize, const float* sel_bias,
+                                       int32_t* topk_idx, float* topk_w, float* probs, float* lse,
+                                       int32_t* local_rank, int32_t* block_counts,
+                                       float* aux_partials, hipStream_t stream) {
+  if (sel_bias == nullptr)
+    return moe_router_topk_fwd(x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, topk_idx,
+                               topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
+  return router_topk_fwd_impl(x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, sel_bias,
+                              topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
 }
 
 extern "C" int moe_route_scan(const int32_t* block_counts, int nblk, int k, int E, int cap,

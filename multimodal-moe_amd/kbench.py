@@ -20,6 +20,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --mot-eval    the tracking evaluator against the host and a forward replay
   python multimodal-moe_amd/kbench.py --hota        the frame-parallel HOTA kernels against the host and rtdetr_mot_eval
   python multimodal-moe_amd/kbench.py --grad-accum [--cold]  the gradient-accumulation kernel over C2's parameters
+  python multimodal-moe_amd/kbench.py --balance [--cold]  loss-free load balancing: the biased router and the balance launch
 """
 from __future__ import annotations
 
@@ -446,6 +447,133 @@ def route_stats_leg(reps, rounds):
             out[key + "_min"] = round(min(v), 2)
             out[key + "_max"] = round(max(v), 2)
         print(json.dumps(out), flush=True)
+
+
+def balance_leg(reps, rounds, steps=3000):
+    """Loss-free load balancing (src/moe/balance.py).  Checks the biased router
+    against eager.route and moe_balance_step against balance_reference; times
+    the router with and without a selection bias, alternated in every round,
+    at the shapes of the ``router`` line (C2 encoder / decoder), and the
+    balance launch for C2's 7 MoE layers; then runs the update rule on the
+    kernels: a frozen router at the project's init scales (E 8, top-2, d 256,
+    6 contexts, router_init_std 0.02, ctx_init_scale 0.5), 8 images x 300
+    unit-normal decoder tokens per step, ``steps`` steps, contexts mixed per
+    image or one per batch, rate 0 and 1e-3.  Prints the max violation (max
+    load / mean - 1) and the share of assignments a capacity factor of 1.25
+    would drop, each as the mean over the first and over the last 100 steps.
+    Synthetic inputs and frozen weights: not a statement about accuracy."""
+    import math
+
+    import numpy as np
+
+    from src.moe.balance import _REC, balance_reference
+    from src.moe.eager import route
+
+    # -- checks ----------------------------------------------------------------
+    g = torch.Generator().manual_seed(0)
+    T, d, E, k, tpi, C = 2400, 256, 8, 2, 300, 6
+    x = (torch.randint(-8, 9, (T, d), generator=g).float() / 8)
+    wg = torch.randint(-4, 5, (E, d), generator=g).float() / 16
+    cb = torch.randint(-64, 65, (C, E), generator=g).float() / 64
+    sb = torch.randint(-256, 257, (E,), generator=g).float() / 128
+    ci = torch.randint(0, C, (T // tpi,), generator=g).int()
+    probs_r, lse_r, idx_r, w_r = route(x, wg, cb, ci, tpi, k, True, sb)
+    idx, w, probs, lse, *_ = L.router_topk_fwd(x.to(torch.bfloat16).cuda(), wg.cuda(), cb.cuda(), ci.cuda(), tpi, k,
+                                               True, sel_bias=sb.cuda())
+    if not torch.equal(idx.cpu().long(), idx_r):
+        raise SystemExit("the biased router's selection differs from eager.route")
+    err = max(float((probs.cpu() - probs_r).abs().max()), float((w.cpu() - w_r).abs().max()))
+    if err > 2e-6:
+        raise SystemExit(f"the biased router's probs / gates are {err:.2e} from eager.route")
+
+    def table(hists, biases):
+        rec = np.zeros(len(biases), dtype=_REC)
+        for i, b in enumerate(biases):
+            rec[i]["hist"] = 0 if hists is None else hists[i].data_ptr()
+            rec[i]["bias"] = b.data_ptr()
+        return torch.from_numpy(rec.view(np.uint8).copy()).cuda()
+
+    Lc = 7
+    hist = torch.randint(0, 1000, (Lc, E), generator=g).int()
+    bias = torch.randint(-256, 257, (Lc, E), generator=g).float() / 128
+    load_r, bias_r = hist.long(), bias.clone()
+    maxvio_r = balance_reference(load_r, bias_r, 1e-3)
+    hist_g, bias_g = hist.cuda(), bias.cuda()
+    load_g = torch.zeros((Lc, E), dtype=torch.int64, device="cuda")
+    maxvio = torch.zeros(Lc, device="cuda")
+    tab = table([hist_g[l] for l in range(Lc)], [bias_g[l] for l in range(Lc)])
+    L.balance_step(tab, Lc, E, load_g, 1e-3, True, maxvio)
+    if not (torch.equal(bias_g.cpu(), bias_r) and torch.equal(maxvio.cpu(), maxvio_r) and int(load_g.abs().sum()) == 0):
+        raise SystemExit("moe_balance_step differs from balance_reference")
+    print(json.dumps({"check": "balance", "router_idx_equal": True, "router_max_abs_err": err,
+                      "balance_step_bitwise": True}), flush=True)
+
+    # -- timing ----------------------------------------------------------------
+    shapes = {"enc": setup(8 * 920, 8, 2, 256, 1024), "dec": setup(8 * 300, 8, 2, 256, 1024, seed=1)}
+    for sname, c in shapes.items():
+        sel = torch.randn(c["E"], device="cuda") * 0.1
+        res = {"plain": [], "sel": []}
+        for _ in range(rounds):
+            res["plain"].append(timed(lambda: L.router_topk_fwd(c["x"], c["wg"], c["cb"], c["ci"], c["tpi"], c["k"],
+                                                                True), reps))
+            res["sel"].append(timed(lambda: L.router_topk_fwd(c["x"], c["wg"], c["cb"], c["ci"], c["tpi"], c["k"],
+                                                              True, sel_bias=sel), reps))
+        out = {"kernel": "router", "shape": sname, "cold": _FLUSH is not None}
+        for key, v in res.items():
+            out[key + "_us"] = round(statistics.median(v), 2)
+            out[key + "_us_min"] = round(min(v), 2)
+            out[key + "_us_max"] = round(max(v), 2)
+        out["sel_over_plain"] = round(out["sel_us"] / out["plain_us"], 4)
+        print(json.dumps(out), flush=True)
+    res = {"add": [], "apply": []}
+    for _ in range(rounds):
+        res["add"].append(timed(lambda: L.balance_step(tab, Lc, E, load_g, 1e-3, False, maxvio), reps))
+        res["apply"].append(timed(lambda: L.balance_step(tab, Lc, E, load_g, 1e-3, True, maxvio), reps))
+    out = {"kernel": "moe_balance_step", "shape": f"L{Lc} E{E}"}
+    for key, v in res.items():
+        out[key + "_us"] = round(statistics.median(v), 2)
+        out[key + "_us_min"] = round(min(v), 2)
+        out[key + "_us_max"] = round(max(v), 2)
+    print(json.dumps(out), flush=True)
+
+    # -- the rule on the kernels -------------------------------------------------
+    B = T // tpi
+    cap = int(math.ceil(1.25 * T * k / E))
+    for batches in ("mixed contexts", "one context per batch"):
+        for rate in (0.0, 1e-3):
+            gg = torch.Generator(device="cuda").manual_seed(1)
+            wgs = (torch.randn((E, d), device="cuda", generator=gg) * 0.02).float()
+            cbs = (torch.randn((C, E), device="cuda", generator=gg) * 0.5).float()
+            sbias = torch.zeros(E, device="cuda")
+            load = torch.zeros((1, E), dtype=torch.int64, device="cuda")
+            mv = torch.zeros(1, device="cuda")
+            vio = torch.zeros(steps, device="cuda")
+            drop = torch.zeros(steps, device="cuda")
+            keep = []  # every step's hist and table stay alive until the final synchronize
+            for s in range(steps):
+                xs = torch.randn((T, d), device="cuda", generator=gg).to(torch.bfloat16)
+                cis = torch.randint(0, C, (B,), device="cuda", generator=gg).int()
+                if batches != "mixed contexts":
+                    cis = cis[:1].expand(B).contiguous()
+                idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xs, wgs, cbs, cis, tpi, k, True,
+                                                                           sel_bias=sbias)
+                h = L.route_dispatch(bcnt, idx, lrank, w, auxp, T, E, 0, T * k)[2]
+                tb = table([h], [sbias])
+                L.balance_step(tb, 1, E, load, rate, True, mv)
+                vio[s] = mv[0]
+                drop[s] = (h - cap).clamp(min=0).sum() / float(T * k)
+                keep.append((h, tb))
+                if len(keep) >= 256:
+                    torch.cuda.synchronize()
+                    keep.clear()
+            torch.cuda.synchronize()
+            n = min(100, steps)
+            print(json.dumps({"simulation": batches, "rate": rate, "steps": steps, "cap_factor": 1.25,
+                              "maxvio_first": round(float(vio[:n].mean()), 3),
+                              "maxvio_last": round(float(vio[-n:].mean()), 3),
+                              "dropped_first": round(float(drop[:n].mean()), 3),
+                              "dropped_last": round(float(drop[-n:].mean()), 3),
+                              "bias_final": [round(float(v), 4) for v in sbias.cpu()]}), flush=True)
 
 
 def resize_leg(reps, rounds):
@@ -1603,6 +1731,11 @@ def main():
                          "and the host loop and exit")
     ap.add_argument("--route-stats", action="store_true",
                     help="time moe_route_stats (C2's eval shapes, batch 16) against its torch reference and exit")
+    ap.add_argument("--balance", action="store_true",
+                    help="check the biased router and moe_balance_step against their CPU statements, time the router "
+                         "with and without a selection bias and the balance launch, run the update rule for "
+                         "--balance-steps steps on a frozen synthetic router, and exit")
+    ap.add_argument("--balance-steps", type=int, default=3000)
     ap.add_argument("--resize", action="store_true",
                     help="time rtdetr_resize_pad_u8 (16 ZOD-sized frames, and identity scale) against the host "
                          "resize it replaces and exit")
@@ -1700,6 +1833,9 @@ def main():
         _FLUSH = torch.zeros(128 << 20, device="cuda", dtype=torch.float32)
     if a.grad_accum:
         grad_accum_leg(a.reps, a.rounds)
+        return
+    if a.balance:
+        balance_leg(a.reps, a.rounds, a.balance_steps)
         return
     for kv in a.tune:
         key, val = kv.split("=", 1)

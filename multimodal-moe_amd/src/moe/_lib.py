@@ -32,6 +32,8 @@ _LL = ctypes.c_longlong
 SIGNATURES = {
     "moe_router_num_blocks": (_I, [_I]),
     "moe_router_topk_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "moe_router_topk_fwd_sel": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "moe_balance_step": (_I, [_P, _I, _I, _P, _F, _I, _P, _P]),
     "moe_route_scan": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "moe_permute_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "moe_combine_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
@@ -406,8 +408,10 @@ def router_num_blocks(T: int) -> int:
     return (T + ROUTER_BLOCK_TOKENS - 1) // ROUTER_BLOCK_TOKENS
 
 
-def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize):
-    """Returns (topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials)."""
+def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias=None):
+    """Returns (topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials).
+    sel_bias fp32 [E]: the experts are selected by logits + sel_bias
+    (moe_router_topk_fwd_sel); None: moe_router_topk_fwd."""
     T, d = x.shape
     E = wg.shape[0]
     _need(x, torch.bfloat16, "x")
@@ -421,6 +425,10 @@ def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize):
         _need(ctx_img, torch.int32, "ctx_img")
         if tokens_per_image <= 0 or ctx_img.numel() * tokens_per_image < T:
             raise MoEKernelError("ctx_img does not cover every token")
+    if sel_bias is not None:
+        _need(sel_bias, torch.float32, "sel_bias")
+        if tuple(sel_bias.shape) != (E,):
+            raise MoEKernelError(f"sel_bias shape {tuple(sel_bias.shape)} != {(E,)}")
     dev = x.device
     nblk = router_num_blocks(T)
     topk_idx = torch.empty((T, k), dtype=torch.int32, device=dev)
@@ -430,13 +438,36 @@ def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize):
     local_rank = torch.empty((T, k), dtype=torch.int32, device=dev)
     block_counts = torch.empty((nblk, k, E), dtype=torch.int32, device=dev)
     aux_partials = torch.empty((nblk, E + 1), dtype=torch.float32, device=dev)
-    rc = lib().moe_router_topk_fwd(
-        _ptr(x), _ptr(wg), _ptr(ctx_bias), _ptr(ctx_img) if ctx_bias is not None else None,
-        int(ctx_bias.shape[0]) if ctx_bias is not None else 0, int(tokens_per_image), T, d, E, k, int(normalize),
-        _ptr(topk_idx), _ptr(topk_w), _ptr(probs), _ptr(lse), _ptr(local_rank),
-        _ptr(block_counts), _ptr(aux_partials), _stream())
-    _check(rc, "moe_router_topk_fwd")
+    head = (_ptr(x), _ptr(wg), _ptr(ctx_bias), _ptr(ctx_img) if ctx_bias is not None else None,
+            int(ctx_bias.shape[0]) if ctx_bias is not None else 0, int(tokens_per_image), T, d, E, k, int(normalize))
+    outs = (_ptr(topk_idx), _ptr(topk_w), _ptr(probs), _ptr(lse), _ptr(local_rank),
+            _ptr(block_counts), _ptr(aux_partials), _stream())
+    if sel_bias is None:
+        _check(lib().moe_router_topk_fwd(*head, *outs), "moe_router_topk_fwd")
+    else:
+        _check(lib().moe_router_topk_fwd_sel(*head, _ptr(sel_bias), *outs), "moe_router_topk_fwd_sel")
     return topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials
+
+
+def balance_step(table, L, E, load, rate, apply, maxvio=None):
+    """moe_balance_step: load [L, E] int64 += each layer's hist (``table``: a
+    uint8 device tensor of L records {hist pointer or 0, bias pointer}, 16 B
+    each); ``apply``: then the selection-bias update of every layer in place,
+    maxvio fp32 [L] written and the load zeroed (balance.balance_reference)."""
+    _need(load, torch.int64, "load")
+    if tuple(load.shape) != (L, E):
+        raise MoEKernelError(f"balance_step: load shape {tuple(load.shape)} != {(L, E)}")
+    if L > 0:
+        _need(table, torch.uint8, "table")
+        if table.numel() < 16 * L:
+            raise MoEKernelError(f"balance_step: table holds {table.numel()} bytes, {L} layers need {16 * L}")
+    if maxvio is not None:
+        _need(maxvio, torch.float32, "maxvio")
+        if maxvio.numel() < L:
+            raise MoEKernelError(f"balance_step: maxvio holds {maxvio.numel()} values for {L} layers")
+    rc = lib().moe_balance_step(_ptr(table) if L > 0 else None, int(L), int(E), _ptr(load), float(rate),
+                                int(bool(apply)), _ptr(maxvio), _stream())
+    _check(rc, "moe_balance_step")
 
 
 def route_scan(block_counts, cap):

@@ -33,6 +33,14 @@ local architecture spec (no network fetch), e.g.::
                                   the first E epochs, bare = 3, at least 100 iterations; -lrf<f> decays the
                                   rate linearly to f x lr over the run, f in (0, 1]; -cos makes the decay
                                   half a cosine.  Default: constant rate, no warm-up
+    rtdetr-r50-moe8-top2-alb      C2 with loss-free expert load balancing (src/moe/balance.py; Wang et al.
+                                  2024): a per-expert bias added to the router logits for the top-k
+                                  selection only, moved by a fixed rate after every optimizer step, up for
+                                  an under-loaded expert and down for an over-loaded one.  Bare = 1e-3 (the
+                                  paper's value, not tuned here), -alb<u> sets the rate (-alb0.01), u > 0;
+                                  the token implies a MoE config.  Default: no bias (balance_rate 0)
+    rtdetr-r50-moe8-top2-alb-lb0  the same without the auxiliary load-balance loss: -lb<c> sets lb_coef,
+                                  c >= 0 (default 1e-2)
 """
 from __future__ import annotations
 
@@ -73,6 +81,9 @@ class MoEConfig:
     ep_lossless_mb: float = 32.0
     router_init_std: float = 0.02
     ctx_init_scale: float = 0.5
+    # loss-free load balancing (balance.py): the selection bias' step per optimizer step; 0 = off (no
+    # bias buffer, the plain router).  Spec token -alb[<u>]
+    balance_rate: float = 0.0
 
     def capacity(self, tokens: int) -> int:
         if self.capacity_factor <= 0:
@@ -116,10 +127,12 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]][-nbs<N>][-warm[<E>]][-lrf<f>][-cos]``
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]][-nbs<N>][-warm[<E>]][-lrf<f>][-cos][-alb[<u>]][-lb<c>]``
     (``-aug``: training batch augmentation, no value; ``-mosaic[<p>]``: four-image mosaic with
     probability p, default 1.0, implies ``-aug``; ``-nbs<N>``: nominal batch size for gradient
-    accumulation; ``-warm[<E>]`` / ``-lrf<f>`` / ``-cos``: the learning-rate schedule)."""
+    accumulation; ``-warm[<E>]`` / ``-lrf<f>`` / ``-cos``: the learning-rate schedule;
+    ``-alb[<u>]``: loss-free load balancing at rate u > 0, default 1e-3, implies a MoE config;
+    ``-lb<c>``: the load-balance loss coefficient, c >= 0)."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
         raise ValueError(f"{spec!r} is a weights file, not an architecture spec")
@@ -164,6 +177,22 @@ def parse_moe_spec(spec: str) -> ModelSpec:
                 raise ValueError(f"bad final learning-rate factor {tok[3:]!r} in model spec {spec!r}") from None
             if not 0.0 < out.lrf <= 1.0:
                 raise ValueError(f"final learning-rate factor outside (0, 1] in model spec {spec!r}")
+        elif tok.startswith("alb"):
+            moe = moe or MoEConfig()
+            try:
+                moe.balance_rate = float(tok[3:]) if tok[3:] else 1e-3
+            except ValueError:
+                raise ValueError(f"bad balance rate {tok[3:]!r} in model spec {spec!r}") from None
+            if not (moe.balance_rate > 0.0 and math.isfinite(moe.balance_rate)):
+                raise ValueError(f"balance rate must be positive in model spec {spec!r}")
+        elif tok.startswith("lb"):
+            moe = moe or MoEConfig()
+            try:
+                moe.lb_coef = float(tok[2:])
+            except ValueError:
+                raise ValueError(f"bad load-balance coefficient {tok[2:]!r} in model spec {spec!r}") from None
+            if not (moe.lb_coef >= 0.0 and math.isfinite(moe.lb_coef)):
+                raise ValueError(f"negative load-balance coefficient in model spec {spec!r}")
         elif tok.startswith("moe"):
             moe = moe or MoEConfig()
             moe.num_experts = int(tok[3:])

@@ -14,14 +14,21 @@ import torch
 import torch.nn.functional as F
 
 
-def route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize):
+def route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias=None):
+    """sel_bias fp32 [E] (loss-free load balancing, balance.py): the k experts
+    are chosen by key = logits + sel_bias -- one fp32 add after the context
+    bias --; probs, lse and the gates still come from the unbiased logits, and
+    no gradient reaches the bias."""
     logits = x.float() @ wg.float().t()
     if ctx_bias is not None:
         logits = logits + ctx_bias.float()[ctx_img.long()].repeat_interleave(tokens_per_image, 0)
     probs = torch.softmax(logits, dim=-1)
     lse = torch.logsumexp(logits, dim=-1)
+    key = logits.detach()
+    if sel_bias is not None:
+        key = key + sel_bias.detach().float()
     # stable descending sort keeps the lower expert id first on ties
-    order = torch.sort(logits.detach(), dim=-1, descending=True, stable=True).indices
+    order = torch.sort(key, dim=-1, descending=True, stable=True).indices
     idx = order[:, :k]
     psel = probs.gather(1, idx)
     w = psel / psel.sum(-1, keepdim=True) if (normalize and k > 1) else psel
@@ -47,11 +54,12 @@ def dispatch_positions(idx, E, cap):
     return pos, hist, offsets
 
 
-def route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=None):
+def route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=None,
+                         sel_bias=None):
     """-> (xp [rows, d], w [T, k], lb, z, pos [T, k], hist [E], offsets [E+1], rows)."""
     T, d = x.shape
     E = wg.shape[0]
-    probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize)
+    probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias)
     pos, hist, offsets = dispatch_positions(idx, E, cap)
     if route_stats is not None:
         from .stats import record
@@ -153,12 +161,14 @@ def combine_eager(yp, w, pos, T):
 
 
 def moe_ffn_eager(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                  expert_dtype="bf16", route_stats=None):
+                  expert_dtype="bf16", route_stats=None, sel_bias=None):
     """route_stats = (table, context ids): add this forward's per-context
-    routing statistics to the table (stats.route_stats_reference)."""
+    routing statistics to the table (stats.route_stats_reference).
+    sel_bias: the layer's selection bias (route)."""
     T = x.shape[0]
     xp, w, lb, z, pos, hist, offsets, rows = route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k,
-                                                                  normalize, cap, route_stats=route_stats)
+                                                                  normalize, cap, route_stats=route_stats,
+                                                                  sel_bias=sel_bias)
     if expert_dtype == "fp8":
         yp = expert_ffn_mx_eager(xp, w1, b1, w2, b2, offsets)
     else:

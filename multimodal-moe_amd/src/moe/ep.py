@@ -277,12 +277,12 @@ def _padded_positions(idx, E, S):
     return pos, hist
 
 
-def _route_padded_eager(x, wg, ctx_bias, ctx_img, tpi, k, normalize, S):
+def _route_padded_eager(x, wg, ctx_bias, ctx_img, tpi, k, normalize, S, sel_bias=None):
     from .eager import route
 
     T, d = x.shape
     E = wg.shape[0]
-    probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tpi, k, normalize)
+    probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tpi, k, normalize, sel_bias)
     pos, hist = _padded_positions(idx, E, S)
     keep = pos >= 0
     t_idx = torch.arange(T, device=x.device).unsqueeze(1).expand(T, k)[keep]
@@ -312,6 +312,9 @@ def moe_ffn_ep(layer, x, ctx_bias, ctx_img, tokens_per_image, cap, residual=Fals
         raise ValueError(f"EP slot rows {S} must equal the layer capacity {cap}")
     fp8 = cfg.expert_dtype == "fp8"
     gs = getattr(layer, "ep_grad_scale", 1.0 / W)  # 1.0 when the optimizer applies 1/W (graph-mode TrainStep)
+    # the layer's selection bias (balance.py), replicated: a rank routes its own tokens over all E
+    # experts, so the ranks' hist sum to the global load
+    sb = getattr(layer, "sel_bias", None)
     if x.is_cuda:
         from . import _lib as L
         from .ops import aux_loss_weighted, aux_losses_hip, combine_hip as combine
@@ -319,10 +322,10 @@ def moe_ffn_ep(layer, x, ctx_bias, ctx_img, tokens_per_image, cap, residual=Fals
 
         if fp8:
             carrier, w, auxp, pos, hist, _, xq, xs, _ = route_dispatch_mx_hip(
-                x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k, cfg.normalize, cap, pad=S)
+                x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k, cfg.normalize, cap, pad=S, sel_bias=sb)
         else:
             xp, w, auxp, pos, hist, _, _ = route_dispatch_hip(x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k,
-                                                              cfg.normalize, cap, pad=S)
+                                                              cfg.normalize, cap, pad=S, sel_bias=sb)
         # lb and z from the single-GPU path's aux-loss kernel: one HIP launch each
         # way instead of ~20 torch ops (differentiable, or the weighted sum when
         # the caller passes its coefficients)
@@ -335,7 +338,7 @@ def moe_ffn_ep(layer, x, ctx_bias, ctx_img, tokens_per_image, cap, residual=Fals
         from .eager import combine_eager as combine, expert_ffn_eager, expert_ffn_mx_eager
 
         xp, w, lb, z, pos, hist = _route_padded_eager(x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k,
-                                                      cfg.normalize, S)
+                                                      cfg.normalize, S, sel_bias=sb)
     if _fused_ep_ok(layer, x, fp8):
         # counts exchange (int32; the compaction caps them at S), then the
         # receive map, the local expert offsets and this rank's overflow in ONE

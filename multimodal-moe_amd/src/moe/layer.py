@@ -49,6 +49,14 @@ class MoEFFN(nn.Module):
         self.b2 = nn.Parameter(b2)
         for p in (self.w1, self.b1, self.w2, self.b2):
             p.expert_parallel = self.ep_size > 1  # excluded from the DP all-reduce
+        # loss-free load balancing (cfg.balance_rate > 0, an -alb spec token; balance.py): a per-expert
+        # bias added to the router logits for the top-k selection only.  No gradient; balance.LoadBalancer
+        # moves it once per optimizer step; replicated on every rank.  Off: no buffer, the plain router
+        if cfg.balance_rate > 0:
+            self.register_buffer("sel_bias", torch.zeros(E, dtype=torch.float32))
+        else:
+            self.sel_bias = None
+        self.last_maxvio = None  # balancing: max load / mean load - 1 of the last optimizer step (fp32 scalar)
         self.last_aux = None   # (lb_raw, z_raw) of the last forward
         self.last_aux_weighted = None  # lb_coef lb + z_coef z (GPU path: fused kernel, differentiable)
         self.last_hist = None  # int32 [E] expert histogram of the last forward
@@ -89,7 +97,8 @@ class MoEFFN(nn.Module):
 
             y, aux, raw, hist = moe_ffn_hip(flat, self.wg, cb, self.w1, self.b1, self.w2, self.b2,
                                             ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype,
-                                            aux_coefs=(cfg.lb_coef, cfg.z_coef), residual=residual, route_stats=rs)
+                                            aux_coefs=(cfg.lb_coef, cfg.z_coef), residual=residual, route_stats=rs,
+                                            sel_bias=self.sel_bias)
             self.last_aux = (raw[0], raw[1])
             self.last_aux_weighted = aux
             self.last_hist = hist
@@ -98,7 +107,8 @@ class MoEFFN(nn.Module):
             from .eager import moe_ffn_eager
 
             y, lb, z, hist = moe_ffn_eager(flat, self.wg, cb, self.w1, self.b1, self.w2, self.b2,
-                                           ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype, route_stats=rs)
+                                           ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype, route_stats=rs,
+                                           sel_bias=self.sel_bias)
         y = y.to(x.dtype)
         if residual:
             y = flat + y

@@ -91,20 +91,28 @@ def _padded_offsets(E, pad, device):
     return t
 
 
+def _sel(sel_bias):
+    """The router's selection-bias operand (loss-free load balancing,
+    balance.py): the layer's fp32 buffer itself, so a captured launch reads the
+    values of the moment by address.  Non-differentiable: every backward is
+    that of the unbiased router."""
+    return None if sel_bias is None else sel_bias.detach().float().contiguous()
+
+
 class _RouteDispatch(torch.autograd.Function):
     """Router + scan + permute (rows copied).  ``pad`` > 0: the fixed-capacity
     layout of the expert-parallel send buffer -- expert e's kept rows at
     [e pad, e pad + min(hist_e, pad)), assignments ranked >= pad dropped."""
 
     @staticmethod
-    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0):
+    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, sel_bias=None):
         T, d = x.shape
         E = wg.shape[0]
         xb = x.to(torch.bfloat16).contiguous()
         wg32 = wg.float().contiguous()
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tokens_per_image, k,
-                                                                   normalize)
+                                                                   normalize, _sel(sel_bias))
         rank_base, hist, offsets = L.route_scan(bcnt, cap)
         if pad:
             offsets, cap = _padded_offsets(E, pad, x.device), pad
@@ -137,7 +145,7 @@ class _RouteDispatch(torch.autograd.Function):
         dx, dlogits = L.token_bwd(d_xp, pos_use, probs, idx, w, d_w, lse, dprob_bias, zc, wg32, normalize)
         # router weight + context-bias gradients: one HIP launch, fixed-order sums
         dwg, dcb = L.router_wgrad(dlogits, xb, ctx_img if has_ctx else None, tpi, C if has_ctx else 0)
-        return dx.to(xdtype), dwg, dcb, None, None, None, None, None, None, None
+        return dx.to(xdtype), dwg, dcb, None, None, None, None, None, None, None, None
 
 
 class _RouteDispatchMX(torch.autograd.Function):
@@ -147,14 +155,15 @@ class _RouteDispatchMX(torch.autograd.Function):
     that dXp (from _ExpertFFNMX.backward) reaches the dispatch transpose."""
 
     @staticmethod
-    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, stats=None):
+    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, stats=None,
+                sel_bias=None):
         T, d = x.shape
         E = wg.shape[0]
         xb = x.to(torch.bfloat16).contiguous()
         wg32 = wg.float().contiguous()
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tokens_per_image, k,
-                                                                   normalize)
+                                                                   normalize, _sel(sel_bias))
         rank_base, hist, offsets = L.route_scan(bcnt, cap)
         if pad:
             offsets, cap = _padded_offsets(E, pad, x.device), pad
@@ -182,14 +191,15 @@ class _RouteIndex(torch.autograd.Function):
     (from _ExpertFFNGather.backward) reaches the dispatch transpose."""
 
     @staticmethod
-    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, lb_coef, z_coef):
+    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, lb_coef, z_coef,
+                sel_bias=None):
         T, d = x.shape
         E = wg.shape[0]
         xb = x.to(torch.bfloat16).contiguous()
         wg32 = wg.float().contiguous()
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tokens_per_image, k,
-                                                                   normalize)
+                                                                   normalize, _sel(sel_bias))
         # scan + index (+ aux losses) in one launch (moe_route_dispatch)
         pos, tok, hist, offsets, _, out3, wcoef = L.route_dispatch(bcnt, idx, lrank, w, auxp, T, E, cap, rows,
                                                                    lb_coef, z_coef)
@@ -207,7 +217,7 @@ class _RouteIndex(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_xp, d_w, d_auxp, _p, _h, _o, _t, _a, _c):
-        return _RouteDispatch.backward(ctx, d_xp, d_w, d_auxp, _p, _h, _o)[:9] + (None, None)
+        return _RouteDispatch.backward(ctx, d_xp, d_w, d_auxp, _p, _h, _o)[:9] + (None, None, None)
 
 
 class _AuxFused(torch.autograd.Function):
@@ -416,24 +426,27 @@ def aux_losses(auxp, hist, T, k):
     return lb, z
 
 
-def route_dispatch_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0):
+def route_dispatch_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, sel_bias=None):
     """-> (xp, w, auxp, pos, hist, offsets, rows); pad > 0: fixed-capacity
-    layout (rows = E pad, offsets = e pad; see _RouteDispatch)."""
+    layout (rows = E pad, offsets = e pad; see _RouteDispatch).  sel_bias fp32
+    [E]: the experts are selected by logits + sel_bias (no gradient)."""
     T = x.shape[0]
     E = wg.shape[0]
     rows = E * pad if pad else (T * k if cap <= 0 else min(T * k, E * cap))
     return _RouteDispatch.apply(x, wg, ctx_bias, ctx_img, int(tokens_per_image), int(k), bool(normalize), int(cap),
-                                rows, int(pad)) + (rows,)
+                                rows, int(pad), sel_bias) + (rows,)
 
 
-def route_dispatch_mx_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, route_stats=None):
+def route_dispatch_mx_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, route_stats=None,
+                          sel_bias=None):
     """-> (carrier, w, auxp, pos, hist, offsets, xq, xs, rows): MXFP8 dispatch.
-    route_stats = (table, context ids): add this forward's routing statistics."""
+    route_stats = (table, context ids): add this forward's routing statistics.
+    sel_bias: as route_dispatch_hip."""
     T = x.shape[0]
     E = wg.shape[0]
     rows = E * pad if pad else (T * k if cap <= 0 else min(T * k, E * cap))
     return _RouteDispatchMX.apply(x, wg, ctx_bias, ctx_img, int(tokens_per_image), int(k), bool(normalize),
-                                  int(cap), rows, int(pad), route_stats) + (rows,)
+                                  int(cap), rows, int(pad), route_stats, sel_bias) + (rows,)
 
 
 # MOE_FUSE_RESIDUAL=0: the residual add stays a torch add (A/B switch)
@@ -463,7 +476,7 @@ class _MoELayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tpi, k, normalize, cap, lb_coef, z_coef, weighted,
-                residual=False, stats=None):
+                residual=False, stats=None, sel_bias=None):
         T, d = x.shape
         E = wg.shape[0]
         G, F, _ = w1.shape
@@ -471,7 +484,8 @@ class _MoELayer(torch.autograd.Function):
         xb = x.to(torch.bfloat16).contiguous()
         wg32 = wg.float().contiguous()
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
-        idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tpi, k, normalize)
+        idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tpi, k, normalize,
+                                                                   _sel(sel_bias))
         pos, tok, hist, offsets, gate, out3, wcoef = L.route_dispatch(bcnt, idx, lrank, w, auxp, T, E, cap, rows,
                                                                       lb_coef, z_coef, row_gate=True)
         if stats is not None:  # (table, context ids): the layer's routing statistics sink (stats.py)
@@ -531,35 +545,37 @@ class _MoELayer(torch.autograd.Function):
                                         dres=dyb if ctx.residual else None)
         # router weight + context-bias gradients: one HIP launch, fixed-order sums
         dwg, dcb = L.router_wgrad(dlogits, xb, ctx_img if has_ctx else None, tpi, C if has_ctx else 0)
-        return (dx.to(xdtype), dwg, dcb, dW1, db1, dW2, db2) + (None,) * 10
+        return (dx.to(xdtype), dwg, dcb, dW1, db1, dW2, db2) + (None,) * 11
 
 
 def moe_layer_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap, aux_coefs=None,
-                  residual=False, route_stats=None):
+                  residual=False, route_stats=None, sel_bias=None):
     """_MoELayer: -> (y, lb_coef lb + z_coef z, raw (lb, z), hist) with aux_coefs,
-    else (y, lb, z, hist); residual=True returns x + y (fused for bf16 x)."""
+    else (y, lb, z, hist); residual=True returns x + y (fused for bf16 x).
+    sel_bias fp32 [E]: the experts are selected by logits + sel_bias (no gradient)."""
     fuse = bool(residual) and x.dtype == torch.bfloat16 and _FUSE_RESIDUAL
     if aux_coefs is not None:
         out = _MoELayer.apply(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, int(tokens_per_image), int(k),
                               bool(normalize), int(cap), float(aux_coefs[0]), float(aux_coefs[1]), True, fuse,
-                              route_stats)
+                              route_stats, sel_bias)
     else:
         out = _MoELayer.apply(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, int(tokens_per_image), int(k),
-                              bool(normalize), int(cap), 1.0, 1.0, False, fuse, route_stats)
+                              bool(normalize), int(cap), 1.0, 1.0, False, fuse, route_stats, sel_bias)
     if residual and not fuse:  # fp32 activations (amp): keep the residual add in x's precision
         out = (x + out[0],) + tuple(out[1:])
     return out
 
 
-def route_index_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, aux_coefs=None):
+def route_index_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, aux_coefs=None, sel_bias=None):
     """-> (carrier, w, auxp, pos, hist, offsets, tok, out3, wcoef, rows): dispatch
-    without the row copy; out3 / wcoef are the fused aux loss (aux_coefs given)."""
+    without the row copy; out3 / wcoef are the fused aux loss (aux_coefs given).
+    sel_bias: as route_dispatch_hip."""
     T = x.shape[0]
     E = wg.shape[0]
     rows = T * k if cap <= 0 else min(T * k, E * cap)
     lb, z = aux_coefs if aux_coefs is not None else (None, None)
     return _RouteIndex.apply(x, wg, ctx_bias, ctx_img, int(tokens_per_image), int(k), bool(normalize), int(cap),
-                             rows, lb, z) + (rows,)
+                             rows, lb, z, sel_bias) + (rows,)
 
 
 def expert_ffn_gather_hip(carrier, xb, tok, w1, b1, w2, b2, offsets, rows, grad_scale=1.0):
@@ -599,7 +615,7 @@ def combine_hip(yp, w, pos, T, resid=None):
 
 
 def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                expert_dtype="bf16", aux_coefs=None, residual=False, route_stats=None):
+                expert_dtype="bf16", aux_coefs=None, residual=False, route_stats=None, sel_bias=None):
     """Routed expert FFN of one layer on the GPU.
 
     x [T, d] (tokens of ``T // tokens_per_image`` images, image-major),
@@ -614,6 +630,10 @@ def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, n
     route_stats = (table int64 [n_ctx, E, 5], context ids [images] or None):
     one more launch after the dispatch adds this forward's per-context routing
     statistics to the table (moe_route_stats); None: nothing is launched.
+    sel_bias fp32 [E] (loss-free load balancing, balance.py): the router picks
+    the k experts with the largest logits + sel_bias (moe_router_topk_fwd_sel);
+    gates, aux losses and every gradient are those of the unbiased logits, and
+    the bias itself gets none.  None: the plain router.
     """
     if not x.is_cuda:
         raise L.MoEKernelError("moe_ffn_hip needs GPU tensors")
@@ -624,11 +644,12 @@ def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, n
     T = x.shape[0]
     if expert_dtype == "fp8":
         carrier, w, auxp, pos, hist, offsets, xq, xs, rows = route_dispatch_mx_hip(
-            x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=route_stats)
+            x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=route_stats,
+            sel_bias=sel_bias)
         yp = expert_ffn_mx_hip(carrier, xq, xs, w1, b1, w2, b2, offsets, rows)
     else:
         return moe_layer_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                             aux_coefs, residual=residual, route_stats=route_stats)
+                             aux_coefs, residual=residual, route_stats=route_stats, sel_bias=sel_bias)
     y = combine_hip(yp, w, pos, T)
     if residual:
         y = x + y.to(x.dtype)

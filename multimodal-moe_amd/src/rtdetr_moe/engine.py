@@ -510,6 +510,8 @@ def _moe_stats(model: RTDETRMoE) -> dict:
         if m.last_hist is not None:
             h = m.last_hist.detach().float().cpu()
             out[f"moe/l{i}_load_cv"] = float(h.std() / h.mean().clamp(min=1e-9))
+        if getattr(m, "last_maxvio", None) is not None:  # load balancing on: max load / mean - 1 of the last step
+            out[f"moe/l{i}_maxvio"] = float(m.last_maxvio.detach())
         if getattr(m, "last_ep_overflow", None) is not None:
             out[f"moe/l{i}_ep_overflow"] = int(m.last_ep_overflow)
         if m.last_aux is not None:

@@ -43,7 +43,11 @@ What stays outside every graph:
 - gradient accumulation (an -nbs<N> spec, TrainStep(accumulate=K)): a replay
   overwrites the static gradient buffers, so after each one a HIP launch adds
   them to an fp32 sum (optim.GradAccumulator); every K-th call runs the
-  data-parallel exchange and the optimizer once, on the mean gradient.
+  data-parallel exchange and the optimizer once, on the mean gradient;
+- loss-free load balancing (an -alb spec, moe.balance.LoadBalancer): one HIP
+  launch after each replay adds every MoE layer's expert histogram to an int64
+  load table, and one ahead of the optimizer step moves the layers' selection
+  biases, which the captured router launches read by address.
 """
 from __future__ import annotations
 
@@ -576,7 +580,8 @@ class TrainStep:
           3. the optimizer takes over the parameters: fp32    }
              ones become views of its flat spaces
           4. the accumulator, when accumulate > 1 (GPU)
-          5. ep_grad_scale = 1.0 on expert-parallel MoE layers
+          5. ep_grad_scale = 1.0 on expert-parallel MoE layers, then the load
+             balancer (an -alb spec)                              _build_balancer
           6. augmenter, image conversion and _cast_in           _build_augmenter
           7. DenoisingState (its generator)
           8. warm-up and capture                                _build_runner
@@ -615,6 +620,9 @@ class TrainStep:
             self._accumulator()
         if world > 1 and images.is_cuda:
             self._unscale_expert_parallel()
+        # loss-free load balancing (an -alb spec): None when no layer has a selection bias, and the
+        # step is unchanged.  Built before the capture: _bind_grads pins it to each capture's hist
+        self.balancer = self._build_balancer()
         self._m_in = 16  # the mosaic path's raw-target padding: grows with the batches' counts
         self.aug, images, max_boxes = self._build_augmenter(spec, augment, mosaic, images, targets, content_hw, seed)
         images = self._cast_in(images)
@@ -674,6 +682,19 @@ class TrainStep:
         for m in self.model.modules():
             if isinstance(m, MoEFFN) and m.ep_size > 1:
                 m.ep_grad_scale = 1.0
+
+    def _build_balancer(self):
+        """-> moe.balance.LoadBalancer or None.  Its two launches stay outside
+        every graph: add() after each micro-step's forward, apply() where the
+        optimizer steps; the captures' warm-up passes therefore move neither
+        the biases nor the load, and the captured router launch reads the
+        biases by address."""
+        from ..moe.balance import LoadBalancer, balanced_layers
+
+        layers = balanced_layers(self.model)
+        if not layers:
+            return None
+        return LoadBalancer(self.model, layers[0].cfg.balance_rate, group=None, world=self.world)
 
     def _build_augmenter(self, spec, augment, mosaic, images, targets, content_hw, seed):
         """-> (aug or None, the images as the step's example input, the first
@@ -737,6 +758,8 @@ class TrainStep:
         a capture (the reducer rebuilds its table when the addresses change)."""
         for p, g in zip(self.params, static_grads):
             p.grad = g
+        if self.balancer is not None:  # the new capture's static hist tensors are what every replay writes
+            self.balancer.pin()
 
     def _augment_in_place(self, images, targets):
         """Graphed step: pad the incoming targets into the augmenter's raw
@@ -794,6 +817,8 @@ class TrainStep:
             self.graphs = False
             for p in self.params:
                 p.grad = None
+            if self.balancer is not None:
+                self.balancer.unpin()
             _drop_autograd_graphs(self.model)  # the captures' AccumulateGrad nodes (side stream) go too
 
     def _allreduce_grads(self, grads=None):
@@ -917,7 +942,10 @@ class TrainStep:
         """FlatAdamW / ShardedDPAdamW (reduction + clip inside)."""
         # with a weight average, ModelEMA.update runs the optimizer step with this update's decay
         opt_step = self.opt.step if self.ema is None else self.ema.update
+        if self.balancer is not None:  # this micro-step's expert loads; applied with the optimizer step below
+            self.balancer.add()
         if self.accumulate <= 1 and (self.acc is None or self.acc.count == 0):
+            self._balance_apply()
             if self.reducer is not None:
                 opt_step(self._allreduce_grads(), inv_world=1.0 / self.world)
             else:
@@ -931,16 +959,27 @@ class TrainStep:
         if acc.count < self.accumulate:
             return
         grads, count = acc.take()
+        self._balance_apply()
         if self.reducer is not None:
             grads = self._allreduce_grads(grads)
         opt_step(grads, inv_world=1.0 / (self.world * count))
         self.opt_steps += 1
 
+    def _balance_apply(self):
+        """Once per optimizer step, ahead of it: the selection biases move by
+        the load summed since the last one (over the ranks at world > 1), so a
+        weight average taken in the optimizer step blends the new biases."""
+        if self.balancer is not None:
+            self.balancer.apply()
+
     def _optimizer_step_cpu(self):
         """torch.optim.AdamW on the gradients autograd summed in ``.grad``."""
         self._pending += 1
+        if self.balancer is not None:
+            self.balancer.add()
         if self._pending < self.accumulate:
             return
+        self._balance_apply()
         if self._pending > 1:  # autograd summed the cycle's backward passes: the mean
             with torch.no_grad():
                 for p in self.opt_params:

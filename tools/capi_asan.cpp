@@ -106,6 +106,18 @@ int main() {
   expect_error("route_stats n_ctx=0", moe_route_stats(i32, f32, i32, f32, i32, 0, 6, 12, 8, 2, i64, s));
   expect_error("route_stats ctx=NULL n_ctx=6", moe_route_stats(i32, f32, i32, f32, nullptr, 6, 6, 12, 8, 2, i64, s));
   expect_error("route_stats stats=NULL", moe_route_stats(i32, f32, i32, f32, i32, 6, 6, 12, 8, 2, nullptr, s));
+  expect_error("router_topk_fwd_sel E=0", moe_router_topk_fwd_sel(p, f32, nullptr, nullptr, 0, 16, 16, 256, 0, 1, 1, f32,
+                                                                  i32, f32, f32, f32, i32, i32, f32, s));
+  expect_error("router_topk_fwd_sel d=100", moe_router_topk_fwd_sel(p, f32, nullptr, nullptr, 0, 16, 16, 100, 8, 2, 1,
+                                                                    f32, i32, f32, f32, f32, i32, i32, f32, s));
+  expect_error("router_topk_fwd_sel sel=NULL k>E", moe_router_topk_fwd_sel(p, f32, nullptr, nullptr, 0, 16, 16, 256, 2, 3,
+                                                                           1, nullptr, i32, f32, f32, f32, i32, i32, f32,
+                                                                           s));
+  expect_error("balance_step E=0", moe_balance_step(buf, 2, 0, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step E=65", moe_balance_step(buf, 2, 65, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step L=-1", moe_balance_step(buf, -1, 8, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step table=NULL", moe_balance_step(nullptr, 2, 8, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step load=NULL", moe_balance_step(buf, 2, 8, nullptr, 1e-3f, 1, f32, s));
   expect_error("resize_pad src=NULL", rtdetr_resize_pad_u8(nullptr, i64, 1, 32, 32, 32, 32, f32, s));
   expect_error("resize_pad desc=NULL", rtdetr_resize_pad_u8(u8, nullptr, 1, 32, 32, 32, 32, f32, s));
   expect_error("resize_pad dst=NULL", rtdetr_resize_pad_u8(u8, i64, 1, 32, 32, 32, 32, nullptr, s));
