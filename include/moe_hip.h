@@ -78,6 +78,20 @@ int moe_router_topk_fwd_sel(const void* x, const float* wg, const float* ctx_bia
                             int32_t* local_rank, int32_t* block_counts,
                             float* aux_partials, hipStream_t stream);
 
+/* The router with a PER-CONTEXT selection bias: moe_router_topk_fwd_sel with
+ * sel_bias fp32 [n_ctx, E] and key[t,e] = fl32(logits[t,e] +
+ * sel_bias[ctx_img[t / tokens_per_image], e]).  ctx_bias, ctx_img and sel_bias
+ * are all required (n_ctx is both tables' row count).  The whole table is
+ * staged in LDS behind the context-bias table: a launch whose dynamic LDS
+ * (E d 4 + 2 n_ctx E 4 + about 1.5 KiB) exceeds 96 KiB is refused with an
+ * error and nothing is launched (E 64, d 256, n_ctx 64 is the example). */
+int moe_router_topk_fwd_selctx(const void* x, const float* wg, const float* ctx_bias,
+                               const int32_t* ctx_img, int n_ctx, int tokens_per_image,
+                               int T, int d, int E, int k, int normalize, const float* sel_bias,
+                               int32_t* topk_idx, float* topk_w, float* probs, float* lse,
+                               int32_t* local_rank, int32_t* block_counts,
+                               float* aux_partials, hipStream_t stream);
+
 /* The selection biases' update, ONE launch for all L MoE layers of a model.
  * table: device array of L records {const int32_t* hist (or NULL); float*
  * bias} (16 B each); load: int64 [L, E]; maxvio: fp32 [L] or NULL.
@@ -93,6 +107,23 @@ int moe_router_topk_fwd_sel(const void* x, const float* wg, const float* ctx_bia
  * 1..64, L >= 0 (L == 0: nothing is launched). */
 int moe_balance_step(const void* table, int L, int E, long long* load, float rate, int apply,
                      float* maxvio, hipStream_t stream);
+
+/* The per-context form, ONE launch for all L layers, grid (C, L).  table:
+ * device array of L records {const int32_t* topk_idx [T, k] (or NULL); float*
+ * bias [C, E]; const int32_t* ctx_img [T / tokens_per_image]; int T; int
+ * tokens_per_image} (32 B each); load: int64 [L, C, E]; maxvio: fp32 [L, C] or
+ * NULL.  Workgroup (c, l):
+ *   load[l,c,e] += the number of (t, j) with topk_idx[t,j] == e among the
+ *                  tokens t of the images with ctx_img == c   (topk_idx non-NULL)
+ * and, when apply != 0, moe_balance_step's rule on row (l, c) of load, bias and
+ * maxvio (a row without load is not touched, maxvio 0).  An expert id outside
+ * [0, E) and a context id outside [0, C) count nowhere.  Integer counters
+ * only: bit for bit balance_reference on the rows, in any workgroup order.
+ * E in 1..64, k in 1..min(8, E), C >= 1, 0 <= L <= 65535 (0: nothing is
+ * launched); the caller guarantees T / tokens_per_image context ids and T k
+ * indices behind the table's pointers. */
+int moe_balance_step_ctx(const void* table, int L, int C, int E, int k, long long* load, float rate,
+                         int apply, float* maxvio, hipStream_t stream);
 
 /* a4, index half: exclusive scans of the block counts.
  * Assignment (t,j) to expert e has rank r = slot_base[j,e] + sum_{b'<b}

@@ -7,10 +7,12 @@
 //                    for E > 32);
 //                    16 lanes per token, each lane owning d/16 channels read as
 //                    16-B chunks (a token row is read by 16 lanes, 4 tokens per
-//                    wave-instruction).  The kSel instantiation (moe_router_
-//                    topk_fwd_sel) ranks the experts by logit + sel_bias[e]
-//                    (loss-free load balancing); everything else, the gates
-//                    included, still comes from the unbiased logits.
+//                    wave-instruction).  The kSel instantiations rank the
+//                    experts by logit + a selection bias (loss-free load
+//                    balancing): kSel 1 (moe_router_topk_fwd_sel) sel_bias[e],
+//                    kSel 2 (moe_router_topk_fwd_selctx) sel_bias[ctx(t)][e];
+//                    everything else, the gates included, still comes from
+//                    the unbiased logits.
 //  route_scan      : one workgroup; each (slot, expert) column split into
 //                    1024/(k*E) block segments (coalesced row reads), segment
 //                    sums -> exclusive prefixes, then hist / kept offsets
@@ -59,7 +61,8 @@ __device__ __forceinline__ void argmax_stage_sel(float& bv, float& bl, int& best
   if (ov > bv || (ov == bv && oi < best)) { bv = ov; bl = ol; best = oi; }
 }
 
-template <int EMAX, int NW, int TPB, bool kSel>
+// kSel: 0 no selection bias, 1 sel_bias fp32 [E], 2 sel_bias fp32 [n_ctx][E] indexed by the token's context
+template <int EMAX, int NW, int TPB, int kSel>
 __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     const uint16_t* __restrict__ x, const float* __restrict__ wg,
     const float* __restrict__ ctx_bias, const int32_t* __restrict__ ctx_img, int n_ctx,
@@ -115,9 +118,11 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
   }
   if (has_ctx)
     for (int i = tid; i < n_ctx * E; i += NT) s_cb[i] = ctx_bias[i];
-  float* s_sb = s_cb + (has_ctx ? n_ctx * E : 0);  // [E] the selection bias (kSel only)
-  if constexpr (kSel)
+  float* s_sb = s_cb + (has_ctx ? n_ctx * E : 0);  // the selection bias: [E] (kSel 1), [n_ctx][E] (kSel 2)
+  if constexpr (kSel == 1)
     for (int i = tid; i < E; i += NT) s_sb[i] = sel_bias[i];
+  if constexpr (kSel == 2)
+    for (int i = tid; i < n_ctx * E; i += NT) s_sb[i] = sel_bias[i];
   for (int i = tid; i < TPB * 8; i += NT) s_idx[i] = -1;
   __syncthreads();
 
@@ -197,10 +202,15 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     const float lse = m + logf(ssm);
 
     // kSel: the selection key fl(logit + sel_bias[e]), one add after the context bias
+    // (kSel 2: the row of the token's context, as the context bias above)
     float key[Q];
-    if constexpr (kSel) {
+    if constexpr (kSel == 1) {
 #pragma unroll
       for (int q = 0; q < Q; ++q) key[q] = own[q] ? logit[q] + s_sb[16 * q + sub] : 0.f;
+    }
+    if constexpr (kSel == 2) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) key[q] = own[q] ? logit[q] + s_sb[cid[it] * E + 16 * q + sub] : 0.f;
     }
 
     // top-k on logits (monotone in probs), kSel: on the keys; ties -> lower expert id
@@ -211,7 +221,7 @@ __global__ __launch_bounds__(NW * 64) void router_topk_fwd_kernel(
     _Pragma("unroll") for (int j = 0; j < 8; ++j) if (j < k) {
       int best = 0x7fffffff;
       float bv = -INFINITY;
-      if constexpr (kSel) {
+      if constexpr (kSel != 0) {
         float bl = 0.f;  // the unbiased logit of the expert whose key is bv
 #pragma unroll
         for (int q = 0; q < Q; ++q)
@@ -917,19 +927,21 @@ extern "C" int moe_router_num_blocks(int T) { return (T + kRouterBlockTokens - 1
 
 // Raise the dynamic-LDS cap of a kernel (once, on its first launch) so a
 // launch needing more than 64 KiB succeeds; later launches make no call.
+constexpr size_t kRouterLdsCap = 96 * 1024;
 template <auto FN>
 static void allow_lds(size_t bytes) {
   // (per device; a failure is reported through moe_last_error and the launch
   // that follows fails its check_launch)
   static unsigned long long done = 0;
-  (void)allow_dyn_lds(reinterpret_cast<const void*>(FN), 96 * 1024, &done, "router: dynamic LDS");
+  (void)allow_dyn_lds(reinterpret_cast<const void*>(FN), (int)kRouterLdsCap, &done, "router: dynamic LDS");
   (void)bytes;
 }
 
 static int emax_for(int E) { return E <= 8 ? 8 : E <= 16 ? 16 : E <= 32 ? 32 : 64; }
 
-// Both router entries: sel_bias NULL launches the plain instantiations, else the kSel ones.
-static int router_topk_fwd_impl(const void* x, const float* wg, const float* ctx_bias, const int32_t* ctx_img,
+// The three router entries: sel_mode 0 (sel_bias NULL) launches the plain instantiations, 1 the per-expert
+// bias' (sel_bias [E]), 2 the per-context bias' (sel_bias [n_ctx, E]).
+static int router_topk_fwd_impl(int sel_mode, const void* x, const float* wg, const float* ctx_bias, const int32_t* ctx_img,
                                 int n_ctx, int tokens_per_image, int T, int d, int E, int k, int normalize,
                                 const float* sel_bias, int32_t* topk_idx, float* topk_w, float* probs, float* lse,
                                 int32_t* local_rank, int32_t* block_counts, float* aux_partials,
@@ -941,13 +953,20 @@ static int router_topk_fwd_impl(const void* x, const float* wg, const float* ctx
   if ((ctx_bias != nullptr) != (ctx_img != nullptr)) return fail("router: ctx_bias and ctx_img go together");
   if (ctx_bias != nullptr && (n_ctx < 1 || (size_t)n_ctx * E > 4096))
     return fail("router: need 1 <= n_ctx and n_ctx * E <= 4096 (the context-bias table is staged in LDS)");
-  if (T == 0) return 0;
+  if (sel_mode == 2 && (sel_bias == nullptr || ctx_img == nullptr))
+    return fail("router: a per-context selection bias needs sel_bias, ctx_bias and ctx_img");
   const int nblk = moe_router_num_blocks(T);
   const int em = emax_for(E);
   constexpr int TPB = kRouterBlockTokens;
   const int nw = em <= 32 ? TPB / 4 : 4;
   const size_t shmem = (size_t)E * d * 4 + TPB * 8 * 4 + nw * (em + 1) * 4 +
-                       (ctx_bias != nullptr ? (size_t)n_ctx * E * 4 : 0) + (sel_bias != nullptr ? (size_t)E * 4 : 0);
+                       (ctx_bias != nullptr ? (size_t)n_ctx * E * 4 : 0) +
+                       (sel_mode == 2 ? (size_t)n_ctx * E * 4 : sel_mode == 1 ? (size_t)E * 4 : 0);
+  // the per-context table is the one operand that can pass the checks above and still not fit
+  if (sel_mode == 2 && shmem > kRouterLdsCap)
+    return fail("router: Wg, the context-bias table and the [n_ctx, E] selection bias need " +
+                std::to_string(shmem) + " B of LDS, over the " + std::to_string(kRouterLdsCap) + " B cap");
+  if (T == 0) return 0;
   const uint16_t* xb = static_cast<const uint16_t*>(x);
   // bytes: x, Wg once, per-token outputs (idx, w, probs, lse, local rank), per-block partials
   ProfScope prof(stream, PROF_ROUTER,
@@ -958,10 +977,12 @@ static int router_topk_fwd_impl(const void* x, const float* wg, const float* ctx
              ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, topk_idx, topk_w, probs, lse,     \
              local_rank, block_counts, aux_partials, sel_bias)
 #define LAUNCH_RS(EM, NW)         \
-  if (sel_bias != nullptr) {      \
-    LAUNCH_R(EM, NW, true);       \
+  if (sel_mode == 2) {            \
+    LAUNCH_R(EM, NW, 2);          \
+  } else if (sel_mode == 1) {     \
+    LAUNCH_R(EM, NW, 1);          \
   } else {                        \
-    LAUNCH_R(EM, NW, false);      \
+    LAUNCH_R(EM, NW, 0);          \
   }
   switch (em) {
     case 8: LAUNCH_RS(8, TPB / 4); break;
@@ -971,7 +992,8 @@ static int router_topk_fwd_impl(const void* x, const float* wg, const float* ctx
   }
 #undef LAUNCH_RS
 #undef LAUNCH_R
-  return check_launch(sel_bias != nullptr ? "moe_router_topk_fwd_sel" : "moe_router_topk_fwd");
+  return check_launch(sel_mode == 2 ? "moe_router_topk_fwd_selctx"
+                                    : sel_mode == 1 ? "moe_router_topk_fwd_sel" : "moe_router_topk_fwd");
 }
 
 extern "C" int moe_router_topk_fwd(const void* x, const float* wg, const float* ctx_bias,
@@ -980,7 +1002,7 @@ extern "C" int moe_router_topk_fwd(const void* x, const float* wg, const float* 
                                    float* topk_w, float* probs, float* lse,
                                    int32_t* local_rank, int32_t* block_counts,
                                    float* aux_partials, hipStream_t stream) {
-  return router_topk_fwd_impl(x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, nullptr,
+  return router_topk_fwd_impl(0, x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, nullptr,
                               topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
 }
 
@@ -993,7 +1015,19 @@ extern "C" int moe_router_topk_fwd_sel(const void* x, const float* wg, const flo
   if (sel_bias == nullptr)
     return moe_router_topk_fwd(x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, topk_idx,
                                topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
-  return router_topk_fwd_impl(x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, sel_bias,
+  return router_topk_fwd_impl(1, x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, sel_bias,
+                              topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
+}
+
+// The per-context selection bias: sel_bias fp32 [n_ctx, E], a token ranked by logit + sel_bias[ctx_img[t / tpi]][e].
+// ctx_bias, ctx_img and sel_bias are all required; a table that does not fit the LDS cap is refused, not launched.
+extern "C" int moe_router_topk_fwd_selctx(const void* x, const float* wg, const float* ctx_bias,
+                                          const int32_t* ctx_img, int n_ctx, int tokens_per_image, int T,
+                                          int d, int E, int k, int normalize, const float* sel_bias,
+                                          int32_t* topk_idx, float* topk_w, float* probs, float* lse,
+                                          int32_t* local_rank, int32_t* block_counts,
+                                          float* aux_partials, hipStream_t stream) {
+  return router_topk_fwd_impl(2, x, wg, ctx_bias, ctx_img, n_ctx, tokens_per_image, T, d, E, k, normalize, sel_bias,
                               topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials, stream);
 }
 

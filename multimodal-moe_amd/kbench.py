@@ -461,12 +461,20 @@ def balance_leg(reps, rounds, steps=3000):
     image or one per batch, rate 0 and 1e-3.  Prints the max violation (max
     load / mean - 1) and the share of assignments a capacity factor of 1.25
     would drop, each as the mean over the first and over the last 100 steps.
-    Synthetic inputs and frozen weights: not a statement about accuracy."""
+    The per-context form (-albc: moe_router_topk_fwd_selctx,
+    moe_balance_step_ctx) has the same legs: checks against eager.route with a
+    [C, E] table and against context_counts + balance_reference on the rows;
+    the three routers alternated; the balance launch with mixed contexts and
+    with all images in one (the worst case: one workgroup per layer counts
+    everything) at C2's and C5's shapes; the simulation with a [C, E] table at
+    rates 1e-3 and 1e-2 (max violation and drops of the whole batch, as in the
+    other rows).  Synthetic inputs and frozen weights: not a statement about
+    accuracy."""
     import math
 
     import numpy as np
 
-    from src.moe.balance import _REC, balance_reference
+    from src.moe.balance import _REC, _REC_CTX, balance_reference, context_counts
     from src.moe.eager import route
 
     # -- checks ----------------------------------------------------------------
@@ -508,22 +516,70 @@ def balance_leg(reps, rounds, steps=3000):
     print(json.dumps({"check": "balance", "router_idx_equal": True, "router_max_abs_err": err,
                       "balance_step_bitwise": True}), flush=True)
 
+    # the per-context form
+    sbc = torch.randint(-256, 257, (C, E), generator=g).float() / 128
+    probs_r, lse_r, idx_r, w_r = route(x, wg, cb, ci, tpi, k, True, sbc)
+    idx, w, probs, lse, *_ = L.router_topk_fwd(x.to(torch.bfloat16).cuda(), wg.cuda(), cb.cuda(), ci.cuda(), tpi, k,
+                                               True, sel_bias=sbc.cuda())
+    if not torch.equal(idx.cpu().long(), idx_r):
+        raise SystemExit("the per-context router's selection differs from eager.route")
+    errc = max(float((probs.cpu() - probs_r).abs().max()), float((w.cpu() - w_r).abs().max()))
+    if errc > 2e-6:
+        raise SystemExit(f"the per-context router's probs / gates are {errc:.2e} from eager.route")
+
+    def ctx_table(idxs, biases, ctxs, tpis):
+        rec = np.zeros(len(biases), dtype=_REC_CTX)
+        for i, b in enumerate(biases):
+            rec[i]["topk_idx"] = 0 if idxs is None else idxs[i].data_ptr()
+            rec[i]["bias"], rec[i]["ctx_img"] = b.data_ptr(), ctxs[i].data_ptr()
+            rec[i]["T"], rec[i]["tokens_per_image"] = ctxs[i].numel() * tpis[i], tpis[i]
+        return torch.from_numpy(rec.view(np.uint8).copy()).cuda()
+
+    def ctx_case(Ec, kc, Bc, single):
+        """C2 / C5-like: one encoder layer (920 tokens per image) and six decoder layers (300)."""
+        tp = [920] + [300] * (Lc - 1)
+        ids = [torch.rand((Bc * t, Ec), generator=g).argsort(1)[:, :kc].int().contiguous() for t in tp]
+        cs = [torch.randint(0, C, (Bc,), generator=g).int() for _ in tp]
+        if single:
+            cs = [c[:1].expand(Bc).contiguous() for c in cs]
+        return tp, ids, cs
+
+    tp, ids, cs = ctx_case(E, k, 8, False)
+    biasc = torch.randint(-256, 257, (Lc, C, E), generator=g).float() / 128
+    loadc_r = torch.stack([context_counts(i, c, t, C, E) for i, c, t in zip(ids, cs, tp)])
+    biasc_r = biasc.clone()
+    mvc_r = balance_reference(loadc_r.view(-1, E), biasc_r.view(-1, E), 1e-3).view(Lc, C)
+    ids_g, cs_g, biasc_g = [i.cuda() for i in ids], [c.cuda() for c in cs], biasc.cuda()
+    loadc_g = torch.zeros((Lc, C, E), dtype=torch.int64, device="cuda")
+    mvc = torch.zeros((Lc, C), device="cuda")
+    tabc = ctx_table(ids_g, [biasc_g[l] for l in range(Lc)], cs_g, tp)
+    L.balance_step_ctx(tabc, Lc, C, E, k, loadc_g, 1e-3, True, mvc)
+    if not (torch.equal(biasc_g.cpu(), biasc_r) and torch.equal(mvc.cpu(), mvc_r) and int(loadc_g.abs().sum()) == 0):
+        raise SystemExit("moe_balance_step_ctx differs from context_counts + balance_reference")
+    print(json.dumps({"check": "balance per context", "router_idx_equal": True, "router_max_abs_err": errc,
+                      "balance_step_ctx_bitwise": True}), flush=True)
+
     # -- timing ----------------------------------------------------------------
     shapes = {"enc": setup(8 * 920, 8, 2, 256, 1024), "dec": setup(8 * 300, 8, 2, 256, 1024, seed=1)}
     for sname, c in shapes.items():
         sel = torch.randn(c["E"], device="cuda") * 0.1
-        res = {"plain": [], "sel": []}
+        selc = torch.randn((6, c["E"]), device="cuda") * 0.1
+        res = {"plain": [], "sel": [], "selctx": []}
         for _ in range(rounds):
             res["plain"].append(timed(lambda: L.router_topk_fwd(c["x"], c["wg"], c["cb"], c["ci"], c["tpi"], c["k"],
                                                                 True), reps))
             res["sel"].append(timed(lambda: L.router_topk_fwd(c["x"], c["wg"], c["cb"], c["ci"], c["tpi"], c["k"],
                                                               True, sel_bias=sel), reps))
+            res["selctx"].append(timed(lambda: L.router_topk_fwd(c["x"], c["wg"], c["cb"], c["ci"], c["tpi"], c["k"],
+                                                                 True, sel_bias=selc), reps))
         out = {"kernel": "router", "shape": sname, "cold": _FLUSH is not None}
         for key, v in res.items():
             out[key + "_us"] = round(statistics.median(v), 2)
             out[key + "_us_min"] = round(min(v), 2)
             out[key + "_us_max"] = round(max(v), 2)
         out["sel_over_plain"] = round(out["sel_us"] / out["plain_us"], 4)
+        out["selctx_over_plain"] = round(out["selctx_us"] / out["plain_us"], 4)
+        out["selctx_over_sel"] = round(out["selctx_us"] / out["sel_us"], 4)
         print(json.dumps(out), flush=True)
     res = {"add": [], "apply": []}
     for _ in range(rounds):
@@ -535,18 +591,37 @@ def balance_leg(reps, rounds, steps=3000):
         out[key + "_us_min"] = round(min(v), 2)
         out[key + "_us_max"] = round(max(v), 2)
     print(json.dumps(out), flush=True)
+    for Ec, kc, Bc in ((8, 2, 8), (32, 4, 16)):  # C2's and C5's MoE layers
+        for single in (False, True):
+            tp, ids, cs = ctx_case(Ec, kc, Bc, single)
+            ids_g, cs_g = [i.cuda() for i in ids], [c.cuda() for c in cs]
+            bg = torch.zeros((Lc, C, Ec), device="cuda")
+            lg = torch.zeros((Lc, C, Ec), dtype=torch.int64, device="cuda")
+            mg = torch.zeros((Lc, C), device="cuda")
+            tb = ctx_table(ids_g, [bg[l] for l in range(Lc)], cs_g, tp)
+            res = {"add": [], "apply": []}
+            for _ in range(rounds):
+                res["add"].append(timed(lambda: L.balance_step_ctx(tb, Lc, C, Ec, kc, lg, 1e-3, False, mg), reps))
+                res["apply"].append(timed(lambda: L.balance_step_ctx(tb, Lc, C, Ec, kc, lg, 1e-3, True, mg), reps))
+            out = {"kernel": "moe_balance_step_ctx", "shape": f"L{Lc} C{C} E{Ec} k{kc} batch {Bc}",
+                   "contexts": "one per batch" if single else "mixed"}
+            for key, v in res.items():
+                out[key + "_us"] = round(statistics.median(v), 2)
+                out[key + "_us_min"] = round(min(v), 2)
+                out[key + "_us_max"] = round(max(v), 2)
+            print(json.dumps(out), flush=True)
 
     # -- the rule on the kernels -------------------------------------------------
     B = T // tpi
     cap = int(math.ceil(1.25 * T * k / E))
     for batches in ("mixed contexts", "one context per batch"):
-        for rate in (0.0, 1e-3):
+        for rate, per_ctx in ((0.0, False), (1e-3, False), (1e-3, True), (1e-2, True)):
             gg = torch.Generator(device="cuda").manual_seed(1)
             wgs = (torch.randn((E, d), device="cuda", generator=gg) * 0.02).float()
             cbs = (torch.randn((C, E), device="cuda", generator=gg) * 0.5).float()
-            sbias = torch.zeros(E, device="cuda")
-            load = torch.zeros((1, E), dtype=torch.int64, device="cuda")
-            mv = torch.zeros(1, device="cuda")
+            sbias = torch.zeros((C, E) if per_ctx else E, device="cuda")
+            load = torch.zeros((1, C, E) if per_ctx else (1, E), dtype=torch.int64, device="cuda")
+            mv = torch.zeros(C if per_ctx else 1, device="cuda")
             vio = torch.zeros(steps, device="cuda")
             drop = torch.zeros(steps, device="cuda")
             keep = []  # every step's hist and table stay alive until the final synchronize
@@ -558,22 +633,28 @@ def balance_leg(reps, rounds, steps=3000):
                 idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xs, wgs, cbs, cis, tpi, k, True,
                                                                            sel_bias=sbias)
                 h = L.route_dispatch(bcnt, idx, lrank, w, auxp, T, E, 0, T * k)[2]
-                tb = table([h], [sbias])
-                L.balance_step(tb, 1, E, load, rate, True, mv)
-                vio[s] = mv[0]
+                if per_ctx:  # the rows move by their contexts' loads; the violation reported is the batch's
+                    tb = ctx_table([idx], [sbias], [cis], [tpi])
+                    L.balance_step_ctx(tb, 1, C, E, k, load, rate, True, mv)
+                    vio[s] = (E * h.max() - h.sum()) / h.sum()
+                else:
+                    tb = table([h], [sbias])
+                    L.balance_step(tb, 1, E, load, rate, True, mv)
+                    vio[s] = mv[0]
                 drop[s] = (h - cap).clamp(min=0).sum() / float(T * k)
-                keep.append((h, tb))
+                keep.append((h, tb, idx, cis))
                 if len(keep) >= 256:
                     torch.cuda.synchronize()
                     keep.clear()
             torch.cuda.synchronize()
             n = min(100, steps)
-            print(json.dumps({"simulation": batches, "rate": rate, "steps": steps, "cap_factor": 1.25,
+            print(json.dumps({"simulation": batches, "bias": "per context" if per_ctx else "per expert",
+                              "rate": rate, "steps": steps, "cap_factor": 1.25,
                               "maxvio_first": round(float(vio[:n].mean()), 3),
                               "maxvio_last": round(float(vio[-n:].mean()), 3),
                               "dropped_first": round(float(drop[:n].mean()), 3),
                               "dropped_last": round(float(drop[-n:].mean()), 3),
-                              "bias_final": [round(float(v), 4) for v in sbias.cpu()]}), flush=True)
+                              "bias_final": [round(float(v), 4) for v in sbias.cpu().reshape(-1)]}), flush=True)
 
 
 def resize_leg(reps, rounds):

@@ -33,7 +33,9 @@ SIGNATURES = {
     "moe_router_num_blocks": (_I, [_I]),
     "moe_router_topk_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "moe_router_topk_fwd_sel": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "moe_router_topk_fwd_selctx": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "moe_balance_step": (_I, [_P, _I, _I, _P, _F, _I, _P, _P]),
+    "moe_balance_step_ctx": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _P, _P]),
     "moe_route_scan": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "moe_permute_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "moe_combine_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
@@ -411,7 +413,9 @@ def router_num_blocks(T: int) -> int:
 def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias=None):
     """Returns (topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials).
     sel_bias fp32 [E]: the experts are selected by logits + sel_bias
-    (moe_router_topk_fwd_sel); None: moe_router_topk_fwd."""
+    (moe_router_topk_fwd_sel); fp32 [n_ctx, E], the shape of ctx_bias, which it
+    needs: by logits + sel_bias[the token's context] (moe_router_topk_fwd_selctx);
+    None: moe_router_topk_fwd."""
     T, d = x.shape
     E = wg.shape[0]
     _need(x, torch.bfloat16, "x")
@@ -427,7 +431,12 @@ def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, se
             raise MoEKernelError("ctx_img does not cover every token")
     if sel_bias is not None:
         _need(sel_bias, torch.float32, "sel_bias")
-        if tuple(sel_bias.shape) != (E,):
+        if sel_bias.dim() == 2:
+            if ctx_bias is None or ctx_img is None:
+                raise MoEKernelError("a [n_ctx, E] sel_bias needs ctx_bias and ctx_img")
+            if tuple(sel_bias.shape) != tuple(ctx_bias.shape):
+                raise MoEKernelError(f"sel_bias shape {tuple(sel_bias.shape)} != ctx_bias' {tuple(ctx_bias.shape)}")
+        elif tuple(sel_bias.shape) != (E,):
             raise MoEKernelError(f"sel_bias shape {tuple(sel_bias.shape)} != {(E,)}")
     dev = x.device
     nblk = router_num_blocks(T)
@@ -444,8 +453,10 @@ def router_topk_fwd(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, se
             _ptr(block_counts), _ptr(aux_partials), _stream())
     if sel_bias is None:
         _check(lib().moe_router_topk_fwd(*head, *outs), "moe_router_topk_fwd")
-    else:
+    elif sel_bias.dim() == 1:
         _check(lib().moe_router_topk_fwd_sel(*head, _ptr(sel_bias), *outs), "moe_router_topk_fwd_sel")
+    else:
+        _check(lib().moe_router_topk_fwd_selctx(*head, _ptr(sel_bias), *outs), "moe_router_topk_fwd_selctx")
     return topk_idx, topk_w, probs, lse, local_rank, block_counts, aux_partials
 
 
@@ -468,6 +479,29 @@ def balance_step(table, L, E, load, rate, apply, maxvio=None):
     rc = lib().moe_balance_step(_ptr(table) if L > 0 else None, int(L), int(E), _ptr(load), float(rate),
                                 int(bool(apply)), _ptr(maxvio), _stream())
     _check(rc, "moe_balance_step")
+
+
+def balance_step_ctx(table, L, C, E, k, load, rate, apply, maxvio=None):
+    """moe_balance_step_ctx, the per-context form of balance_step: load [L, C, E]
+    int64 += the per-context counts of each layer's top-k indices (``table``:
+    a uint8 device tensor of L records {topk_idx pointer or 0, bias pointer,
+    ctx_img pointer, T, tokens_per_image}, 32 B each; balance.py builds and
+    checks it); ``apply``: then the rule on every (layer, context) row in
+    place, maxvio fp32 [L, C] written and the load zeroed."""
+    _need(load, torch.int64, "load")
+    if tuple(load.shape) != (L, C, E):
+        raise MoEKernelError(f"balance_step_ctx: load shape {tuple(load.shape)} != {(L, C, E)}")
+    if L > 0:
+        _need(table, torch.uint8, "table")
+        if table.numel() < 32 * L:
+            raise MoEKernelError(f"balance_step_ctx: table holds {table.numel()} bytes, {L} layers need {32 * L}")
+    if maxvio is not None:
+        _need(maxvio, torch.float32, "maxvio")
+        if maxvio.numel() < L * C:
+            raise MoEKernelError(f"balance_step_ctx: maxvio holds {maxvio.numel()} values for {L * C} rows")
+    rc = lib().moe_balance_step_ctx(_ptr(table) if L > 0 else None, int(L), int(C), int(E), int(k), _ptr(load),
+                                    float(rate), int(bool(apply)), _ptr(maxvio), _stream())
+    _check(rc, "moe_balance_step_ctx")
 
 
 def route_scan(block_counts, cap):

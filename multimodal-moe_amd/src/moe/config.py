@@ -41,6 +41,12 @@ local architecture spec (no network fetch), e.g.::
                                   the token implies a MoE config.  Default: no bias (balance_rate 0)
     rtdetr-r50-moe8-top2-alb-lb0  the same without the auxiliary load-balance loss: -lb<c> sets lb_coef,
                                   c >= 0 (default 1e-2)
+    rtdetr-r50-moe8-top2-albc     the same rule with a bias per (context, expert): a token is ranked with the
+                                  row of its image's context, and a row moves by the load its context's tokens
+                                  put on the experts, so a batch that holds one context is flattened too.
+                                  The contexts then no longer differ in WHICH experts they select, only in the
+                                  gates.  -albc<u> sets the rate (-albc0.01), bare = 1e-3; needs the context
+                                  (-albc-noctx is refused).  Default: off (balance_per_context False)
 """
 from __future__ import annotations
 
@@ -84,6 +90,9 @@ class MoEConfig:
     # loss-free load balancing (balance.py): the selection bias' step per optimizer step; 0 = off (no
     # bias buffer, the plain router).  Spec token -alb[<u>]
     balance_rate: float = 0.0
+    # the selection bias is fp32 [num_contexts, E], indexed by the image's context and moved by that context's
+    # load, instead of [E].  Spec token -albc[<u>] (sets balance_rate too); needs use_context
+    balance_per_context: bool = False
 
     def capacity(self, tokens: int) -> int:
         if self.capacity_factor <= 0:
@@ -127,11 +136,12 @@ _SPEC_RE = re.compile(r"^rtdetr-(r18|r34|r50|r101)((?:-[a-z0-9.]+)*)$")
 
 
 def parse_moe_spec(spec: str) -> ModelSpec:
-    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]][-nbs<N>][-warm[<E>]][-lrf<f>][-cos][-alb[<u>]][-lb<c>]``
+    """Parse ``rtdetr-<backbone>[-moe<E>][-top<k>][-cf<f>][-fp8][-ep<n>][-epcf<f>][-dec<L>][-dn<N>][-ema[<d>]][-ematau<N>][-aug][-mosaic[<p>]][-nbs<N>][-warm[<E>]][-lrf<f>][-cos][-alb[<u>]][-albc[<u>]][-lb<c>]``
     (``-aug``: training batch augmentation, no value; ``-mosaic[<p>]``: four-image mosaic with
     probability p, default 1.0, implies ``-aug``; ``-nbs<N>``: nominal batch size for gradient
     accumulation; ``-warm[<E>]`` / ``-lrf<f>`` / ``-cos``: the learning-rate schedule;
     ``-alb[<u>]``: loss-free load balancing at rate u > 0, default 1e-3, implies a MoE config;
+    ``-albc[<u>]``: the same with a bias per (context, expert), not with ``-noctx``;
     ``-lb<c>``: the load-balance loss coefficient, c >= 0)."""
     s = spec.strip().lower()
     if s.endswith(".pt") or s.endswith(".pth"):
@@ -177,12 +187,14 @@ def parse_moe_spec(spec: str) -> ModelSpec:
                 raise ValueError(f"bad final learning-rate factor {tok[3:]!r} in model spec {spec!r}") from None
             if not 0.0 < out.lrf <= 1.0:
                 raise ValueError(f"final learning-rate factor outside (0, 1] in model spec {spec!r}")
-        elif tok.startswith("alb"):
+        elif tok.startswith("alb"):  # -albc[<u>] ahead of -alb[<u>]: the later token of the two decides the mode
             moe = moe or MoEConfig()
+            moe.balance_per_context = tok.startswith("albc")
+            val = tok[4:] if moe.balance_per_context else tok[3:]
             try:
-                moe.balance_rate = float(tok[3:]) if tok[3:] else 1e-3
+                moe.balance_rate = float(val) if val else 1e-3
             except ValueError:
-                raise ValueError(f"bad balance rate {tok[3:]!r} in model spec {spec!r}") from None
+                raise ValueError(f"bad balance rate {val!r} in model spec {spec!r}") from None
             if not (moe.balance_rate > 0.0 and math.isfinite(moe.balance_rate)):
                 raise ValueError(f"balance rate must be positive in model spec {spec!r}")
         elif tok.startswith("lb"):
@@ -239,5 +251,7 @@ def parse_moe_spec(spec: str) -> ModelSpec:
             raise ValueError("top_k must be <= num_experts")
         if moe.num_experts % moe.ep_size:
             raise ValueError("num_experts must be divisible by ep_size")
+        if moe.balance_per_context and not moe.use_context:
+            raise ValueError(f"-albc needs the image context, which -noctx removes, in model spec {spec!r}")
     out.moe = moe
     return out

@@ -18,7 +18,10 @@ def route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias=Non
     """sel_bias fp32 [E] (loss-free load balancing, balance.py): the k experts
     are chosen by key = logits + sel_bias -- one fp32 add after the context
     bias --; probs, lse and the gates still come from the unbiased logits, and
-    no gradient reaches the bias."""
+    no gradient reaches the bias.  sel_bias fp32 [C, E] (the per-context form,
+    an -albc spec; needs ctx_img): key = logits + sel_bias[ctx_img[t //
+    tokens_per_image]], the row of the token's image; everything else as with
+    [E]."""
     logits = x.float() @ wg.float().t()
     if ctx_bias is not None:
         logits = logits + ctx_bias.float()[ctx_img.long()].repeat_interleave(tokens_per_image, 0)
@@ -26,7 +29,12 @@ def route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias=Non
     lse = torch.logsumexp(logits, dim=-1)
     key = logits.detach()
     if sel_bias is not None:
-        key = key + sel_bias.detach().float()
+        sb = sel_bias.detach().float()
+        if sb.dim() == 2:
+            if ctx_img is None:
+                raise ValueError("route: a [C, E] selection bias needs ctx_img")
+            sb = sb[ctx_img.long()].repeat_interleave(tokens_per_image, 0)
+        key = key + sb
     # stable descending sort keeps the lower expert id first on ties
     order = torch.sort(key, dim=-1, descending=True, stable=True).indices
     idx = order[:, :k]
@@ -55,11 +63,14 @@ def dispatch_positions(idx, E, cap):
 
 
 def route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=None,
-                         sel_bias=None):
-    """-> (xp [rows, d], w [T, k], lb, z, pos [T, k], hist [E], offsets [E+1], rows)."""
+                         sel_bias=None, idx_sink=None):
+    """-> (xp [rows, d], w [T, k], lb, z, pos [T, k], hist [E], offsets [E+1], rows).
+    idx_sink: a list that receives the selected experts idx [T, k]."""
     T, d = x.shape
     E = wg.shape[0]
     probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, sel_bias)
+    if idx_sink is not None:
+        idx_sink.append(idx)
     pos, hist, offsets = dispatch_positions(idx, E, cap)
     if route_stats is not None:
         from .stats import record
@@ -161,14 +172,15 @@ def combine_eager(yp, w, pos, T):
 
 
 def moe_ffn_eager(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                  expert_dtype="bf16", route_stats=None, sel_bias=None):
+                  expert_dtype="bf16", route_stats=None, sel_bias=None, idx_sink=None):
     """route_stats = (table, context ids): add this forward's per-context
     routing statistics to the table (stats.route_stats_reference).
-    sel_bias: the layer's selection bias (route)."""
+    sel_bias: the layer's selection bias (route), [E] or [C, E]; idx_sink: a
+    list that receives the selected experts idx [T, k]."""
     T = x.shape[0]
     xp, w, lb, z, pos, hist, offsets, rows = route_dispatch_eager(x, wg, ctx_bias, ctx_img, tokens_per_image, k,
                                                                   normalize, cap, route_stats=route_stats,
-                                                                  sel_bias=sel_bias)
+                                                                  sel_bias=sel_bias, idx_sink=idx_sink)
     if expert_dtype == "fp8":
         yp = expert_ffn_mx_eager(xp, w1, b1, w2, b2, offsets)
     else:

@@ -277,12 +277,14 @@ def _padded_positions(idx, E, S):
     return pos, hist
 
 
-def _route_padded_eager(x, wg, ctx_bias, ctx_img, tpi, k, normalize, S, sel_bias=None):
+def _route_padded_eager(x, wg, ctx_bias, ctx_img, tpi, k, normalize, S, sel_bias=None, idx_sink=None):
     from .eager import route
 
     T, d = x.shape
     E = wg.shape[0]
     probs, lse, idx, w = route(x, wg, ctx_bias, ctx_img, tpi, k, normalize, sel_bias)
+    if idx_sink is not None:
+        idx_sink.append(idx)
     pos, hist = _padded_positions(idx, E, S)
     keep = pos >= 0
     t_idx = torch.arange(T, device=x.device).unsqueeze(1).expand(T, k)[keep]
@@ -315,6 +317,8 @@ def moe_ffn_ep(layer, x, ctx_bias, ctx_img, tokens_per_image, cap, residual=Fals
     # the layer's selection bias (balance.py), replicated: a rank routes its own tokens over all E
     # experts, so the ranks' hist sum to the global load
     sb = getattr(layer, "sel_bias", None)
+    # per-context balancing: the layer keeps this forward's topk_idx (MoEFFN.last_topk_idx)
+    sink = [] if (sb is not None and sb.dim() == 2) else None
     if x.is_cuda:
         from . import _lib as L
         from .ops import aux_loss_weighted, aux_losses_hip, combine_hip as combine
@@ -322,10 +326,12 @@ def moe_ffn_ep(layer, x, ctx_bias, ctx_img, tokens_per_image, cap, residual=Fals
 
         if fp8:
             carrier, w, auxp, pos, hist, _, xq, xs, _ = route_dispatch_mx_hip(
-                x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k, cfg.normalize, cap, pad=S, sel_bias=sb)
+                x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k, cfg.normalize, cap, pad=S, sel_bias=sb,
+                idx_sink=sink)
         else:
             xp, w, auxp, pos, hist, _, _ = route_dispatch_hip(x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k,
-                                                              cfg.normalize, cap, pad=S, sel_bias=sb)
+                                                              cfg.normalize, cap, pad=S, sel_bias=sb,
+                                                              idx_sink=sink)
         # lb and z from the single-GPU path's aux-loss kernel: one HIP launch each
         # way instead of ~20 torch ops (differentiable, or the weighted sum when
         # the caller passes its coefficients)
@@ -338,7 +344,9 @@ def moe_ffn_ep(layer, x, ctx_bias, ctx_img, tokens_per_image, cap, residual=Fals
         from .eager import combine_eager as combine, expert_ffn_eager, expert_ffn_mx_eager
 
         xp, w, lb, z, pos, hist = _route_padded_eager(x, layer.wg, ctx_bias, ctx_img, tokens_per_image, k,
-                                                      cfg.normalize, S, sel_bias=sb)
+                                                      cfg.normalize, S, sel_bias=sb, idx_sink=sink)
+    if sink is not None:
+        layer.last_topk_idx = sink[0].to(torch.int32)
     if _fused_ep_ok(layer, x, fp8):
         # counts exchange (int32; the compaction caps them at S), then the
         # receive map, the local expert offsets and this rank's overflow in ONE

@@ -51,11 +51,20 @@ class MoEFFN(nn.Module):
             p.expert_parallel = self.ep_size > 1  # excluded from the DP all-reduce
         # loss-free load balancing (cfg.balance_rate > 0, an -alb spec token; balance.py): a per-expert
         # bias added to the router logits for the top-k selection only.  No gradient; balance.LoadBalancer
-        # moves it once per optimizer step; replicated on every rank.  Off: no buffer, the plain router
-        if cfg.balance_rate > 0:
+        # moves it once per optimizer step; replicated on every rank.  Off: no buffer, the plain router.
+        # cfg.balance_per_context (an -albc token): the buffer is [C, E], a token is ranked with the row of its
+        # image's context, and the balancer counts this layer's topk_idx per context (last_topk_idx, last_ctx)
+        self.per_context = bool(cfg.balance_rate > 0 and cfg.balance_per_context)
+        if self.per_context and not cfg.use_context:
+            raise ValueError("MoEFFN: balance_per_context needs use_context")
+        if self.per_context:
+            self.register_buffer("sel_bias", torch.zeros(cfg.num_contexts, E, dtype=torch.float32))
+        elif cfg.balance_rate > 0:
             self.register_buffer("sel_bias", torch.zeros(E, dtype=torch.float32))
         else:
             self.sel_bias = None
+        self.last_topk_idx = None  # per-context balancing only: int32 [T, k] the last forward's selected experts
+        self.last_ctx = None       # ... and int32 [B] its images' context ids
         self.last_maxvio = None  # balancing: max load / mean load - 1 of the last optimizer step (fp32 scalar)
         self.last_aux = None   # (lb_raw, z_raw) of the last forward
         self.last_aux_weighted = None  # lb_coef lb + z_coef z (GPU path: fused kernel, differentiable)
@@ -82,6 +91,11 @@ class MoEFFN(nn.Module):
         ci = ctx_img.to(torch.int32).contiguous() if cb is not None else None
         # the statistics are per context whether or not the router has a context bias
         rs = (self.route_stats, ci if ci is not None else ctx_img) if self.route_stats is not None else None
+        sink = None
+        if self.per_context:
+            if ci is None:
+                raise ValueError("MoEFFN: a per-context selection bias needs ctx_img")
+            sink = []  # receives this forward's topk_idx from inside the routing op
         if self.ep_size > 1 or cfg.expert_parallel:  # C4: experts sharded over ranks, all-to-all exchange
             from .ep import moe_ffn_ep
 
@@ -91,6 +105,7 @@ class MoEFFN(nn.Module):
                 self.last_aux = (lb, z)
                 self.last_aux_weighted = self.ep_aux_weighted
                 self.last_hist = hist
+                self.last_ctx = ci if self.per_context else None
                 return y.to(x.dtype).view(B, L, d)
         elif flat.is_cuda:
             from .ops import moe_ffn_hip
@@ -98,23 +113,28 @@ class MoEFFN(nn.Module):
             y, aux, raw, hist = moe_ffn_hip(flat, self.wg, cb, self.w1, self.b1, self.w2, self.b2,
                                             ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype,
                                             aux_coefs=(cfg.lb_coef, cfg.z_coef), residual=residual, route_stats=rs,
-                                            sel_bias=self.sel_bias)
+                                            sel_bias=self.sel_bias, idx_sink=sink)
             self.last_aux = (raw[0], raw[1])
             self.last_aux_weighted = aux
             self.last_hist = hist
+            if sink is not None:
+                self.last_topk_idx, self.last_ctx = sink[0], ci
             return y.to(x.dtype).view(B, L, d)
         else:
             from .eager import moe_ffn_eager
 
             y, lb, z, hist = moe_ffn_eager(flat, self.wg, cb, self.w1, self.b1, self.w2, self.b2,
                                            ci, L, cfg.top_k, cfg.normalize, cap, cfg.expert_dtype, route_stats=rs,
-                                           sel_bias=self.sel_bias)
+                                           sel_bias=self.sel_bias, idx_sink=sink)
+            if sink is not None:
+                self.last_topk_idx = sink[0].to(torch.int32)
         y = y.to(x.dtype)
         if residual:
             y = flat + y
         self.last_aux = (lb, z)
         self.last_aux_weighted = getattr(self, "ep_aux_weighted", None)
         self.last_hist = hist
+        self.last_ctx = ci if self.per_context else None
         return y.view(B, L, d)
 
     def aux_loss(self) -> torch.Tensor | None:

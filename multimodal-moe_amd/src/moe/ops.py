@@ -99,13 +99,23 @@ def _sel(sel_bias):
     return None if sel_bias is None else sel_bias.detach().float().contiguous()
 
 
+def _keep_idx(idx_sink, idx):
+    """Per-context balancing (balance.py): hand the router's topk_idx [T, k] to
+    the layer through ``idx_sink``, a list, from inside the forward -- in a
+    captured step the layer's reference is what keeps the graph's pool from
+    reusing the memory before LoadBalancer.add() reads it after the replay."""
+    if idx_sink is not None:
+        idx_sink.append(idx)
+
+
 class _RouteDispatch(torch.autograd.Function):
     """Router + scan + permute (rows copied).  ``pad`` > 0: the fixed-capacity
     layout of the expert-parallel send buffer -- expert e's kept rows at
     [e pad, e pad + min(hist_e, pad)), assignments ranked >= pad dropped."""
 
     @staticmethod
-    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, sel_bias=None):
+    def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, sel_bias=None,
+                idx_sink=None):
         T, d = x.shape
         E = wg.shape[0]
         xb = x.to(torch.bfloat16).contiguous()
@@ -113,6 +123,7 @@ class _RouteDispatch(torch.autograd.Function):
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tokens_per_image, k,
                                                                    normalize, _sel(sel_bias))
+        _keep_idx(idx_sink, idx)
         rank_base, hist, offsets = L.route_scan(bcnt, cap)
         if pad:
             offsets, cap = _padded_offsets(E, pad, x.device), pad
@@ -145,7 +156,7 @@ class _RouteDispatch(torch.autograd.Function):
         dx, dlogits = L.token_bwd(d_xp, pos_use, probs, idx, w, d_w, lse, dprob_bias, zc, wg32, normalize)
         # router weight + context-bias gradients: one HIP launch, fixed-order sums
         dwg, dcb = L.router_wgrad(dlogits, xb, ctx_img if has_ctx else None, tpi, C if has_ctx else 0)
-        return dx.to(xdtype), dwg, dcb, None, None, None, None, None, None, None, None
+        return dx.to(xdtype), dwg, dcb, None, None, None, None, None, None, None, None, None
 
 
 class _RouteDispatchMX(torch.autograd.Function):
@@ -156,7 +167,7 @@ class _RouteDispatchMX(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, rows, pad=0, stats=None,
-                sel_bias=None):
+                sel_bias=None, idx_sink=None):
         T, d = x.shape
         E = wg.shape[0]
         xb = x.to(torch.bfloat16).contiguous()
@@ -164,6 +175,7 @@ class _RouteDispatchMX(torch.autograd.Function):
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tokens_per_image, k,
                                                                    normalize, _sel(sel_bias))
+        _keep_idx(idx_sink, idx)
         rank_base, hist, offsets = L.route_scan(bcnt, cap)
         if pad:
             offsets, cap = _padded_offsets(E, pad, x.device), pad
@@ -426,27 +438,29 @@ def aux_losses(auxp, hist, T, k):
     return lb, z
 
 
-def route_dispatch_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, sel_bias=None):
+def route_dispatch_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, sel_bias=None,
+                       idx_sink=None):
     """-> (xp, w, auxp, pos, hist, offsets, rows); pad > 0: fixed-capacity
     layout (rows = E pad, offsets = e pad; see _RouteDispatch).  sel_bias fp32
-    [E]: the experts are selected by logits + sel_bias (no gradient)."""
+    [E] or [n_ctx, E]: the experts are selected by logits + sel_bias (no
+    gradient).  idx_sink: a list that receives topk_idx (_keep_idx)."""
     T = x.shape[0]
     E = wg.shape[0]
     rows = E * pad if pad else (T * k if cap <= 0 else min(T * k, E * cap))
     return _RouteDispatch.apply(x, wg, ctx_bias, ctx_img, int(tokens_per_image), int(k), bool(normalize), int(cap),
-                                rows, int(pad), sel_bias) + (rows,)
+                                rows, int(pad), sel_bias, idx_sink) + (rows,)
 
 
 def route_dispatch_mx_hip(x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, pad=0, route_stats=None,
-                          sel_bias=None):
+                          sel_bias=None, idx_sink=None):
     """-> (carrier, w, auxp, pos, hist, offsets, xq, xs, rows): MXFP8 dispatch.
     route_stats = (table, context ids): add this forward's routing statistics.
-    sel_bias: as route_dispatch_hip."""
+    sel_bias, idx_sink: as route_dispatch_hip."""
     T = x.shape[0]
     E = wg.shape[0]
     rows = E * pad if pad else (T * k if cap <= 0 else min(T * k, E * cap))
     return _RouteDispatchMX.apply(x, wg, ctx_bias, ctx_img, int(tokens_per_image), int(k), bool(normalize),
-                                  int(cap), rows, int(pad), route_stats, sel_bias) + (rows,)
+                                  int(cap), rows, int(pad), route_stats, sel_bias, idx_sink) + (rows,)
 
 
 # MOE_FUSE_RESIDUAL=0: the residual add stays a torch add (A/B switch)
@@ -476,7 +490,7 @@ class _MoELayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tpi, k, normalize, cap, lb_coef, z_coef, weighted,
-                residual=False, stats=None, sel_bias=None):
+                residual=False, stats=None, sel_bias=None, idx_sink=None):
         T, d = x.shape
         E = wg.shape[0]
         G, F, _ = w1.shape
@@ -486,6 +500,7 @@ class _MoELayer(torch.autograd.Function):
         cb = ctx_bias.float().contiguous() if ctx_bias is not None else None
         idx, w, probs, lse, lrank, bcnt, auxp = L.router_topk_fwd(xb, wg32, cb, ctx_img, tpi, k, normalize,
                                                                    _sel(sel_bias))
+        _keep_idx(idx_sink, idx)
         pos, tok, hist, offsets, gate, out3, wcoef = L.route_dispatch(bcnt, idx, lrank, w, auxp, T, E, cap, rows,
                                                                       lb_coef, z_coef, row_gate=True)
         if stats is not None:  # (table, context ids): the layer's routing statistics sink (stats.py)
@@ -545,22 +560,23 @@ class _MoELayer(torch.autograd.Function):
                                         dres=dyb if ctx.residual else None)
         # router weight + context-bias gradients: one HIP launch, fixed-order sums
         dwg, dcb = L.router_wgrad(dlogits, xb, ctx_img if has_ctx else None, tpi, C if has_ctx else 0)
-        return (dx.to(xdtype), dwg, dcb, dW1, db1, dW2, db2) + (None,) * 11
+        return (dx.to(xdtype), dwg, dcb, dW1, db1, dW2, db2) + (None,) * 12
 
 
 def moe_layer_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap, aux_coefs=None,
-                  residual=False, route_stats=None, sel_bias=None):
+                  residual=False, route_stats=None, sel_bias=None, idx_sink=None):
     """_MoELayer: -> (y, lb_coef lb + z_coef z, raw (lb, z), hist) with aux_coefs,
     else (y, lb, z, hist); residual=True returns x + y (fused for bf16 x).
-    sel_bias fp32 [E]: the experts are selected by logits + sel_bias (no gradient)."""
+    sel_bias fp32 [E] or [n_ctx, E]: the experts are selected by logits + sel_bias (no gradient);
+    idx_sink: a list that receives topk_idx (_keep_idx)."""
     fuse = bool(residual) and x.dtype == torch.bfloat16 and _FUSE_RESIDUAL
     if aux_coefs is not None:
         out = _MoELayer.apply(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, int(tokens_per_image), int(k),
                               bool(normalize), int(cap), float(aux_coefs[0]), float(aux_coefs[1]), True, fuse,
-                              route_stats, sel_bias)
+                              route_stats, sel_bias, idx_sink)
     else:
         out = _MoELayer.apply(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, int(tokens_per_image), int(k),
-                              bool(normalize), int(cap), 1.0, 1.0, False, fuse, route_stats, sel_bias)
+                              bool(normalize), int(cap), 1.0, 1.0, False, fuse, route_stats, sel_bias, idx_sink)
     if residual and not fuse:  # fp32 activations (amp): keep the residual add in x's precision
         out = (x + out[0],) + tuple(out[1:])
     return out
@@ -615,7 +631,7 @@ def combine_hip(yp, w, pos, T, resid=None):
 
 
 def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                expert_dtype="bf16", aux_coefs=None, residual=False, route_stats=None, sel_bias=None):
+                expert_dtype="bf16", aux_coefs=None, residual=False, route_stats=None, sel_bias=None, idx_sink=None):
     """Routed expert FFN of one layer on the GPU.
 
     x [T, d] (tokens of ``T // tokens_per_image`` images, image-major),
@@ -633,7 +649,10 @@ def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, n
     sel_bias fp32 [E] (loss-free load balancing, balance.py): the router picks
     the k experts with the largest logits + sel_bias (moe_router_topk_fwd_sel);
     gates, aux losses and every gradient are those of the unbiased logits, and
-    the bias itself gets none.  None: the plain router.
+    the bias itself gets none.  fp32 [n_ctx, E] (an -albc spec; needs ctx_bias
+    and ctx_img): the row of the token's context (moe_router_topk_fwd_selctx).
+    None: the plain router.  idx_sink: a list that receives the router's
+    topk_idx int32 [T, k] (_keep_idx; per-context balancing counts it).
     """
     if not x.is_cuda:
         raise L.MoEKernelError("moe_ffn_hip needs GPU tensors")
@@ -645,11 +664,12 @@ def moe_ffn_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, n
     if expert_dtype == "fp8":
         carrier, w, auxp, pos, hist, offsets, xq, xs, rows = route_dispatch_mx_hip(
             x, wg, ctx_bias, ctx_img, tokens_per_image, k, normalize, cap, route_stats=route_stats,
-            sel_bias=sel_bias)
+            sel_bias=sel_bias, idx_sink=idx_sink)
         yp = expert_ffn_mx_hip(carrier, xq, xs, w1, b1, w2, b2, offsets, rows)
     else:
         return moe_layer_hip(x, wg, ctx_bias, w1, b1, w2, b2, ctx_img, tokens_per_image, k, normalize, cap,
-                             aux_coefs, residual=residual, route_stats=route_stats, sel_bias=sel_bias)
+                             aux_coefs, residual=residual, route_stats=route_stats, sel_bias=sel_bias,
+                             idx_sink=idx_sink)
     y = combine_hip(yp, w, pos, T)
     if residual:
         y = x + y.to(x.dtype)

@@ -118,6 +118,18 @@ int main() {
   expect_error("balance_step L=-1", moe_balance_step(buf, -1, 8, i64, 1e-3f, 1, f32, s));
   expect_error("balance_step table=NULL", moe_balance_step(nullptr, 2, 8, i64, 1e-3f, 1, f32, s));
   expect_error("balance_step load=NULL", moe_balance_step(buf, 2, 8, nullptr, 1e-3f, 1, f32, s));
+  expect_error("router_topk_fwd_selctx ctx=NULL", moe_router_topk_fwd_selctx(p, f32, nullptr, nullptr, 0, 16, 16, 256, 8, 2,
+                                                                             1, f32, i32, f32, f32, f32, i32, i32, f32, s));
+  expect_error("router_topk_fwd_selctx sel=NULL", moe_router_topk_fwd_selctx(p, f32, f32, i32, 6, 16, 16, 256, 8, 2, 1,
+                                                                             nullptr, i32, f32, f32, f32, i32, i32, f32, s));
+  expect_error("router_topk_fwd_selctx LDS", moe_router_topk_fwd_selctx(p, f32, f32, i32, 64, 16, 16, 256, 64, 2, 1, f32,
+                                                                        i32, f32, f32, f32, i32, i32, f32, s));
+  expect_error("balance_step_ctx E=65", moe_balance_step_ctx(buf, 2, 6, 65, 2, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step_ctx k>E", moe_balance_step_ctx(buf, 2, 6, 2, 3, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step_ctx C=0", moe_balance_step_ctx(buf, 2, 0, 8, 2, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step_ctx L=-1", moe_balance_step_ctx(buf, -1, 6, 8, 2, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step_ctx table=NULL", moe_balance_step_ctx(nullptr, 2, 6, 8, 2, i64, 1e-3f, 1, f32, s));
+  expect_error("balance_step_ctx load=NULL", moe_balance_step_ctx(buf, 2, 6, 8, 2, nullptr, 1e-3f, 1, f32, s));
   expect_error("resize_pad src=NULL", rtdetr_resize_pad_u8(nullptr, i64, 1, 32, 32, 32, 32, f32, s));
   expect_error("resize_pad desc=NULL", rtdetr_resize_pad_u8(u8, nullptr, 1, 32, 32, 32, 32, f32, s));
   expect_error("resize_pad dst=NULL", rtdetr_resize_pad_u8(u8, i64, 1, 32, 32, 32, 32, nullptr, s));
