@@ -1412,7 +1412,12 @@ int rtdetr_conv1x1_block_out(const void* h2, const void* w2c, const void* resid,
  * "conv_bm" forward pixel-tile rows 64 / 128 / 256; "conv_wg_stages"
  * weight-gradient LDS ring depth 2..4; "conv_wg_splits" weight-gradient pixel
  * slices returned by rtdetr_conv_wgrad_splits; "conv_dgrad_flip" 1 = always
- * write the flipped weight, 0 = always read it in place. */
+ * write the flipped weight, 0 = always read it in place.  "conv_wg_reduce"
+ * (default 1): the weight gradient's slice sums with the threads along the row
+ * and every load of a round in flight, 0 = 16 columns x 16 slice groups per
+ * workgroup; "conv_wg_stage" (default 1): the fp32 slice tiles leave through
+ * LDS as whole rows, 0 = stored from the accumulator fragments.  Both pairs are
+ * bitwise the same results (tests/test_gpu_wgrad_slices.py). */
 int rtdetr_conv_set_tuning(const char* key, int value);
 
 /* Training-step optimizer (the bench step's AdamW; reference: Ultralytics'

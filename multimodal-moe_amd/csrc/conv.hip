@@ -63,6 +63,11 @@ static int g_conv_halo = -1;       // "conv_halo": 3x3 stride-1 forward / data g
                                    // -1 = automatic
 static int g_conv_8ph = -1;        // "conv_8ph": the 256 x 256 eight-phase kernel (conv_8ph_kernel): 0 never,
                                    // 1 wherever it applies, -1 automatic (3x3, >= 256 tiles)
+static int g_conv_wg_reduce = 1;   // "conv_wg_reduce": weight-gradient slice sums, 0 = 16 columns x 16 thread groups
+                                   // per workgroup (wgrad_reduce_body), 1 = threads along the row, 16 / GT groups
+                                   // in a thread (wgrad_reduce_wide); bitwise the same sums
+static int g_conv_wg_stage = 1;    // "conv_wg_stage": weight-gradient partial tile, 0 = stored from the accumulator
+                                   // fragments (64-B pieces), 1 = staged through the ring's LDS, whole rows
 static int g_conv_k32 = -1;        // "conv_k32": 1-3 = forward / data-gradient 32-deep K-tiles, ring depth 2-4;
                                    // 0 = never; -1 = automatic (k32_auto)
 
@@ -1098,7 +1103,19 @@ struct ConvWgArgs {
   int B, H, W, C, N, P;
   int nsplit, kt_per;    // pixel K-tiles per slice
   int Ho, Wo, st;        // output pixels (dY) and the stride: x neighbour (st y + dy, st x + dx)
+  int stage;             // 1 = the partial tile leaves through LDS as whole rows ("conv_wg_stage")
 };
+
+// XOR mask on the 16-B chunk index of row r of the staged fp32 partial tile
+// (rows of 256 or 512 B, unpadded).  The accumulator stores (ds_write_b128:
+// 8 consecutive lanes per LDS cycle, 32 banks) put the same chunk of 8
+// consecutive rows into one cycle: the low three bits of the mask differ for
+// r = 0..7, so the 8 chunks fall into 8 different 16-B bank groups instead of
+// one.  The row reads (ds_read_b128: 16 lanes per cycle, 64 banks) take the
+// chunk sets {0-3, 12-15} and {4-11} of one or two rows per cycle; the mask
+// flips chunk bits 2 and 3 together, which maps each set onto itself, so a
+// cycle's 16 chunks stay 16 different ones mod 16.
+__device__ __forceinline__ int wg_stage_swz(int r) { return (r & 3) | ((r & 4) ? 12 : 0); }
 
 // Tile WBM (output channels) x WBN (tap-major input channels of one tap):
 // 128 x 128, or 64 on a side with 64 channels (ResNet stage 1).
@@ -1204,6 +1221,40 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvWgArgs a) {
   }
   // lane holds dW[m0 + wm WBM/2 + 16 i + (lane & 15)][nn0 + wn WBN/2 + 16 j + 4 (lane >> 4) + 0..3]
   float* out = a.part + (size_t)split * a.N * NN;
+  if (a.stage) {
+    // "conv_wg_stage": the tile goes through the (now idle) ring and leaves as
+    // whole rows, WBN x 4 contiguous bytes at 16 B per lane, instead of 16
+    // 64-B fragments per instruction.  The fp32 tile fills a 2-deep ring
+    // exactly (no room for row padding), so the 16-B chunk c of row r sits at
+    // chunk c ^ wg_stage_swz(r): see wg_stage_swz.
+    constexpr int CH = WBN / 4;  // 16-B chunks per tile row
+    static_assert(WBM * WBN * 4 <= S * TILE, "the fp32 tile must fit the ring");
+    float4* t = reinterpret_cast<float4*>(smem);
+    __syncthreads();  // every wave has read its last K-tile
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int r = wm * (WBM / 2) + 16 * i + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int c = wn * (WBN / 8) + 4 * j + (lane >> 4);
+        t[r * CH + (c ^ wg_stage_swz(r))] = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+      }
+    }
+    __syncthreads();
+    constexpr int PASSES = WBM * CH / 256;
+    float4 v[PASSES];
+#pragma unroll
+    for (int q = 0; q < PASSES; ++q) {
+      const int u16 = q * 256 + tid, r = u16 / CH, c = u16 % CH;
+      v[q] = t[r * CH + (c ^ wg_stage_swz(r))];
+    }
+#pragma unroll
+    for (int q = 0; q < PASSES; ++q) {
+      const int u16 = q * 256 + tid, r = u16 / CH, c = u16 % CH;
+      *reinterpret_cast<float4*>(out + (size_t)(m0 + r) * NN + nn0 + 4 * c) = v[q];
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int m = m0 + wm * (WBM / 2) + 16 * i + (lane & 15);
@@ -1261,6 +1312,145 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __r
   wgrad_reduce_body(part, nsplit, n, dw, out_bf16, blockIdx.x, red);
 }
 
+// "conv_wg_reduce" 1: the same sums with the threads laid along the row.
+// wgrad_reduce_body's sixteen groups are kept, s[g] = the slices k = g, g + 16,
+// ... in increasing k from +0.0f, then s[0] + s[1] + ... + s[15] left to
+// right, a group without a slice adding its +0.0f: the arithmetic above,
+// element by element.  What changes is who holds them.  The 256 threads are
+// GT group-threads x 256 / GT float4 columns (a wave reads 1 KiB contiguous of
+// a slice row); a thread keeps the 16 / GT groups gb .. gb + 16 / GT - 1 of its
+// column in registers, issues the loads of a round of 16 slices before that
+// round's adds (GT = 4: of two rounds).
+//   up to 32 slices  GT = 1: all 16 groups in the thread, no LDS, no barrier.
+//                    Most weights are here (3, 8, 14 slices), so with <= 8
+//                    (<= 4) slices a thread takes NC = 2 (4) columns, 256
+//                    apart, to keep as many loads in flight; the 16 / NC
+//                    groups that can hold a slice are summed, the others are
+//                    the literal +0.0f.
+//   more slices      GT = 4 (a wave per 4 groups, 64 columns): few columns per
+//                    slice there (1-2 output tiles), so the slices are shared
+//                    out; the group sums meet in LDS and group-thread 0 adds
+//                    the sixteen in order.
+struct WgRedLayout {
+  int gt, nc;
+};
+__host__ __device__ inline WgRedLayout wg_red_layout(int nsplit) {
+  return nsplit <= 4 ? WgRedLayout{1, 4} : nsplit <= 8 ? WgRedLayout{1, 2} : nsplit <= 32 ? WgRedLayout{1, 1}
+                                                                                          : WgRedLayout{4, 1};
+}
+// blocks of one weight's reduction
+static long long wg_red_blocks(long long n, int nsplit, bool wide) {
+  const WgRedLayout l = wg_red_layout(nsplit);
+  const long long cols = wide ? 256 / l.gt * l.nc : 16;
+  return (n / 4 + cols - 1) / cols;
+}
+constexpr int kWgRedLds = 16 * 64;  // float4: GT = 4's 16 groups x 64 columns
+
+template <int GT, int NC>
+__device__ __forceinline__ void wgrad_reduce_wide(const float* __restrict__ part, int nsplit, long long n,
+                                                  void* __restrict__ dw, int out_bf16, long long blk, float4* red) {
+  static_assert(GT == 1 || NC == 1, "several columns per thread only without group-threads");
+  constexpr int CW = 256 / GT;       // columns of a block (per NC)
+  constexpr int GP = 16 / GT;        // groups of a thread
+  constexpr int G = GP / NC;         // of them, those that can hold a slice: nsplit <= G when NC > 1
+  // (gb is wave-uniform, in a scalar register: the slice bounds below are scalar branches)
+  const int col = threadIdx.x % CW, gb = GT > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x / CW) * GP : 0;
+  // element i[c] = i0 + lo[c]: a block-uniform base (scalar address arithmetic) and a small lane offset.
+  // A lane past the row's end reads the row's last float4 instead (no branch around a load) and stores nothing.
+  const long long i0 = blk * (NC * CW) * 4;
+  const char* __restrict__ base = reinterpret_cast<const char*>(part + i0);
+  unsigned lo[NC];  // bytes
+  long long i[NC];
+  float4 s[G][NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    i[c] = i0 + (c * CW + col) * 4;
+    lo[c] = 4u * (i[c] < n ? (unsigned)(c * CW + col) * 4 : (unsigned)(n - 4 - i0));
+#pragma unroll
+    for (int g = 0; g < G; ++g) s[g][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  auto add = [&](float4& acc, const float4& v) {
+    acc.x += v.x;
+    acc.y += v.y;
+    acc.z += v.z;
+    acc.w += v.w;
+  };
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  int k0 = 0;
+  if constexpr (NC == 1) {
+    constexpr int R = GT > 1 ? 2 : 1;  // whole rounds at a time: R GP loads, then their adds in slice order
+    for (; k0 + 16 * R <= nsplit; k0 += 16 * R) {
+      float4 v[R][G];
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+          v[r][g] = *reinterpret_cast<const float4*>(base + (size_t)(k0 + 16 * r + gb + g) * n * 4 + lo[0]);
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) add(s[g][0], v[r][g]);
+    }
+  }
+  for (; k0 < nsplit; k0 += 16) {
+    float4 v[G][NC];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+      if (k0 + gb + g < nsplit) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          v[g][c] = *reinterpret_cast<const float4*>(base + (size_t)(k0 + gb + g) * n * 4 + lo[c]);
+      }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+      if (k0 + gb + g < nsplit) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) add(s[g][c], v[g][c]);
+      }
+  }
+  if constexpr (GT > 1) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) red[(gb + g) * CW + col] = s[g][0];
+    __syncthreads();
+    if (gb) return;
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    if (i[c] >= n) continue;
+    float4 t = s[0][c];
+#pragma unroll
+    for (int g = 1; g < 16; ++g) {
+      if constexpr (GT > 1) add(t, g < G ? s[g][c] : red[g * CW + col]);
+      else add(t, g < G ? s[g][c] : zero4);
+    }
+    if (out_bf16) {
+      uint2 o;
+      o.x = pack2bf(t.x, t.y);
+      o.y = pack2bf(t.z, t.w);
+      *reinterpret_cast<uint2*>(static_cast<uint16_t*>(dw) + i[c]) = o;
+    } else {
+      *reinterpret_cast<float4*>(static_cast<float*>(dw) + i[c]) = t;
+    }
+  }
+}
+
+__device__ __forceinline__ void wgrad_reduce_wide_body(const float* __restrict__ part, int nsplit, long long n,
+                                                       void* __restrict__ dw, int out_bf16, long long blk,
+                                                       float4* red) {
+  const WgRedLayout l = wg_red_layout(nsplit);
+  if (l.gt == 4) wgrad_reduce_wide<4, 1>(part, nsplit, n, dw, out_bf16, blk, red);
+  else if (l.nc == 4) wgrad_reduce_wide<1, 4>(part, nsplit, n, dw, out_bf16, blk, red);
+  else if (l.nc == 2) wgrad_reduce_wide<1, 2>(part, nsplit, n, dw, out_bf16, blk, red);
+  else wgrad_reduce_wide<1, 1>(part, nsplit, n, dw, out_bf16, blk, red);
+}
+
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_wide_kernel(const float* __restrict__ part, int nsplit,
+                                                                     long long n, void* __restrict__ dw,
+                                                                     int out_bf16) {
+  __shared__ float4 red[kWgRedLds];
+  wgrad_reduce_wide_body(part, nsplit, n, dw, out_bf16, blockIdx.x, red);
+}
+
 // The slice sums of up to kWgRedBatch weight gradients in ONE launch (round 6:
 // the training step defers every convolution's reduction to the end of the
 // backward, src/rtdetr_moe/conv.py deferred_wgrads): descriptor q owns blocks
@@ -1287,6 +1477,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_batch_kernel(WgRedBatch
     else hi = mid - 1;
   }
   wgrad_reduce_body(b.part[lo], b.nsplit[lo], b.n[lo], b.dw[lo], b.out_bf16, bid - b.base[lo], red);
+}
+
+// the same with conv_wgrad_reduce_wide_kernel's body (base[] counts its blocks)
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_batch_wide_kernel(WgRedBatch b) {
+  __shared__ float4 red[kWgRedLds];
+  const int bid = blockIdx.x;
+  int lo = 0, hi = b.count - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (b.base[mid] <= bid) lo = mid;
+    else hi = mid - 1;
+  }
+  wgrad_reduce_wide_body(b.part[lo], b.nsplit[lo], b.n[lo], b.dw[lo], b.out_bf16, bid - b.base[lo], red);
 }
 
 // ---------------------------------------------------------------------------
@@ -2320,6 +2523,7 @@ extern "C" int rtdetr_conv_wgrad_part(const void* dy, const void* x, float* part
   a.kt_per = (ktot + nsplit - 1) / nsplit;
   const long long nw = (long long)N * KS * KS * C;
   const double P = a.P;
+  a.stage = g_conv_wg_stage != 0;
   ProfScope prof(stream, PROF_CONV, 2.0 * ((double)B * H * W * C + P * N) + 4.0 * nsplit * nw, false, 0.0,
                  2.0 * P * nw);
   if (KS == 3) launch_wgrad<3>(a, stream, prof);
@@ -2334,8 +2538,12 @@ extern "C" int rtdetr_conv_wgrad(const void* dy, const void* x, float* part, int
   if (int rc = rtdetr_conv_wgrad_part(dy, x, part, nsplit, zero, B, H, W, C, N, KS, stride, stream)) return rc;
   const long long nw = (long long)N * KS * KS * C;
   ProfScope prof(stream, PROF_CONV, 4.0 * nsplit * nw + (out_bf16 ? 2.0 : 4.0) * nw);
-  MOE_LAUNCH(prof, conv_wgrad_reduce_kernel, dim3((unsigned)((nw / 4 + 15) / 16)), dim3(256), 0, stream, part,
-             nsplit, nw, dw, out_bf16);
+  const bool wide = g_conv_wg_reduce != 0;
+  const dim3 grid((unsigned)wg_red_blocks(nw, nsplit, wide));
+  if (wide)
+    MOE_LAUNCH(prof, conv_wgrad_reduce_wide_kernel, grid, dim3(256), 0, stream, part, nsplit, nw, dw, out_bf16);
+  else
+    MOE_LAUNCH(prof, conv_wgrad_reduce_kernel, grid, dim3(256), 0, stream, part, nsplit, nw, dw, out_bf16);
   return check_launch("rtdetr_conv_wgrad (reduce)");
 }
 
@@ -2344,6 +2552,7 @@ extern "C" int rtdetr_conv_wgrad_reduce_batch(int n, const float* const* parts, 
                                               hipStream_t stream) {
   if (n < 1 || n > kWgRedBatch || parts == nullptr || nsplits == nullptr || nws == nullptr || dws == nullptr)
     return fail("rtdetr_conv_wgrad_reduce_batch: 1..48 weights, non-NULL arrays");
+  const bool wide = g_conv_wg_reduce != 0;
   WgRedBatch b{};
   b.count = n;
   b.out_bf16 = out_bf16 ? 1 : 0;
@@ -2358,13 +2567,16 @@ extern "C" int rtdetr_conv_wgrad_reduce_batch(int n, const float* const* parts, 
     b.n[q] = nws[q];
     b.nsplit[q] = nsplits[q];
     b.base[q] = (int)blocks;
-    blocks += (nws[q] / 4 + 15) / 16;
+    blocks += wg_red_blocks(nws[q], nsplits[q], wide);
     bytes += 4.0 * nsplits[q] * nws[q] + (out_bf16 ? 2.0 : 4.0) * nws[q];
   }
   if (blocks > 0x7fffffffLL) return fail("rtdetr_conv_wgrad_reduce_batch: too many blocks");
   b.base[n] = (int)blocks;
   ProfScope prof(stream, PROF_CONV, bytes);
-  MOE_LAUNCH(prof, conv_wgrad_reduce_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b);
+  if (wide)
+    MOE_LAUNCH(prof, conv_wgrad_reduce_batch_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b);
+  else
+    MOE_LAUNCH(prof, conv_wgrad_reduce_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b);
   return check_launch("rtdetr_conv_wgrad_reduce_batch");
 }
 
@@ -2493,6 +2705,14 @@ extern "C" int rtdetr_conv_set_tuning(const char* key, int value) {
   }
   if (std::string(key) == "conv_wg_stages") {
     g_conv_wg_stages = value;
+    return 0;
+  }
+  if (std::string(key) == "conv_wg_reduce") {
+    g_conv_wg_reduce = value;
+    return 0;
+  }
+  if (std::string(key) == "conv_wg_stage") {
+    g_conv_wg_stage = value;
     return 0;
   }
   if (std::string(key) == "conv_wg_splits") {

@@ -3,6 +3,11 @@ bench's find-db and benchmark mode) against the HIP implicit-GEMM kernels
 (csrc/conv.hip), forward, data gradient and weight gradient separately.
 
     python tools/conv_bench.py > gpurun_out/conv_bench.jsonl
+
+``--wgrad``: only the HIP weight gradient, its two launches timed apart (the
+pixel-slice partials, rtdetr_conv_wgrad_part, and their sum, a
+rtdetr_conv_wgrad_reduce_batch of one) with "conv_wg_stage" / "conv_wg_reduce"
+0 and 1 in turn, and the bytes each moves.
 """
 from __future__ import annotations
 
@@ -57,6 +62,40 @@ def timeit(fn, reps=20):
     return a.elapsed_time(b) * 1e3 / reps  # us
 
 
+def wgrad_ab(L, C, shape, x, gy, w):
+    """us of the weight gradient's two launches with their A/B keys 0 and 1 (two rounds each, interleaved)."""
+    import ctypes
+
+    B, Ci, Co, H, W, ks = shape[:6]
+    st = shape[6] if len(shape) > 6 else 1
+    lib, z = L.lib(), C._zero(x.device).data_ptr()
+    ns = lib.rtdetr_conv_wgrad_splits(B, gy.shape[2], gy.shape[3], Ci, Co, ks)
+    nw = Co * Ci * ks * ks
+    part = torch.empty(ns * nw, dtype=torch.float32, device=x.device)
+    gw = torch.empty_like(w)
+    cv = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    desc = [cv((ctypes.c_void_p * 1)(part.data_ptr())), cv((ctypes.c_int * 1)(ns)), cv((ctypes.c_longlong * 1)(nw)),
+            cv((ctypes.c_void_p * 1)(gw.data_ptr()))]
+    t_part = lambda: lib.rtdetr_conv_wgrad_part(gy.data_ptr(), x.data_ptr(), part.data_ptr(), ns, z, B, H, W, Ci, Co,  # noqa: E731
+                                                ks, st, L._stream())
+    t_red = lambda: lib.rtdetr_conv_wgrad_reduce_batch(1, *desc, 1, L._stream())  # noqa: E731
+    us = {"part": [[], []], "reduce": [[], []]}
+    for _ in range(2):
+        for v in (0, 1):
+            L.set_tuning("conv_wg_stage", v)
+            L.set_tuning("conv_wg_reduce", v)
+            us["part"][v].append(round(timeit(t_part), 1))
+            us["reduce"][v].append(round(timeit(t_red), 1))
+    red_mb = (4.0 * ns * nw + 2.0 * nw) / 1e6
+    part_mb = (2.0 * (x.numel() + gy.numel()) + 4.0 * ns * nw) / 1e6
+    best = lambda a: min(a)  # noqa: E731
+    return {"shape": list(shape), "wgrad_splits": ns, "part_us_key0": us["part"][0], "part_us_key1": us["part"][1],
+            "reduce_us_key0": us["reduce"][0], "reduce_us_key1": us["reduce"][1], "part_mb": round(part_mb, 1),
+            "reduce_mb": round(red_mb, 1),
+            "reduce_tbs_key0": round(red_mb / best(us["reduce"][0]), 2),
+            "reduce_tbs_key1": round(red_mb / best(us["reduce"][1]), 2)}
+
+
 def main():
     from src.moe import _lib as L
     from src.rtdetr_moe import conv as C
@@ -65,7 +104,8 @@ def main():
     torch.backends.cudnn.benchmark = True
     dev = torch.device("cuda", 0)
     shapes = SHAPES
-    args = [a for a in sys.argv[1:] if "=" not in a]
+    wgrad_only = "--wgrad" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if "=" not in a and a != "--wgrad"]
     for kv in [a for a in sys.argv[1:] if "=" in a]:  # e.g. conv_bm=256
         k, v = kv.split("=")
         L._check(L.lib().rtdetr_conv_set_tuning(k.encode(), int(v)), "rtdetr_conv_set_tuning")
@@ -81,6 +121,9 @@ def main():
         gy = torch.randn(B, Co, Ho, Wo, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         pad = (ks - 1) // 2
         flop = 2.0 * B * Ho * Wo * Ci * Co * ks * ks
+        if wgrad_only:
+            print(json.dumps(wgrad_ab(L, C, shape, x, gy, w)), flush=True)
+            continue
         t_mf = timeit(lambda: F.conv2d(x, w, None, st, pad))
         t_md = timeit(lambda: torch.ops.aten.convolution_backward(gy, x, w, None, [st, st], [pad, pad], [1, 1], False,
                                                                   [0, 0], 1, [True, False, False]))
