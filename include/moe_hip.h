@@ -897,6 +897,27 @@ int rtdetr_eval_match_bands(const float* boxes, const float* scores, const int32
 int rtdetr_resize_pad_u8(const uint8_t* src, const long long* desc, int B, int out_h, int out_w, int pad_h,
                          int pad_w, float* dst, hipStream_t stream);
 
+/* rtdetr_resize_pad_u8 with a mirror flag per slot (engine.predict(flip=True):
+ * the mirrored passes of flip test-time augmentation).  flip int32 [B] on the
+ * device; a slot with a non-zero value reads source column w - 1 - j of its
+ * descriptor's window wherever rtdetr_resize_pad_u8 reads column j, in the
+ * tiled LDS form (the horizontal pass's byte pointer starts at 3 (w - 1 - lo)
+ * and steps by -3) and in the direct form alike.  A tile crop -- offset plus
+ * 3 x0, width tw -- mirrors inside its own window and never reads across the
+ * crop's edge.  Tap ranges, fp64 weights, fp32 accumulation in tap order, the
+ * fp32 intermediate, the division by 255, the content top-left of the padding,
+ * every element of dst written exactly once and the empty-slot rules are
+ * rtdetr_resize_pad_u8's, so bit for bit a mirrored slot is what
+ * rtdetr_resize_pad_u8 writes for a host-mirrored copy of the same pixels and
+ * a slot with 0 is rtdetr_resize_pad_u8 on the same descriptor.  (It is NOT
+ * the mirror of the unmirrored slot's image: the taps of a non-integer scale
+ * are not symmetric in the last bits.)
+ * NULL flip is refused without a launch (rtdetr_resize_pad_u8 is the entry
+ * without flags); the other argument checks, B == 0, graph capture and the
+ * profiler kind (MOE_PROF_RESIZE) are rtdetr_resize_pad_u8's. */
+int rtdetr_resize_pad_u8_flip(const uint8_t* src, const long long* desc, const int32_t* flip, int B, int out_h,
+                              int out_w, int pad_h, int pad_w, float* dst, hipStream_t stream);
+
 /* Tiled prediction (engine.predict(tiles=...), merge.py): the detections of a
  * frame's passes -- the full frame and its tiles -- merged by a greedy,
  * score-ordered suppression, one launch per batch, one workgroup per image
@@ -1604,7 +1625,7 @@ enum moe_prof_kind {
   MOE_PROF_AUGMENT = 15,   /* training batch augmentation (train_augment_* / train_mosaic_*) */
   MOE_PROF_EVAL = 16,      /* validation: detections matched to ground truth (rtdetr_eval_match[_bands]), tracks scored (rtdetr_mot_eval, rtdetr_hota_*) */
   MOE_PROF_ROUTE_STATS = 17, /* validation: per-context routing statistics (moe_route_stats) */
-  MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8) */
+  MOE_PROF_RESIZE = 18,    /* inference preprocessing: resize, /255, pad, channels-last (rtdetr_resize_pad_u8[_flip]) */
   MOE_PROF_MERGE = 19,     /* tiled prediction: the passes' detections merged (rtdetr_nms_merge, rtdetr_box_fuse) */
   MOE_PROF_TRACK = 20,     /* tracking: a sequence's detections linked across frames (rtdetr_track_update[_shift|_assoc]) */
   MOE_PROF_MOTION = 21,    /* tracking: a frame's global shift against its predecessor (rtdetr_frame_shift) */

@@ -27,6 +27,9 @@
 // pixel sums its taps from global memory with the same arithmetic -- which is
 // correct at every scale.  Tiles of the padding, and slots whose descriptor is
 // empty (h or w <= 0) or malformed, are zero-filled.
+//
+// rtdetr_resize_pad_u8_flip (predict(flip=True)'s mirrored passes) is the same kernel's second instantiation: a
+// flag per slot, and a flagged slot reads its window's columns right to left in both forms.
 #include "moe_common.h"
 #include "prof.h"
 
@@ -66,9 +69,10 @@ __device__ __forceinline__ double tap_weight(int j, const TapLine& t) {
   return fmax(0.0, 1.0 - fabs(d));
 }
 
-// one output value straight from global memory (any scale)
+// one output value straight from global memory (any scale); mirror: tap j reads source column w - 1 - j
+template <bool kFlip>
 __device__ float resize_direct(const uint8_t* __restrict__ img, int h, int w, long long stride, int out_h, int out_w,
-                               int y, int x, int ch) {
+                               int y, int x, int ch, bool mirror) {
   const TapLine ty = tap_line(y, h, out_h), tx = tap_line(x, w, out_w);
   double sy = 0.0, sx = 0.0;
   for (int j = ty.lo; j < ty.hi; ++j) sy += tap_weight(j, ty);
@@ -77,16 +81,26 @@ __device__ float resize_direct(const uint8_t* __restrict__ img, int h, int w, lo
   for (int jy = ty.lo; jy < ty.hi; ++jy) {
     const uint8_t* row = img + (long long)jy * stride + ch;
     float hacc = 0.f;
-    for (int jx = tx.lo; jx < tx.hi; ++jx) hacc += (float)(tap_weight(jx, tx) / sx) * (float)row[3 * (long long)jx];
+    for (int jx = tx.lo; jx < tx.hi; ++jx) {
+      const int col = kFlip && mirror ? w - 1 - jx : jx;
+      hacc += (float)(tap_weight(jx, tx) / sx) * (float)row[3 * (long long)col];
+    }
     acc += (float)(tap_weight(jy, ty) / sy) * hacc;
   }
   return acc / 255.0f;
 }
 
+// kFlip = false is rtdetr_resize_pad_u8's kernel as it always was (``flip`` is NULL and never read); kFlip = true is
+// rtdetr_resize_pad_u8_flip's: ``flip`` int32 [B], and a slot with a non-zero value (uniform over the workgroup: one
+// slot per blockIdx.z) is read right to left -- wherever the unmirrored form reads column j of the descriptor's
+// window it reads column w - 1 - j, with the same tap ranges, weights and order, so the slot's image is, bit for bit,
+// the one the unmirrored form gives for a host-mirrored copy of the same pixels.
+template <bool kFlip>
 __global__ __launch_bounds__(kRsThreads) void resize_pad_u8_kernel(const uint8_t* __restrict__ src,
                                                                    const long long* __restrict__ desc, int out_h,
                                                                    int out_w, int pad_h, int pad_w,
-                                                                   float* __restrict__ dst) {
+                                                                   float* __restrict__ dst,
+                                                                   const int32_t* __restrict__ flip) {
   // fp32 [kRsRows][kRsRowF] tile of the horizontal pass; before that, the raw fp64 weights [kRsLines][kRsTaps]
   __shared__ __attribute__((aligned(16))) float tile[kRsRows * kRsRowF];
   __shared__ float wts[kRsLines * kRsWS];
@@ -94,6 +108,7 @@ __global__ __launch_bounds__(kRsThreads) void resize_pad_u8_kernel(const uint8_t
   static_assert(sizeof(double) * kRsLines * kRsTaps <= sizeof(float) * kRsRows * kRsRowF, "raw weights fit the tile");
 
   const int tid = threadIdx.x, b = blockIdx.z;
+  const bool mirror = kFlip && flip[b] != 0;
   const int x0 = blockIdx.x * kRsTW, y0 = blockIdx.y * kRsTH;
   const int vr = min(kRsTH, pad_h - y0), vc3 = 3 * min(kRsTW, pad_w - x0);  // the tile's part of dst
   float* __restrict__ out = dst + (((size_t)b * pad_h + y0) * pad_w + x0) * 3;
@@ -111,7 +126,8 @@ __global__ __launch_bounds__(kRsThreads) void resize_pad_u8_kernel(const uint8_t
   if (w64 > (long long)kRsMaxReduce * out_w || h64 > (long long)kRsMaxReduce * out_h) {  // direct form
     for (int e = tid; e < vr * vc3; e += kRsThreads) {
       const int r = e / vc3, xc = e % vc3, y = y0 + r, x = x0 + xc / 3;
-      out[r * orow + xc] = (y < out_h && x < out_w) ? resize_direct(img, h, w, stride, out_h, out_w, y, x, xc % 3)
+      out[r * orow + xc] = (y < out_h && x < out_w) ? resize_direct<kFlip>(img, h, w, stride, out_h, out_w, y, x,
+                                                                             xc % 3, mirror)
                                                     : 0.f;
     }
     return;
@@ -150,18 +166,31 @@ __global__ __launch_bounds__(kRsThreads) void resize_pad_u8_kernel(const uint8_t
   for (int it = tid; it < nrows * kRsRowF; it += kRsThreads) {
     const int r = it / kRsRowF, xc = it % kRsRowF, x = xc / 3, ch = xc - 3 * x;
     const int cnt = cnt_s[x];
-    const uint8_t* p = img + (long long)(r0 + r) * stride + 3 * (long long)lo_s[x] + ch;
+    // mirrored: the byte pointer starts at the window's column w - 1 - lo and steps by -3
+    const uint8_t* p = img + (long long)(r0 + r) * stride + 3 * (long long)(mirror ? w - 1 - lo_s[x] : lo_s[x]) + ch;
     const float* wx = wts + x * kRsWS;
     float acc = 0.f;
     int k = 0;
-    for (; k + 4 <= cnt; k += 4) {  // four byte loads in flight, summed in tap order
-      const float v0 = (float)p[3 * k], v1 = (float)p[3 * k + 3], v2 = (float)p[3 * k + 6], v3 = (float)p[3 * k + 9];
-      acc += wx[k] * v0;
-      acc += wx[k + 1] * v1;
-      acc += wx[k + 2] * v2;
-      acc += wx[k + 3] * v3;
+    if (mirror) {
+      for (; k + 4 <= cnt; k += 4) {
+        const float v0 = (float)p[-3 * k], v1 = (float)p[-3 * k - 3], v2 = (float)p[-3 * k - 6],
+                    v3 = (float)p[-3 * k - 9];
+        acc += wx[k] * v0;
+        acc += wx[k + 1] * v1;
+        acc += wx[k + 2] * v2;
+        acc += wx[k + 3] * v3;
+      }
+      for (; k < cnt; ++k) acc += wx[k] * (float)p[-3 * k];
+    } else {
+      for (; k + 4 <= cnt; k += 4) {  // four byte loads in flight, summed in tap order
+        const float v0 = (float)p[3 * k], v1 = (float)p[3 * k + 3], v2 = (float)p[3 * k + 6], v3 = (float)p[3 * k + 9];
+        acc += wx[k] * v0;
+        acc += wx[k + 1] * v1;
+        acc += wx[k + 2] * v2;
+        acc += wx[k + 3] * v3;
+      }
+      for (; k < cnt; ++k) acc += wx[k] * (float)p[3 * k];
     }
-    for (; k < cnt; ++k) acc += wx[k] * (float)p[3 * k];
     tile[it] = acc;
   }
   __syncthreads();
@@ -193,7 +222,24 @@ extern "C" int rtdetr_resize_pad_u8(const uint8_t* src, const long long* desc, i
   if (grid.y > 65535u || grid.z > 65535u) return fail("rtdetr_resize_pad_u8: need pad_h <= 524280 and B <= 65535");
   // the source sizes live in the device descriptor: the launch is priced by what it writes
   ProfScope prof(stream, PROF_RESIZE, 12.0 * pad_h * pad_w * B + 32.0 * B);
-  MOE_LAUNCH(prof, resize_pad_u8_kernel, grid, dim3(kRsThreads), 0, stream, src, desc, out_h, out_w, pad_h, pad_w,
-             dst);
+  MOE_LAUNCH(prof, resize_pad_u8_kernel<false>, grid, dim3(kRsThreads), 0, stream, src, desc, out_h, out_w, pad_h,
+             pad_w, dst, (const int32_t*)nullptr);
   return check_launch("rtdetr_resize_pad_u8");
+}
+
+extern "C" int rtdetr_resize_pad_u8_flip(const uint8_t* src, const long long* desc, const int32_t* flip, int B,
+                                         int out_h, int out_w, int pad_h, int pad_w, float* dst, hipStream_t stream) {
+  if (B < 0) return fail("rtdetr_resize_pad_u8_flip: need B >= 0");
+  if (out_h < 1 || out_w < 1) return fail("rtdetr_resize_pad_u8_flip: need out_h >= 1 and out_w >= 1");
+  if (pad_h < out_h || pad_w < out_w) return fail("rtdetr_resize_pad_u8_flip: need pad_h >= out_h and pad_w >= out_w");
+  if (!flip) return fail("rtdetr_resize_pad_u8_flip: NULL flip (rtdetr_resize_pad_u8 is the entry without flags)");
+  if (B == 0) return 0;
+  if (!src || !desc || !dst) return fail("rtdetr_resize_pad_u8_flip: NULL pointer");
+  const dim3 grid((pad_w + kRsTW - 1) / kRsTW, (pad_h + kRsTH - 1) / kRsTH, B);
+  if (grid.y > 65535u || grid.z > 65535u)
+    return fail("rtdetr_resize_pad_u8_flip: need pad_h <= 524280 and B <= 65535");
+  ProfScope prof(stream, PROF_RESIZE, 12.0 * pad_h * pad_w * B + 36.0 * B);
+  MOE_LAUNCH(prof, resize_pad_u8_kernel<true>, grid, dim3(kRsThreads), 0, stream, src, desc, out_h, out_w, pad_h,
+             pad_w, dst, flip);
+  return check_launch("rtdetr_resize_pad_u8_flip");
 }

@@ -11,6 +11,7 @@ per (kernel, shape, variant) with us / TFLOP/s / GB/s.
   python multimodal-moe_amd/kbench.py --eval-match-bands  the size-stratified matcher, the plain one and the host loop
   python multimodal-moe_amd/kbench.py --route-stats the routing-statistics kernel against its torch reference
   python multimodal-moe_amd/kbench.py --resize      the inference resize kernel against the host resize it replaces
+  python multimodal-moe_amd/kbench.py --resize-flip the mirrored resize launch against the unmirrored one and the old entry
   python multimodal-moe_amd/kbench.py --nms-merge   tiled prediction's merge kernel against the host reference
   python multimodal-moe_amd/kbench.py --box-fuse    tiled prediction's box-fusion kernel against the merge kernel
   python multimodal-moe_amd/kbench.py --track       the tracker's kernel against the host loop and a forward replay
@@ -730,6 +731,61 @@ def resize_leg(reps, rounds):
         line["hbm_peak_share"] = round(line["GBs"] / L.PEAK_HBM_GBS, 3)
         line["host_over_device_path"] = round(line["host_path_ms"] / line["device_path_ms"], 1)
         print(json.dumps(line), flush=True)
+
+
+def resize_flip_leg(reps, rounds):
+    """rtdetr_resize_pad_u8_flip at --resize's shape (16 frames of 3848 x 2168
+    -> 1248 x 704).  First equality: all flags 1 against rtdetr_resize_pad_u8 on
+    host-mirrored frames, all flags 0 against it on the frames as they are
+    (torch.equal, or the run stops).  Then three launches timed, interleaved in
+    each round: all flags 0, all flags 1, and rtdetr_resize_pad_u8.  kernel_us:
+    the dispatch-stamped execution time; median, min and max over the rounds."""
+    import numpy as np
+
+    from src.rtdetr_moe.preprocess import PackCollate, mirrored, padded_hw
+
+    B, (sh, sw) = 16, (2168, 3848)
+    out_hw, pad_hw = padded_hw((704, 1248))
+    rng = np.random.default_rng(0)
+    frames = []
+    for _ in range(B):  # smooth content plus noise, one frame per slot (resize_leg's)
+        base = rng.integers(0, 256, (sh // 8 + 1, sw // 8 + 1, 3)).astype(np.float32)
+        up = np.kron(base, np.ones((8, 8, 1), np.float32))[:sh, :sw]
+        frames.append(np.clip(up + rng.normal(0, 8, (sh, sw, 3)), 0, 255).astype(np.uint8))
+    pack = PackCollate(out_hw)
+    packed = pack([(f, f"{i}.png", 0) for i, f in enumerate(frames)])
+    dbuf, desc = packed["buf"].cuda(), packed["desc"]
+    L.check_resize_desc(desc, dbuf.numel())
+    ddesc = desc.cuda()
+    zeros, ones = (torch.full((B,), v, dtype=torch.int32, device="cuda") for v in (0, 1))
+    plain = L.resize_pad(dbuf, None, out_hw, pad_hw, desc_dev=ddesc)
+    if not torch.equal(L.resize_pad(dbuf, None, out_hw, pad_hw, desc_dev=ddesc, flip=zeros), plain):
+        raise SystemExit("rtdetr_resize_pad_u8_flip with flags 0 differs from rtdetr_resize_pad_u8")
+    mbuf = pack([(mirrored(f), f"{i}.png", 0) for i, f in enumerate(frames)])["buf"].cuda()
+    want = L.resize_pad(mbuf, None, out_hw, pad_hw, desc_dev=ddesc)
+    del mbuf
+    out = L.resize_pad(dbuf, None, out_hw, pad_hw, desc_dev=ddesc, flip=ones)
+    if not torch.equal(out, want):
+        raise SystemExit("rtdetr_resize_pad_u8_flip with flags 1 differs from rtdetr_resize_pad_u8 on mirrored frames")
+    if torch.equal(out, plain):
+        raise SystemExit("the mirrored launch wrote the unmirrored image")
+    del want, plain
+    legs = {"flip_all_0": lambda: L.resize_pad(dbuf, None, out_hw, pad_hw, out=out, desc_dev=ddesc, flip=zeros),
+            "flip_all_1": lambda: L.resize_pad(dbuf, None, out_hw, pad_hw, out=out, desc_dev=ddesc, flip=ones),
+            "rtdetr_resize_pad_u8": lambda: L.resize_pad(dbuf, None, out_hw, pad_hw, out=out, desc_dev=ddesc)}
+    res = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            res[k].append(timed(fn, reps))
+    byts = int(dbuf.numel()) + 12 * pad_hw[0] * pad_hw[1] * B
+    line = {"kernel": "rtdetr_resize_pad_u8_flip", "shape": f"B{B} {sh}x{sw} -> {out_hw[0]}x{out_hw[1]} "
+            f"(pad {pad_hw[0]}x{pad_hw[1]})", "equal_to_host_mirrored": True, "rounds": rounds, "bytes": byts}
+    for k, v in res.items():
+        line[k + "_us"] = round(statistics.median(v), 3)
+        line[k + "_us_min"] = round(min(v), 3)
+        line[k + "_us_max"] = round(max(v), 3)
+    line["mirrored_over_unmirrored"] = round(line["flip_all_1_us"] / line["flip_all_0_us"], 3)
+    print(json.dumps(line), flush=True)
 
 
 def nms_merge_leg(reps, rounds):
@@ -1823,6 +1879,9 @@ def main():
     ap.add_argument("--nms-merge", action="store_true",
                     help="time rtdetr_nms_merge (B 16, N 1500, max_det 300) against merge.merge_reference on the host "
                          "and one EvalForward replay, and exit")
+    ap.add_argument("--resize-flip", action="store_true",
+                    help="check rtdetr_resize_pad_u8_flip against rtdetr_resize_pad_u8 on host-mirrored frames, time "
+                         "it with all flags 0 and all flags 1 against the old entry (--resize's shape), and exit")
     ap.add_argument("--box-fuse", action="store_true",
                     help="time rtdetr_box_fuse (B 16, 5 passes of 300, max_det 300) against rtdetr_nms_merge on the "
                          "same inputs and one EvalForward replay, after checking it against merge.fuse_reference")
@@ -1881,6 +1940,9 @@ def main():
         return
     if a.route_stats:
         route_stats_leg(a.reps, a.rounds)
+        return
+    if a.resize_flip:
+        resize_flip_leg(a.reps, a.rounds)
         return
     if a.resize:
         resize_leg(a.reps, a.rounds)

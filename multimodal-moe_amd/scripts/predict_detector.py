@@ -47,7 +47,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="ios: intersection over the smaller box; iou: over the union")
     ap.add_argument("--class-agnostic", action="store_true", help="merge across labels")
     ap.add_argument("--merge", type=str, default="nms", choices=("nms", "fuse"),
-                    help="nms: keep the best copy of every object; fuse (with --tiles): average it with its other copies")
+                    help="nms: keep the best copy of every object; fuse (with --tiles or --flip): average it with its "
+                         "other copies")
+    ap.add_argument("--flip", action="store_true",
+                    help="flip test-time augmentation: every pass also runs mirrored, un-mirrored boxes join the merge")
     ap.add_argument("--fuse-iou", type=float, default=0.55,
                     help="--merge fuse: how well a copy must agree with the kept box to be averaged in")
     ap.add_argument("--track", action="store_true",
@@ -149,7 +152,8 @@ def main(argv=None) -> None:
                          name=f"{a.run_name}_predict", save_json=True, save_img=a.save_img, tiles=a.tiles,
                          tile_overlap=a.tile_overlap, merge_iou=a.merge_iou, merge_metric=a.merge_metric,
                          class_agnostic=a.class_agnostic, merge=a.merge, fuse_iou=a.fuse_iou,
-                         track=tracker_args(a), **gt_args(a), **({"save_det": True} if a.save_det else {}))
+                         track=tracker_args(a), **gt_args(a), **({"save_det": True} if a.save_det else {}),
+                         **({"flip": True} if a.flip else {}))
     n_det = sum(len(p.scores) for p in res.predictions)
     print(f"{len(res.predictions)} images, {n_det} detections at conf >= {a.conf}")
     if a.track:

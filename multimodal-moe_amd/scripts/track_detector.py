@@ -14,6 +14,8 @@ DIR/<sequence>.txt): MOTA, MOTP, IDF1 and the counts per sequence and combined,
 printed and written to mot_metrics.json; scripts/eval_tracks.py scores the
 written mot/ directory again later, without a model.  --hota (with --gt) adds
 HOTA, DetA, AssA and LocA to both.
+--flip (as scripts/predict_detector.py takes it) tracks the merged result of
+flip test-time augmentation: every pass also runs mirrored.
 """
 from __future__ import annotations
 

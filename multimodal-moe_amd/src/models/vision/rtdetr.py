@@ -18,6 +18,7 @@ such as the reference default "rtdetr-l.pt" needs a network fetch and raises.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Union
@@ -104,10 +105,23 @@ def eval_rtdetr_detector(
 ):
     """Evaluate a checkpoint on ``split``; returns a metrics object with
     ``.results_dict`` ("metrics/mAP50(B)", ...), ``.box`` (map50, map, mp, mr,
-    curves, curves_results), ``.speed`` (ms per image) and ``.model``."""
+    curves, curves_results), ``.speed`` (ms per image) and ``.model``.
+    The signature is the reference's, so the engine's switches come from the
+    environment, as its reports do: MOE_EVAL_FLIP=1 scores the two-pass ensemble
+    of ``predict_rtdetr_detector(..., flip=True)`` instead -- every batch also
+    runs mirrored and the two passes' rows are merged before they are matched
+    (engine.validate(flip=True)) -- with MOE_EVAL_MERGE (nms | fuse),
+    MOE_EVAL_MERGE_IOU, MOE_EVAL_MERGE_METRIC (ios | iou) and MOE_EVAL_FUSE_IOU
+    as prediction's merge, merge_iou, merge_metric and fuse_iou."""
     eng = _engine()
+    more = {}
+    if os.environ.get("MOE_EVAL_FLIP", "0") == "1":
+        more = dict(flip=True, merge=os.environ.get("MOE_EVAL_MERGE", "nms"),
+                    merge_iou=float(os.environ.get("MOE_EVAL_MERGE_IOU", "0.5")),
+                    merge_metric=os.environ.get("MOE_EVAL_MERGE_METRIC", "ios"),
+                    fuse_iou=float(os.environ.get("MOE_EVAL_FUSE_IOU", "0.55")))
     return eng.validate(_check_model_name(weights_path), data_yaml, split=split, imgsz=_imgsz(imgsz),
-                        batch=batch, device=device, project=project, name=name)
+                        batch=batch, device=device, project=project, name=name, **more)
 
 
 def predict_rtdetr_detector(
@@ -126,6 +140,7 @@ def predict_rtdetr_detector(
     class_agnostic: bool = False,
     merge: str = "nms",
     fuse_iou: float = 0.55,
+    flip: bool = False,
 ):
     """Detect on image files (a directory, a glob, a list of paths or a dataset
     yaml) of any size; returns a results object with ``.predictions`` (per
@@ -137,12 +152,16 @@ def predict_rtdetr_detector(
     (engine.predict); ``.predictions[i].source`` then names each row's pass.
     ``merge="fuse"`` (with tiles) keeps the same rows and averages each box with
     the copies of its object at ``fuse_iou``; ``.predictions[i].members`` then
-    counts the boxes averaged into each row."""
+    counts the boxes averaged into each row.  ``flip=True`` adds horizontal-flip
+    test-time augmentation: every pass runs a second time mirrored, its boxes
+    un-mirrored, and the merge takes all passes (``source`` then counts the
+    mirrored passes after the unmirrored ones; ``merge="fuse"`` is legal
+    without tiles)."""
     eng = _engine()
     return eng.predict(_check_model_name(weights_path), source, imgsz=_imgsz(imgsz), batch=batch, device=device,
                        conf=conf, project=project, name=name, tiles=tiles, tile_overlap=tile_overlap,
                        merge_iou=merge_iou, merge_metric=merge_metric, class_agnostic=class_agnostic, merge=merge,
-                       fuse_iou=fuse_iou)
+                       fuse_iou=fuse_iou, **({"flip": True} if flip else {}))
 
 
 def predict_rtdetr_tracker(
@@ -164,7 +183,7 @@ def predict_rtdetr_tracker(
     fields (None: the defaults, ByteTrack's, not tuned here).  Every
     ``.predictions[i]`` holds the reported rows only and gains ``.track_ids``,
     ``.track_boxes``, ``.sequence`` and ``.frame``; ``.save_dir`` gains
-    tracks.json and mot/<sequence>.txt.  ``predict_args``: tiles, merge, ... as
+    tracks.json and mot/<sequence>.txt.  ``predict_args``: tiles, merge, flip, ... as
     predict_rtdetr_detector takes them."""
     eng = _engine()
     return eng.track(_check_model_name(weights_path), source, imgsz=_imgsz(imgsz), batch=batch, device=device,

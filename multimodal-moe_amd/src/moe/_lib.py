@@ -122,6 +122,7 @@ SIGNATURES = {
     "rtdetr_eval_match": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "rtdetr_eval_match_bands": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_resize_pad_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "rtdetr_resize_pad_u8_flip": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "rtdetr_nms_merge": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "rtdetr_box_fuse": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "rtdetr_track_update": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _F, _F, _I, _P, _P, _P,
@@ -1007,7 +1008,7 @@ def check_resize_desc(desc, nbytes: int) -> None:
                                  f"the {nbytes}-byte source buffer")
 
 
-def resize_pad(src, desc_host, out_hw, pad_hw, out=None, desc_dev=None):
+def resize_pad(src, desc_host, out_hw, pad_hw, out=None, desc_dev=None, flip=None):
     """The model's input from a batch of decoded frames, one launch
     (rtdetr_resize_pad_u8): src uint8 device buffer with the frames (HWC RGB)
     back to back; desc_host int64 [B, 4] on the host (byte offset, height,
@@ -1018,7 +1019,12 @@ def resize_pad(src, desc_host, out_hw, pad_hw, out=None, desc_dev=None):
     check_resize_desc and uploaded it, as a launch under graph capture must).
     Returns the fp32 channels-last [B, 3, pad_h, pad_w] tensor (``out`` when
     given), every element written: content resized to out_hw top-left with the
-    antialiased bilinear filter, / 255, zero padding."""
+    antialiased bilinear filter, / 255, zero padding.
+    ``flip``: None launches rtdetr_resize_pad_u8; an int32 [B] tensor (uploaded
+    here when it is on the host) launches rtdetr_resize_pad_u8_flip, which
+    reads a slot with a non-zero value mirrored: the image of a host-mirrored
+    copy of the slot's window, bit for bit.  The descriptors' host-side bound
+    check is the same."""
     if not src.is_cuda:
         raise MoEKernelError("src must be a GPU tensor (HIP path has no CPU fallback)")
     if src.dtype != torch.uint8 or src.dim() != 1 or not src.is_contiguous():
@@ -1050,8 +1056,16 @@ def resize_pad(src, desc_host, out_hw, pad_hw, out=None, desc_dev=None):
         if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, 3, ph, pw) \
                 or not out.permute(0, 2, 3, 1).is_contiguous():
             raise MoEKernelError(f"resize_pad: out must be a channels-last fp32 GPU tensor [{B}, 3, {ph}, {pw}]")
-    rc = lib().rtdetr_resize_pad_u8(_ptr(src), _ptr(desc_dev), B, oh, ow, ph, pw, _ptr(out), _stream())
-    _check(rc, "rtdetr_resize_pad_u8")
+    if flip is None:
+        rc = lib().rtdetr_resize_pad_u8(_ptr(src), _ptr(desc_dev), B, oh, ow, ph, pw, _ptr(out), _stream())
+        _check(rc, "rtdetr_resize_pad_u8")
+        return out
+    if not isinstance(flip, torch.Tensor) or flip.dtype != torch.int32 or tuple(flip.shape) != (B,):
+        raise MoEKernelError(f"resize_pad: flip must be an int32 [{B}] tensor")
+    flip = flip.to(src.device, non_blocking=True).contiguous()
+    rc = lib().rtdetr_resize_pad_u8_flip(_ptr(src), _ptr(desc_dev), _ptr(flip), B, oh, ow, ph, pw, _ptr(out),
+                                         _stream())
+    _check(rc, "rtdetr_resize_pad_u8_flip")
     return out
 
 

@@ -671,7 +671,7 @@ class EvalForward:
 @torch.no_grad()
 def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed, speed: dict | None = None,
               ev_out: list | None = None, report: dict | None = None, size_report: dict | None = None,
-              size_bands=None):
+              size_bands=None, flip=False, merge="nms", merge_iou=0.5, merge_metric="ios", fuse_iou=0.55):
     """report: a dict to fill with the per-context report (``_fill_report``):
     detection metrics per solar bin and each MoE layer's routing table, summed
     over the split by one more HIP launch per layer forward.  None: the pass
@@ -681,7 +681,15 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
     AP, recall and log-average miss rate per pedestrian-height band of
     size_bands (``metrics.named_bands``; heights in source-frame pixels, an
     image's scale its target's ``src_size`` height over the content height, 1.0
-    without one), matched by one more HIP launch per batch.  None: as above."""
+    without one), matched by one more HIP launch per batch.  None: as above.
+
+    flip: score the two-pass ensemble of predict(flip=True) (``_flip_rows``): a second forward per batch on the
+    mirrored content, its boxes un-mirrored, both passes' rows merged (fused) to the K rows a pass has.  The
+    context report's routing tables count the unmirrored pass only: a replayed graph carries its sink with it, so
+    the tables are put back after the second forward instead of the sink being taken off (the same tables either
+    way).  ``speed`` includes both passes.  False: the pass launches and returns exactly what it does without."""
+    content_w = _hw(imgsz)[1]
+    rule = (merge == "fuse", float(merge_iou), merge_metric, float(fuse_iou))
     model.eval()
     names = bands = None
     if size_report is not None:
@@ -722,12 +730,29 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
                 torch.cuda.synchronize()
             t2 = time.perf_counter()
             H, W = images.shape[-2:]
+            rows, t_second = None, 0.0
+            if flip:  # the graph's outputs are valid until the next call: the first pass's rows before the second
+                first = model.postprocess_batched(out, [(W, H)] * images.shape[0])
+                snap = stats.snapshot() if stats is not None else None
+                mirrored = _mirror_content(images, content_w)
+                if on_gpu:
+                    torch.cuda.synchronize()
+                tm = time.perf_counter()
+                out = fwd(mirrored, ctx)
+                if on_gpu:
+                    torch.cuda.synchronize()
+                t_second = time.perf_counter() - tm  # "inference" has both forwards, "postprocess" the rest
+                if snap is not None:
+                    stats.restore(snap)
+                rows = _flip_rows(first, model.postprocess_batched(out, [(W, H)] * images.shape[0]), content_w,
+                                  content_h, rule, on_gpu)
             if on_gpu:
-                ev.update_batch(*model.postprocess_batched(out, [(W, H)] * images.shape[0]), targets, size=(W, H),
-                                ctx=ids, bands=bands, scales=scales)
+                ev.update_batch(*(rows or model.postprocess_batched(out, [(W, H)] * images.shape[0])), targets,
+                                size=(W, H), ctx=ids, bands=bands, scales=scales)
                 torch.cuda.synchronize()
             else:
-                dets = model.postprocess(out, [(W, H)] * images.shape[0])
+                dets = [{"boxes": b, "scores": sc, "labels": lb} for b, sc, lb in zip(*rows)] if flip \
+                    else model.postprocess(out, [(W, H)] * images.shape[0])
                 for i, (det, t) in enumerate(zip(dets, targets)):
                     gt_xyxy = gt_xyxy_pixels(t["boxes"].numpy().astype(np.float64), W, H)
                     ev.update(det["boxes"].float().cpu().numpy(), det["scores"].float().cpu().numpy(),
@@ -736,8 +761,8 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
                               scale=1.0 if scales is None else scales[i])
             t3 = time.perf_counter()
             t_pre += t1 - t0 - t_cap
-            t_inf += t2 - t1
-            t_post += t3 - t2
+            t_inf += t2 - t1 + t_second
+            t_post += t3 - t2 - t_second
             n_img += images.shape[0]
     model.train()
     if speed is not None and n_img:
@@ -748,6 +773,57 @@ def _evaluate(model: RTDETRMoE, data, split, imgsz, batch, device, workers, seed
     if size_report is not None:
         _fill_size_report(size_report, ev, names, bands, n_img)
     return ev.compute()
+
+
+def _mirror_content(images, content_w: int):
+    """The batch with its content region mirrored: columns [0, content_w) reversed, the padding left where it is,
+    the layout (channels-last on the GPU) kept."""
+    out = images.clone()
+    out[..., :content_w] = images[..., :content_w].flip(-1)
+    return out
+
+
+def _flip_rows(first, second, content_w, content_h, rule, on_gpu):
+    """validate(flip=True): the two passes' rows -> the merged rows to score.  ``first`` / ``second``:
+    postprocess_batched's (boxes [B, K, 4], scores, labels) of the batch and of its mirrored copy, in pixels of the
+    padded tensor, whose content starts at x = 0: the second pass's boxes are un-mirrored with
+    merge.unmirror_boxes(., content_w), the rows concatenated [B, 2 K] and merged to max_det = K at conf 0 by the
+    call predict uses -- ``rule``: (fuse, merge_iou, merge_metric, fuse_iou); fused, both passes have the content
+    region (0, 0, content_w, content_h) as their window (validation clips no box, so no side is ever cut by it).
+    K is postprocess_batched's, at most 300, so the 2 K candidates always fit the merge's limits.  On a GPU: ONE
+    launch (_lib.nms_merge / _lib.box_fuse) -> (boxes [B, K, 4], scores,
+    labels [B, K]) with the merge's zero-score tail as it stands: update_batch takes no per-image count, and it
+    drops rows scored under its conf_thres (0.001) before they reach any list, so the tail is neutral for AP.  On
+    the CPU: merge_reference / fuse_reference per image -> three lists of the kept rows."""
+    from .merge import fuse_reference, merge_reference, unmirror_boxes
+
+    fuse, merge_iou, merge_metric, fuse_iou = rule
+    (b1, s1, l1), (b2, s2, l2) = first, second
+    B, K = int(s1.shape[0]), int(s1.shape[1])
+    cb = torch.cat([b1, unmirror_boxes(b2, float(content_w))], 1)
+    cs, cl = torch.cat([s1, s2], 1), torch.cat([l1, l2], 1)
+    win = torch.tensor([[[0.0, 0.0, float(content_w), float(content_h)]] * 2] * B,
+                       dtype=torch.float32) if fuse else None
+    if on_gpu:
+        from ..moe import _lib
+
+        args = (cb.contiguous(), cs.contiguous(), cl.to(torch.int32).contiguous(), None, 0.0, merge_iou, merge_metric,
+                K, False)
+        got = _lib.box_fuse(*args, fuse_iou, win.to(cb.device)) if fuse else _lib.nms_merge(*args)
+        return got[0], got[1], got[2].to(l1.dtype)
+    boxes, scores, labels = [], [], []
+    for i in range(B):
+        if fuse:
+            keep, fb, _ = fuse_reference(cb[i], cs[i], cl[i], None, 0.0, merge_iou, merge_metric, K, False, fuse_iou,
+                                         win[i])
+            boxes.append(torch.from_numpy(fb).reshape(-1, 4))
+        else:
+            keep = merge_reference(cb[i], cs[i], cl[i], None, 0.0, merge_iou, merge_metric, K, False)
+            boxes.append(cb[i][torch.from_numpy(keep)])
+        keep = torch.from_numpy(keep)
+        scores.append(cs[i][keep])
+        labels.append(cl[i][keep])
+    return boxes, scores, labels
 
 
 def _fill_size_report(report: dict, ev: DetectionEvaluator, names, bands, images: int) -> None:
@@ -791,7 +867,8 @@ def _fill_report(report: dict, model: RTDETRMoE, ev: DetectionEvaluator, stats) 
 
 def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0", project=None, name=None,
              workers=4, seed=0, context_report: bool | None = None, size_report: bool | None = None,
-             size_bands=None) -> DetMetrics:
+             size_bands=None, flip=False, merge="nms", merge_iou=0.5, merge_metric="ios",
+             fuse_iou=0.55) -> DetMetrics:
     """context_report: also build the per-context report (``DetMetrics.context``
     and, with a save directory, context_report.json there); None reads
     MOE_CONTEXT_REPORT=1.  Off by default.
@@ -801,9 +878,25 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
     rate per pedestrian-height band; None reads MOE_SIZE_REPORT=1.  Off by
     default.  size_bands: (name, lo, hi) triples in source-frame pixels, lo
     inclusive, hi exclusive, hi None for an open band (default far [0, 40),
-    medium [40, 100), near [100, inf))."""
+    medium [40, 100), near [100, inf)).
+
+    flip (off by default): score predict(flip=True)'s two-pass ensemble against
+    the ground truth -- per batch a second forward on the images with their
+    content mirrored, its boxes un-mirrored (merge.unmirror_boxes), the two
+    passes' rows [B, 2 K] merged to K rows at conf 0 by predict's own merge
+    (``merge`` "nms" or "fuse" with ``merge_iou``, ``merge_metric`` and
+    ``fuse_iou`` as predict takes them; one rtdetr_nms_merge / rtdetr_box_fuse
+    launch on a GPU, merge_reference / fuse_reference per image on the CPU).
+    Every metric and both reports then describe the merged rows; the context
+    report's routing tables count the unmirrored pass only, and ``speed``
+    includes both passes.  Without ``flip`` the merge arguments are not looked
+    at and validation launches and returns what it always did."""
     if size_bands is not None:
         named_bands(size_bands)  # a bad table fails before the model loads
+    if flip:
+        from .predictor import _check_args
+
+        _check_args(None, 0.2, merge, merge_iou, merge_metric, fuse_iou, None, True)  # before the model loads
     devices = parse_device(device)
     dev = torch.device("cpu") if devices == ["cpu"] else torch.device("cuda", devices[0])
     if dev.type == "cuda":
@@ -818,7 +911,8 @@ def validate(weights, data, split="val", imgsz=(704, 1248), batch=16, device="0"
     report = {} if _context_report_on(context_report) else None
     sizes = {} if _size_report_on(size_report) else None
     box = _evaluate(model, data, split, imgsz, batch, dev, workers, seed, speed, report=report, size_report=sizes,
-                    size_bands=size_bands)
+                    size_bands=size_bands, flip=bool(flip), merge=merge, merge_iou=merge_iou,
+                    merge_metric=merge_metric, fuse_iou=fuse_iou)
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:
         save_dir.mkdir(parents=True, exist_ok=True)

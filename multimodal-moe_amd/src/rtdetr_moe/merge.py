@@ -1,6 +1,8 @@
-"""Tiled prediction's two host-side definitions (engine.predict(tiles=...)).
+"""Multi-pass prediction's host-side definitions (engine.predict(tiles=..., flip=...)).
 
 * ``tile_windows``: the overlapping grid of crops of a frame.
+* ``unmirror_boxes``: the boxes of a mirrored pass back in their window
+  (predict / validate with ``flip``).
 * ``merge_reference``: the greedy, score-ordered merge of the detections of a
   frame's passes (full frame + tiles), stated once.  The HIP kernel
   rtdetr_nms_merge (_lib.nms_merge) takes the same decisions bit for bit and is
@@ -73,6 +75,31 @@ def parse_tiles(tiles):
     if rows < 1 or cols < 1:
         raise ValueError(f"tiles must be >= 1 per axis, got {rows}x{cols}")
     return rows, cols
+
+
+def unmirror_boxes(boxes, width):
+    """The boxes of a mirrored pass (predict / validate with ``flip``) back in
+    the unmirrored window: boxes fp32 [..., 4] xyxy (a tensor on any device, or
+    an array) -> the same kind and shape with x1' = width - x2 and x2' = width
+    - x1, y unchanged; fp32, each subtraction rounded on its own.  ``width``:
+    the window's width in the boxes' units, a number or anything that
+    broadcasts against boxes[..., 0] (one width per slot: [S, 1] for [S, k, 4]
+    boxes); it is rounded to fp32 first.  Applied to a mirrored pass's boxes as
+    postprocess_batched returns them, ahead of the shift by the window's origin
+    and the clip.  On coordinates and widths that fp32 subtracts exactly it is
+    its own inverse."""
+    import torch
+
+    if isinstance(boxes, torch.Tensor):
+        if boxes.dtype != torch.float32:
+            raise ValueError(f"unmirror_boxes: boxes must be fp32, got {boxes.dtype}")
+        w = torch.as_tensor(width, dtype=torch.float32, device=boxes.device)
+        return torch.stack([w - boxes[..., 2], boxes[..., 1], w - boxes[..., 0], boxes[..., 3]], -1)
+    b = np.asarray(boxes)
+    if b.dtype != np.float32:
+        raise ValueError(f"unmirror_boxes: boxes must be fp32, got {b.dtype}")
+    w = np.asarray(width, dtype=np.float32)
+    return np.stack([w - b[..., 2], b[..., 1], w - b[..., 0], b[..., 3]], -1).astype(np.float32)
 
 
 def merge_reference(boxes, scores, labels, n_valid, conf, thr, metric="ios", max_det=300, class_agnostic=False):

@@ -27,7 +27,7 @@ import torch
 from ..moe import _lib
 from ..moe.context import MISSING_ID
 from .merge import (FUSE_MAX_DET, FUSE_MAX_N, FUSE_MAX_P, MERGE_MAX_DET, MERGE_MAX_N, METRICS, fuse_reference,
-                    merge_reference, parse_tiles, tile_windows)
+                    merge_reference, parse_tiles, tile_windows, unmirror_boxes)
 from .motion import MotionState, new_motion_state, sequence_shifts
 from .preprocess import mapped_sizes
 from .track import TRACK_MAX_K, TrackArgs, TrackState, new_state, track_reference
@@ -49,7 +49,8 @@ class Prediction:
     boxes: torch.Tensor
     scores: torch.Tensor
     labels: torch.Tensor
-    # tiled prediction: the pass each row came from, int64 [n]: 0 the full frame, 1 + t tile t; None without tiles
+    # tiled prediction: the pass each row came from, int64 [n]: 0 the full frame, 1 + t tile t; with flip, P0 = 1 +
+    # tiles more passes follow, pass P0 + p the mirror of pass p; None without tiles and flip
     source: torch.Tensor | None = None
     # merge="fuse": the candidates averaged into each row's box, its own included, int64 [n] (>= 1); None otherwise
     members: torch.Tensor | None = None
@@ -199,21 +200,22 @@ TRACK_COLS, TRACK_ID, TRACK_BOX = 5, -5, slice(-4, None)
 CMC_COLS, CMC = 3, slice(-8, -5)
 
 
-def _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track):
+def _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track, flip=False):
     """-> (TrackArgs or None, tiles (rows, cols) or None, fuse): what can be refused before a device or a model is
-    touched."""
+    touched.  ``flip``: the run has mirrored passes, which the merge's arguments then serve as they serve tiles."""
     targs = None if track is None or track is False else TrackArgs.parse(track)
     tiles = parse_tiles(tiles)
     if merge not in ("nms", "fuse"):
         raise ValueError(f"merge must be 'nms' or 'fuse', got {merge!r}")
     fuse = merge == "fuse"
     if fuse:
-        if tiles is None:
+        if tiles is None and not flip:
             raise ValueError("merge='fuse' fuses the passes of tiled prediction: give tiles=(rows, cols)")
         if not 0.0 <= float(fuse_iou) <= 1.0:
             raise ValueError(f"fuse_iou must be in [0, 1], got {fuse_iou}")
     if tiles is not None:
         tile_windows(2 * tiles[1], 2 * tiles[0], tiles, tile_overlap)  # the overlap's ValueError, before any work
+    if tiles is not None or flip:
         if merge_metric not in METRICS:
             raise ValueError(f"merge_metric must be one of {sorted(METRICS)}, got {merge_metric!r}")
         if not 0.0 <= float(merge_iou) <= 1.0:
@@ -221,12 +223,24 @@ def _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, t
     return targs, tiles, fuse
 
 
-def _check_candidates(tiles, fuse, max_det, model) -> int:
+def _check_candidates(tiles, fuse, max_det, model, flip=False) -> int:
     """-> the tiles per frame (0 without tiles), once the loaded model's candidates per frame fit the merge's
-    (the fusion's) limits."""
-    if tiles is None:
+    (the fusion's) limits.  ``flip`` doubles the passes: 2 P0 k candidates and 2 P0 passes, P0 = 1 + tiles."""
+    if tiles is None and not flip:
         return 0
-    n_tiles = tiles[0] * tiles[1]
+    n_tiles = 0 if tiles is None else tiles[0] * tiles[1]
+    if flip:
+        grid = "no tiles" if tiles is None else f"tiles {tiles[0]}x{tiles[1]}"
+        n_pass = 2 * (1 + n_tiles)
+        n_cand = n_pass * min(max_det, model.decoder.num_queries * model.num_classes)
+        if n_cand > MERGE_MAX_N or max_det > MERGE_MAX_DET:
+            raise ValueError(f"{grid} with flip and max_det {max_det} is {n_cand} candidates per frame: the merge "
+                             f"takes at most {MERGE_MAX_N} candidates and max_det {MERGE_MAX_DET}")
+        if fuse and (n_cand > FUSE_MAX_N or max_det > FUSE_MAX_DET or n_pass > FUSE_MAX_P):
+            raise ValueError(f"{grid} with flip and max_det {max_det} is {n_pass} passes and {n_cand} candidates "
+                             f"per frame: the fusion takes at most {FUSE_MAX_P} passes, {FUSE_MAX_N} candidates "
+                             f"and max_det {FUSE_MAX_DET}")
+        return n_tiles
     n_cand = (1 + n_tiles) * min(max_det, model.decoder.num_queries * model.num_classes)
     if n_cand > MERGE_MAX_N or max_det > MERGE_MAX_DET:
         raise ValueError(f"tiles {tiles[0]}x{tiles[1]} with max_det {max_det} is {n_cand} candidates per frame: "
@@ -245,13 +259,17 @@ def _pad_slots(t, slots, value=0):
     return torch.cat([t, t.new_full((fill,) + tuple(t.shape[1:]), value)]) if fill > 0 else t
 
 
-def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False):
+def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False, mirror=False):
     """One detection pass over a chunk of m <= batch slots.  ``ctx`` int32 [m]; ``windows`` the slots' (x0, y0, w,
     h) in source pixels; the model's input is either rows ``desc`` of the resize kernel's descriptor table into
     ``src`` (one resize launch) or the host's ``images``.  On a GPU the chunk is filled to ``batch`` with empty
     slots.  ``full``: the slots are whole frames -- ``src`` is the batch's buffer on the host and goes up here (the
     one upload; the tile passes take the device's copy), the first call captures the graph (untimed), and the boxes
-    are clipped without the shift by the origin (adding a zero origin would turn a -0.0 into +0.0).  -> a namespace:
+    are clipped without the shift by the origin (adding a zero origin would turn a -0.0 into +0.0).  ``mirror``: a
+    mirrored pass (predict(flip=True)) -- the resize launch reads the slots right to left (flip = 1 per slot, one
+    device tensor kept on ``run``; rtdetr_resize_pad_u8_flip; ``images`` are the host's mirrored ones) and the
+    boxes are un-mirrored in their window
+    (merge.unmirror_boxes with the window's width) ahead of the shift and the clip.  -> a namespace:
     boxes [S, k, 4] in source pixels, scores, labels [S, k] and lim [S, 4], the clipping limits, of all S slots, the
     m real ones first; src, and images, the model's input, on the device; the clock at t_ready, the input standing on
     the device, and at t_done, after the forward, and t_cap, the capture's seconds before t_ready.  ``run``: the
@@ -262,7 +280,12 @@ def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False):
     ctx = _pad_slots(ctx, slots, MISSING_ID).to(run.dev)
     if desc is not None:
         src = src.to(run.dev, non_blocking=True)  # a tile pass: on the device already, nothing is copied
-        images = _lib.resize_pad(src, _pad_slots(desc, slots), run.out_hw, run.pad_hw)
+        flags = None
+        if mirror:  # one device tensor for the run: a fill slot's descriptor is empty whatever its flag says
+            if getattr(run, "flip_flags", None) is None:
+                run.flip_flags = torch.ones(slots, dtype=torch.int32, device=run.dev)
+            flags = run.flip_flags
+        images = _lib.resize_pad(src, _pad_slots(desc, slots), run.out_hw, run.pad_hw, flip=flags)
     else:
         images = _pad_slots(images, slots).to(run.dev, non_blocking=True)
         if on_gpu:
@@ -281,6 +304,9 @@ def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False):
     t_done = time.perf_counter()
     mapped = mapped_sizes([(w, h) for _, _, w, h in windows], run.out_hw, run.pad_hw) + [(1.0, 1.0)] * fill
     boxes, scores, labels = run.model.postprocess_batched(out, mapped, num_top=run.max_det)
+    if mirror:
+        boxes = unmirror_boxes(boxes, torch.tensor([[w] for _, _, w, _ in windows] + [[1.0]] * fill,
+                                                   dtype=boxes.dtype, device=boxes.device))
     lim = torch.tensor([[x0 + w, y0 + h, x0 + w, y0 + h] for x0, y0, w, h in windows] + [[1.0] * 4] * fill,
                        dtype=boxes.dtype, device=boxes.device)
     if full:
@@ -293,11 +319,13 @@ def _detect(run, ctx, windows, src=None, desc=None, images=None, full=False):
                            t_ready=t_ready, t_done=t_done)
 
 
-def _tile_candidates(run, bt, full, n_tiles):
+def _tile_candidates(run, bt, full, n_tiles, mirror=False):
     """The tile passes of a batch of n frames, whose full-frame pass gave ``full`` (_detect's): the n n_tiles tiles
     are slots, frame-major, detected in chunks of ``batch`` on the captured graph (rows of bt["tile_desc"] into the
     uploaded buffer, or bt["tile_images"]) -> the candidates per frame [n, (1 + n_tiles) k, ...], the full frame's
-    k rows, then each tile's, row-major, and the passes' seconds of "preprocess" and of "inference"."""
+    k rows, then each tile's, row-major, and the passes' seconds of "preprocess" and of "inference".  ``mirror``:
+    the mirrored tile passes after the mirrored full-frame pass ``full`` -- the same descriptor rows read mirrored
+    (or bt["flip_tile_images"]), every crop inside its own window."""
     n, k = len(bt["paths"]), full.boxes.shape[1]
     wins = [w for frame_wins in bt["windows"] for w in frame_wins]
     slot_ctx = bt["ctx"].repeat_interleave(n_tiles)
@@ -309,7 +337,8 @@ def _tile_candidates(run, bt, full, n_tiles):
         m = len(wins[part])
         det = _detect(run, slot_ctx[part], wins[part], full.src,
                       None if full.src is None else bt["tile_desc"][part],
-                      bt["tile_images"][part] if full.src is None else None)
+                      bt["flip_tile_images" if mirror else "tile_images"][part] if full.src is None else None,
+                      mirror=mirror)
         tb.append(det.boxes[:m])
         ts.append(det.scores[:m])
         tl.append(det.labels[:m])
@@ -321,16 +350,20 @@ def _tile_candidates(run, bt, full, n_tiles):
     return cb, cs, cl, t_pre, t_inf
 
 
-def _pass_windows(sizes, windows):
+def _pass_windows(sizes, windows, flip=False):
     """The passes' windows per frame for the fusion, fp32 [n, P, 4] x0 y0 x1 y1 on the host: the frame, then the
-    bounds each tile's boxes were clipped with."""
-    return torch.tensor([[[0.0, 0.0, float(fw), float(fh)]]
-                         + [[float(x0), float(y0), float(x0 + tw), float(y0 + th)] for x0, y0, tw, th in wins]
-                         for (fw, fh), wins in zip(sizes, windows)], dtype=torch.float32)
+    bounds each tile's boxes were clipped with (``windows``: per frame its tiles', None without tiles).  ``flip``:
+    the same rows once more -- an un-mirrored box is in source coordinates and a cut side is cut on the same edge,
+    so a mirrored pass has the window of its unmirrored pass."""
+    win = torch.tensor([[[0.0, 0.0, float(fw), float(fh)]]
+                        + [[float(x0), float(y0), float(x0 + tw), float(y0 + th)] for x0, y0, tw, th in wins]
+                        for (fw, fh), wins in zip(sizes, windows or [[]] * len(sizes))], dtype=torch.float32)
+    return torch.cat([win, win], 1) if flip else win
 
 
 def _merge_rows(cb, cs, cl, rule, fuse_iou, win, on_device, track_block=None, heads=None) -> list:
-    """The merge of a batch's candidates [n, N, ...] (the full frame's k rows, then each tile's) -> the frames' kept
+    """The merge of a batch's candidates [n, N, ...] (the full frame's k rows, then each tile's; with flip the
+    mirrored passes' in the same order after them) -> the frames' kept
     rows on the host: BOX, SCORE, LABEL, CAND and, fused, MEMBERS.  ``rule``: (conf, merge_iou, merge_metric,
     max_det, class_agnostic); ``win`` fp32 [n, P, 4], the passes' windows: fuse with ``fuse_iou`` (None: NMS).
     ``on_device``: ONE launch (rtdetr_nms_merge / rtdetr_box_fuse) and one packed copy back, which
@@ -548,7 +581,7 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
             workers=4, project=None, name=None, save_json=True, save_img=False, tiles=None, tile_overlap=0.2,
             merge_iou=0.5, merge_metric="ios", class_agnostic=False, merge="nms", fuse_iou=0.55, track=None,
             sequence_of=None, gt=None, gt_classes=None, gt_ignore_classes=(), eval_iou=0.5,
-            hota=False, save_det=False) -> PredictResults:
+            hota=False, save_det=False, flip=False) -> PredictResults:
     """Detect on image files of any size.  ``source``: a directory, a glob, a
     list of paths or a dataset yaml (preprocess.FrameSource).  On a GPU each
     batch is one upload of the decoded uint8 frames and ONE HIP launch
@@ -663,11 +696,41 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     predictions.json, the run's rows as MOTChallenge detection text
     (tune.det_lines: frame,-1,x,y,w,h,score,class,-1,-1, every fp32 value with
     its bits), sequences and frame numbers from frame_sequences as for
-    tracking -- the input of engine.tune_tracker / scripts/tune_tracker.py."""
+    tracking -- the input of engine.tune_tracker / scripts/tune_tracker.py.
+    ``flip`` (off by default): horizontal-flip test-time augmentation.  Every
+    pass -- the full frame and, with ``tiles``, every tile -- runs a second
+    time on its window mirrored, and the merge (the fusion) takes the
+    candidates of all 2 P0 passes, P0 = 1 + rows cols: today's passes first,
+    then their mirrored copies in the same order, so pass P0 + p of
+    ``Prediction.source`` is the mirror of pass p and ``.speed["passes"]`` is
+    2 P0 (2 without tiles).  A mirrored pass's input is the resize of the
+    window's mirrored bytes (preprocess.resize_reference of a[:, ::-1]; NOT the
+    mirror of the resized image: the two differ in late bits wherever the taps
+    are not symmetric).  On a GPU the mirrored passes are further chunks of
+    ``batch`` slots over the same descriptor rows -- the full frames', then the
+    tiles' -- with flip = 1 (rtdetr_resize_pad_u8_flip: one resize launch per
+    chunk, reading the buffer already on the device, no second upload), each a
+    replay of the same captured graph with the slots' contexts; on the host
+    path the collates add host_resize of the mirrored frame or crop.  A
+    mirrored pass's boxes are un-mirrored in their window
+    (merge.unmirror_boxes: x1' = w - x2, x2' = w - x1 in fp32, w the window's
+    width) as postprocess_batched returns them, before the shift by the
+    window's origin and the clip; everything after that is what runs for
+    tiles.  For the fusion a mirrored pass has its unmirrored pass's window.
+    Without ``tiles`` the candidates [n, 2 k] go through the same merge /
+    fusion launch, and merge="fuse" is legal.  The limits are the kernels':
+    2 P0 k <= 4096 candidates, and 2 P0 <= 64 passes for the fusion (a 2x2 grid
+    with flip at max_det 300 fits, a 3x3 grid does not).  The tracker and the
+    camera-motion estimate hang off the merge's output and the unmirrored
+    full-frame pass's input, as with tiles.  No accuracy claim is made: the
+    tree has no trained weights; validate(..., flip=True) scores the same
+    two-pass ensemble against ground truth.  With ``flip`` off nothing of this
+    runs."""
     # engine imports this module, and tests replace engine.EvalForward and preprocess.FrameSource: looked up per call
     from . import engine, preprocess
 
-    targs, tiles, fuse = _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track)
+    flip = bool(flip)
+    targs, tiles, fuse = _check_args(tiles, tile_overlap, merge, merge_iou, merge_metric, fuse_iou, track, flip)
     if save_det and targs is not None:
         raise ValueError("save_det writes an untracked run's detections: a tracked frame holds only the reported rows")
     if gt is not None:
@@ -694,21 +757,23 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     model.eval()
     out_hw, pad_hw = preprocess.padded_hw(imgsz)
     gpu_resize = predict_resize_on_gpu(dev)
-    n_tiles = _check_candidates(tiles, fuse, max_det, model)
+    n_tiles = _check_candidates(tiles, fuse, max_det, model, flip)
+    merged = tiles is not None or flip  # more than one pass per frame: the candidates go through the merge
     gpu_merge = predict_merge_on_gpu(dev)
     ds = preprocess.FrameSource(source, contexts=contexts)
     tracker = None
     if targs is not None:  # on the device unless the merge left the candidates on the host
         tracker = _Tracker(targs, ds.paths, sequence_of, batch, max_det, dev,
-                           predict_track_on_gpu(dev) and (tiles is None or gpu_merge), out_hw)
+                           predict_track_on_gpu(dev) and (not merged or gpu_merge), out_hw)
     truth = _load_truth(gt, tracker.seq_of, gt_classes, gt_ignore_classes) if gt is not None else None
     gpu_track = tracker is not None and tracker.on_device
     cmc = tracker is not None and tracker.cmc
     if tiles is None:
-        collate = preprocess.PackCollate(out_hw, pin=True) if gpu_resize else preprocess.HostCollate(out_hw, pad_hw)
+        collate = preprocess.PackCollate(out_hw, pin=True) if gpu_resize \
+            else preprocess.HostCollate(out_hw, pad_hw, flip)
     else:
         collate = preprocess.TilePackCollate(out_hw, tiles, tile_overlap, pin=True) if gpu_resize \
-            else preprocess.TileHostCollate(out_hw, pad_hw, tiles, tile_overlap)
+            else preprocess.TileHostCollate(out_hw, pad_hw, tiles, tile_overlap, flip)
     run = SimpleNamespace(model=model, fwd=engine.EvalForward(model), dev=dev, batch=batch, max_det=max_det,
                           out_hw=out_hw, pad_hw=pad_hw)
     clock = {"preprocess": 0.0, "inference": 0.0, "postprocess": 0.0}  # seconds, every batch's
@@ -731,13 +796,26 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
         heads = [] if cmc and gpu_track else None  # every frame's first row: its CMC columns
         if cmc and not gpu_track:
             tracker.host_block(n_done, full.images, sizes)
-        t_pre = t_inf = 0.0  # of the tile passes
-        if tiles is None:
+        t_pre = t_inf = 0.0  # of the passes after the full-frame one
+        if not merged:
             rows, k = _untiled_rows(full, n, conf, track_block, heads), None
         else:
             k = full.boxes.shape[1]
-            cb, cs, cl, t_pre, t_inf = _tile_candidates(run, bt, full, n_tiles)
-            win = _pass_windows(sizes, bt["windows"]) if fuse else None
+            cb, cs, cl = full.boxes[:n], full.scores[:n], full.labels[:n]
+            if tiles is not None:
+                cb, cs, cl, t_pre, t_inf = _tile_candidates(run, bt, full, n_tiles)
+            if flip:  # the mirrored passes, in the same order: the full frames' descriptor rows, then the tiles'
+                ta = time.perf_counter()
+                mfull = _detect(run, bt["ctx"], [(0, 0, w, h) for w, h in sizes], full.src, bt.get("desc"),
+                                bt.get("flip_images"), full=True, mirror=True)
+                t_pre += mfull.t_ready - ta
+                t_inf += mfull.t_done - mfull.t_ready
+                mb, ms, ml = mfull.boxes[:n], mfull.scores[:n], mfull.labels[:n]
+                if tiles is not None:
+                    mb, ms, ml, tp, ti = _tile_candidates(run, bt, mfull, n_tiles, mirror=True)
+                    t_pre, t_inf = t_pre + tp, t_inf + ti
+                cb, cs, cl = torch.cat([cb, mb], 1), torch.cat([cs, ms], 1), torch.cat([cl, ml], 1)
+            win = _pass_windows(sizes, bt.get("windows"), flip) if fuse else None
             rows = _merge_rows(cb, cs, cl, rule, fuse_iou, win, gpu_merge, track_block, heads)
         for i, row in enumerate(rows):
             tr = {}
@@ -753,8 +831,8 @@ def predict(weights, source, imgsz=(704, 1248), batch=16, device="0", conf=0.25,
     if was_training:
         model.train()
     speed = {key: 1e3 * t / max(len(preds), 1) for key, t in clock.items()}
-    if tiles is not None:
-        speed["passes"] = 1 + n_tiles
+    if merged:
+        speed["passes"] = (1 + n_tiles) * (2 if flip else 1)
     mot = _score_tracks(preds, truth, eval_iou, dev, bool(hota)) if truth is not None else None
     save_dir = Path(project) / name if project and name else None
     if save_dir is not None:

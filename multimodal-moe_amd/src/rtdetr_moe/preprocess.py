@@ -22,6 +22,11 @@
 * ``TilePackCollate`` / ``TileHostCollate``: the same batches with the tiles of
   every frame (engine.predict(tiles=...)): further descriptor rows into the
   buffer that is uploaded anyway, or crops resized on the host.
+* ``mirrored``: a frame or crop with its columns reversed.  The mirrored image
+  of predict(flip=True) is the resize of the mirrored bytes (resize_reference /
+  host_resize of ``mirrored(a)``), not the mirror of the resized image; on the
+  GPU rtdetr_resize_pad_u8_flip reads the same descriptor rows right to left,
+  and the host collates add it with ``flip``.
 """
 from __future__ import annotations
 
@@ -226,18 +231,28 @@ def host_resize(frame: np.ndarray, out_hw, pad_hw) -> torch.Tensor:
     return _padded_image(np.asarray(im, dtype=np.uint8), pad_hw[0], pad_hw[1], False)
 
 
+def mirrored(frame: np.ndarray) -> np.ndarray:
+    """A frame or a crop, uint8 [h, w, 3], with its columns reversed (a contiguous copy)."""
+    return frame[:, ::-1].copy()
+
+
 class HostCollate:
     """[(frame, path, ctx)] -> {"images": fp32 [B, 3, pad_h, pad_w], "paths",
-    "sizes", "ctx"}: the datasets' host preprocessing."""
+    "sizes", "ctx"}: the datasets' host preprocessing.  With ``flip`` also
+    "flip_images", the mirrored passes' inputs (predict(flip=True)): host_resize
+    of each frame's mirrored bytes -- not the mirror of its resized image."""
 
-    def __init__(self, out_hw, pad_hw):
-        self.out_hw, self.pad_hw = tuple(out_hw), tuple(pad_hw)
+    def __init__(self, out_hw, pad_hw, flip=False):
+        self.out_hw, self.pad_hw, self.flip = tuple(out_hw), tuple(pad_hw), bool(flip)
 
     def __call__(self, batch):
-        return {"images": torch.stack([host_resize(b[0], self.out_hw, self.pad_hw) for b in batch]),
-                "paths": [b[1] for b in batch],
-                "sizes": [(int(b[0].shape[1]), int(b[0].shape[0])) for b in batch],
-                "ctx": torch.tensor([b[2] for b in batch], dtype=torch.int32)}
+        bt = {"images": torch.stack([host_resize(b[0], self.out_hw, self.pad_hw) for b in batch]),
+              "paths": [b[1] for b in batch],
+              "sizes": [(int(b[0].shape[1]), int(b[0].shape[0])) for b in batch],
+              "ctx": torch.tensor([b[2] for b in batch], dtype=torch.int32)}
+        if self.flip:
+            bt["flip_images"] = torch.stack([host_resize(mirrored(b[0]), self.out_hw, self.pad_hw) for b in batch])
+        return bt
 
 
 # ---------------------------------------------------------------------------
@@ -277,23 +292,30 @@ class TileHostCollate(HostCollate):
     """HostCollate plus the tiles of every frame, cropped on the host (numpy
     slices of the decoded frame) and resized with host_resize: "tile_images"
     fp32 [B T, 3, pad_h, pad_w], frame-major, tiles row-major, and "windows":
-    per frame its T windows (x0, y0, tw, th) in source pixels."""
+    per frame its T windows (x0, y0, tw, th) in source pixels.  With ``flip``
+    also "flip_tile_images": host_resize of every crop mirrored inside its own
+    window."""
 
-    def __init__(self, out_hw, pad_hw, tiles, overlap):
-        super().__init__(out_hw, pad_hw)
+    def __init__(self, out_hw, pad_hw, tiles, overlap, flip=False):
+        super().__init__(out_hw, pad_hw, flip)
         self.tiles, self.overlap = (int(tiles[0]), int(tiles[1])), float(overlap)
 
     def __call__(self, batch):
         from .merge import tile_windows
 
         bt = super().__call__(batch)
-        imgs, windows = [], []
+        imgs, flipped, windows = [], [], []
         for frame, _, _ in batch:
             wins = tile_windows(int(frame.shape[1]), int(frame.shape[0]), self.tiles, self.overlap)
             imgs += [host_resize(np.ascontiguousarray(frame[y0:y0 + th, x0:x0 + tw]), self.out_hw, self.pad_hw)
                      for x0, y0, tw, th in wins]
+            if self.flip:
+                flipped += [host_resize(mirrored(frame[y0:y0 + th, x0:x0 + tw]), self.out_hw, self.pad_hw)
+                            for x0, y0, tw, th in wins]
             windows.append(wins)
         bt["tile_images"] = torch.stack(imgs)
+        if self.flip:
+            bt["flip_tile_images"] = torch.stack(flipped)
         bt["windows"] = windows
         return bt
 

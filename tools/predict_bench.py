@@ -11,6 +11,7 @@ the tiled legs fuse the boxes (rtdetr_box_fuse / merge.fuse_reference).
 
   python tools/predict_bench.py [--model rtdetr-r50-moe8-top2] [--n 64] [--batch 16] [--rounds 3] [--workers 4]
   python tools/predict_bench.py --tiles 2x2 [--conf 0.25]
+  python tools/predict_bench.py --flip [--tiles 2x2] [--merge fuse]
 With --track it runs, on the same files (one sequence) and alternately,
 prediction with the tracker on the GPU (MOE_PREDICT_TRACK=1), on the host
 (MOE_PREDICT_TRACK=0) and without it, at conf 0; the random weights score every
@@ -80,6 +81,31 @@ def tiles_leg(a, d: Path, engine):
     print(json.dumps(out), flush=True)
 
 
+def flip_leg(a, d: Path, engine):
+    """Prediction without and with flip test-time augmentation (with --tiles: both tiled), alternated per round."""
+    legs = (("flip_off", False), ("flip_on", True))
+    os.environ["MOE_PREDICT_RESIZE"] = "1"
+    runs = {name: [] for name, _ in legs}
+    for r in range(a.rounds):
+        for name, flip in legs:
+            torch.manual_seed(0)
+            t0 = time.perf_counter()
+            res = engine.predict(a.model, d, batch=a.batch, device=a.device, conf=a.conf, workers=a.workers,
+                                 tiles=a.tiles, merge=a.merge if a.tiles or flip else "nms", flip=flip)
+            line = {"round": r, "leg": name, "images": len(res.predictions),
+                    "detections": sum(len(p.scores) for p in res.predictions),
+                    "wall_s": round(time.perf_counter() - t0, 2), **{k: round(v, 3) for k, v in res.speed.items()}}
+            print(json.dumps(line), flush=True)
+            runs[name].append(res.speed)
+    out = {"model": a.model, "batch": a.batch, "workers": a.workers, "tiles": a.tiles, "conf": a.conf,
+           "merge": a.merge, "flip": True}
+    for name, _ in legs:
+        for k in ("preprocess", "inference", "postprocess"):
+            v = [s[k] for s in runs[name]]
+            out[f"{name}/{k}"] = [round(statistics.median(v), 3), round(min(v), 3), round(max(v), 3)]
+    print(json.dumps(out), flush=True)
+
+
 def track_leg(a, d: Path, engine):
     """Tracking on the GPU, on the host and off, alternated per round."""
     os.environ["MOE_PREDICT_RESIZE"] = "1"
@@ -131,6 +157,8 @@ def main(argv=None):
     ap.add_argument("--track", action="store_true",
                     help="time prediction with the tracker on the GPU, on the host and off (conf 0, one sequence)")
     ap.add_argument("--cmc", action="store_true", help="with --track: add a leg with camera-motion compensation")
+    ap.add_argument("--flip", action="store_true",
+                    help="time prediction with and without flip test-time augmentation (with --tiles: both tiled)")
     a = ap.parse_args(argv)
     if a.cmc and not a.track:
         ap.error("--cmc needs --track")
@@ -157,6 +185,9 @@ def main(argv=None):
                           "host_resize_ms_per_frame_one_core": round(statistics.median(rsz), 2)}), flush=True)
         if a.track:
             track_leg(a, d, engine)
+            return
+        if a.flip:
+            flip_leg(a, d, engine)
             return
         if a.tiles:
             tiles_leg(a, d, engine)
